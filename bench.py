@@ -9,8 +9,11 @@ issueSafe -> cycle -> WinLoss -> auto-reset -> observation -> masks) consumes th
 in HBM; the synthetic random-policy actions of the next step are sampled from the masks it writes and
 written back to that tensor by the same launch (--policy fused, the default: mrts_step_fused_dev,
 bit-identical to the standalone policy kernel) or by a separate policy launch before each step
-(--policy kernel: what an external agent's launch would look like).  The JSON line also carries the
-other form's throughput over the next K steps ("other_policy_form").  Default mask mode "delta":
+(--policy kernel: what an external agent's launch would look like).  A plain run sets up, burns in, warms
+up, times the K steps and prints the headline line; with --full the line also carries everything that
+takes runs of its own: the other form's throughput over the next K steps ("other_policy_form"), the
+roofline block, the full_contract and with_gather windows, the CPU baseline and c3's c2 / c5 child runs.
+--dump-outputs DIR writes the last timed step's tensors to DIR/<name>.npy.  Default mask mode "delta":
 the mask / action tensors are persistent and only rows that changed are rewritten (identical
 contents to a full rewrite, tested); --mask-mode full rewrites every byte.  An env-step is one game-cycle
 (a self-play game counts once, not twice).  Inputs are resident in HBM; nothing crosses PCIe in
@@ -79,6 +82,16 @@ def parse():
                          "from C++; fused policy only, the default there), graph = replay of a captured hipGraph "
                          "(the default for --policy kernel), eager = one Python call per step")
     ap.add_argument("--no-graph", action="store_true", help="alias of --launch eager")
+    ap.add_argument("--full", action="store_true",
+                    help="after the timed window, also measure everything else the line can carry: the step kernel's "
+                         "duration from an eager event pass, the roofline block, the other policy / launch forms, the "
+                         "full_contract and with_gather windows, the CPU baseline and (c3) the c2 / c5 child runs; each "
+                         "can be dropped again with its --no-* option.  Without --full the run sets up, warms up, times "
+                         "the K steps and prints the headline line")
+    ap.add_argument("--dump-outputs", metavar="DIR", default=None,
+                    help="after the timed window, write what its last step left in the caller's tensors (obs, reward, "
+                         "done, masks, actions) to DIR/<name>.npy as float32 / float64; tensors too large for the 64 MB "
+                         "budget are written for a fixed, seeded sample of the slots")
     ap.add_argument("--no-cpu-baseline", action="store_true")
     ap.add_argument("--no-gather-window", action="store_true",
                     help="skip the second timed window with the per-step RCCL observation all-gather (with_gather)")
@@ -616,6 +629,45 @@ def full_contract_window(a, sh, local, base, total_games, world, mdist, torch, d
     return out
 
 
+DUMP_SAMPLE_BYTES = 48 << 20  # --dump-outputs: float32 bytes the per-slot tensors may take together (64 MB in all)
+
+
+def snapshot_outputs(env, torch, masks=True):
+    """--dump-outputs, right after the timed window: device copies of what its last step left in the tensors a
+    caller of the timed path reads — the observation, the rewards and dones, the legal-action masks (where the
+    steps write them) and the action rows (the fused policies write the next step's).  reward / done are whole;
+    the per-slot tensors are whole when they fit DUMP_SAMPLE_BYTES as float32, else the same seeded sample of
+    slots (numpy default_rng(SEED), sorted) of each: the same arguments give the same slots in every build."""
+    import numpy as np
+
+    per_slot = {"obs": env.obs, "actions": env.actions}
+    if masks and env.masks is not None:
+        per_slot["masks"] = env.masks
+    S = env.obs.shape[0]
+    n = max(1, min(S, DUMP_SAMPLE_BYTES // (4 * sum(t[0].numel() for t in per_slot.values()))))
+    if n < S:
+        sel = torch.from_numpy(np.sort(np.random.default_rng(SEED).choice(S, n, replace=False))).to(env.device)
+        outs = {k: t.index_select(0, sel) for k, t in per_slot.items()}
+    else:
+        outs = {k: t.clone() for k, t in per_slot.items()}
+    outs["reward"] = env.reward.clone()
+    outs["done"] = env.done.clone()
+    torch.cuda.synchronize(env.device)
+    return outs
+
+
+def write_outputs(path, outs, rank=0):
+    """DIR/<name>.npy (rank 0; DIR/<name>.rank<r>.npy for the other ranks' shards): float64 stays, the integer
+    tensors become float32 (every value is far below 2^24, so the conversion is exact)."""
+    import numpy as np
+
+    os.makedirs(path, exist_ok=True)
+    for name, t in outs.items():
+        arr = t.cpu().numpy()
+        arr = arr if arr.dtype == np.float64 else arr.astype(np.float32)
+        np.save(os.path.join(path, name + (f".rank{rank}" if rank else "") + ".npy"), arr)
+
+
 def child_env(environ):
     """The environment of a child bench.py run: a fresh one-rank run, so none of a launcher's rendezvous variables
     (under torch.distributed.run, TORCHELASTIC_USE_AGENT_STORE would make the child's process group wait as a
@@ -628,7 +680,7 @@ def child_env(environ):
 def other_configs(a, timeout=240.0):
     """the other single-GPU BASELINE configs in the driver's own line — c2 (configs[1]: 8x8, 1024
     games, unmasked uniform rows) and c5 (configs[4] per GPU: 32x32, 2048 partially observable games, masked
-    policy) — each a child bench.py with the same K / W / burn-in, run after this process has released its
+    policy) — each a child `bench.py --full` with the same K / W / burn-in, run after this process has released its
     handle and process group; its JSON line (value, ms_per_step, roofline with the matching-hash PMC file,
     cpu_baseline, ...) nested under its name.  When the driver's K is not 200, each of c2 / c3 / c5 also gets a
     quick K = 200 child without the CPU baseline (`configs.c2.k200`, `configs.c5.k200`, `configs.c3_k200`), the
@@ -638,7 +690,8 @@ def other_configs(a, timeout=240.0):
     env = child_env(os.environ)
 
     def child(cfg, extra):
-        cmd = [sys.executable, os.path.abspath(__file__), "--config", cfg, "--warmup", str(a.warmup), "--burnin", str(a.burnin)]
+        cmd = [sys.executable, os.path.abspath(__file__), "--full", "--config", cfg, "--warmup", str(a.warmup), "--burnin",
+               str(a.burnin)]
         cmd += extra
         t0 = time.perf_counter()
         try:
@@ -701,6 +754,8 @@ def main_c1(a, json_fd):
     graph.replay()
     torch.cuda.synchronize()
     t = time.perf_counter() - t0
+    if a.dump_outputs:
+        write_outputs(a.dump_outputs, snapshot_outputs(env, torch, masks=False))
     assert not env.error_flags().any()
     out = {
         "metric": METRIC, "value": a.steps / t, "unit": "env-steps/s", "n_gpus": 1, "rccl_world_size": 1,
@@ -712,7 +767,7 @@ def main_c1(a, json_fd):
                    "burnin_steps": a.burnin, "launch": "hipGraph replay of the K timed steps",
                    "parallelism": "single env"},
     }
-    if not a.no_cpu_baseline:
+    if a.full and not a.no_cpu_baseline:
         out["cpu_baseline"] = cpu_baseline_c1(os.path.join(ROOT, a.map))
     sys.stdout.flush()
     os.write(json_fd, (json.dumps(out) + "\n").encode())
@@ -742,13 +797,15 @@ def main():
     rank = int(os.environ.get("RANK", "0"))
     local = int(os.environ.get("LOCAL_RANK", "0"))
     torch.cuda.set_device(local)
-    # a process group always: RCCL over xGMI between the ranks, and at N = 1 a one-rank group for the
-    # with-exchange window (SURVEY.md §8e's second curve)
+    # a process group: RCCL over xGMI between the ranks, and at N = 1 a one-rank group for the exchanges
+    # (--gather-obs, and --full's with-exchange window: SURVEY.md §8e's second curve); a plain one-rank
+    # run has no collective and starts none
     pg_error = None
     if world == 1 and "MASTER_PORT" not in os.environ:
         os.environ.update(MASTER_ADDR="127.0.0.1", MASTER_PORT=str(free_port()), RANK="0", WORLD_SIZE="1")
     try:
-        dist.init_process_group("nccl", device_id=torch.device("cuda", local), rank=rank, world_size=world)
+        if world > 1 or a.full or a.gather_obs:
+            dist.init_process_group("nccl", device_id=torch.device("cuda", local), rank=rank, world_size=world)
     except Exception as ex:  # only tolerated at N = 1 (then no exchange window)
         if world > 1:
             raise
@@ -833,15 +890,15 @@ def main():
     env.synchronize()
     # rows decoded per step (sum of mask[...,0]) and live units, for the algorithmic-byte count —
     # taken after the burn-in, so that the warmup steps run right before the timed window (no host
-    # work leaves the GPU idle in between)
-    if uniform:  # the steps write no masks: one untimed mask write to count the idle units
+    # work leaves the GPU idle in between); only --full's roofline block needs them
+    if a.full and uniform:  # the steps write no masks: one untimed mask write to count the idle units
         env.get_masks()
         env.synchronize()
-    rows = float(env.masks[..., 0].sum().item()) / S
+    rows = float(env.masks[..., 0].sum().item()) / S if a.full else None
     units = []
-    for s in range(0, min(S, 64), 2):
+    for s in range(0, min(S, 64), 2) if a.full else ():
         units.append(env.dump_state(s)[4])
-    mean_units = float(np.mean(units))
+    mean_units = float(np.mean(units)) if a.full else None
 
     # The K timed steps are enqueued so that host launch overhead does not pace the GPU: by default
     # (fused policy) one native call, mrts_rollout_fused_dev, issues the K step launches from C++;
@@ -908,7 +965,9 @@ def main():
     if world > 1:
         dist.barrier()
     t = time.perf_counter() - t0
-    if native or graph is not None:  # kernel-duration pass (untimed for `value`)
+    # --dump-outputs: the last timed step's tensors, copied before anything else runs on the handle
+    dumped = snapshot_outputs(env, torch, masks=not uniform) if a.dump_outputs else None
+    if a.full and (native or graph is not None):  # kernel-duration pass (untimed for `value`)
         # hold the stream in a GPU spin while the host enqueues the K eager steps, so each event
         # pair brackets back-to-back kernels instead of the host's launch latency
         try:
@@ -920,8 +979,9 @@ def main():
         torch.cuda.synchronize(env.device)
         base += a.steps
     t = mdist.max_over_ranks(t, env.device)
-    step_ms = [s.elapsed_time(e) for s, e in evs]
-    kern_ms = float(np.mean(step_ms))
+    # the per-launch events were recorded by --full's eager pass, or inside an eager timed window
+    step_ms = [s.elapsed_time(e) for s, e in evs] if a.full or not (native or graph is not None) else None
+    kern_ms = float(np.mean(step_ms)) if step_ms else None
     single_kern_ms = kern_ms  # one step per launch (the eager event pass)
     launch_ms = None
     if roll_ev is not None:  # the multi-step launch: its duration / K is the per-step kernel time
@@ -929,6 +989,84 @@ def main():
         kern_ms = launch_ms / a.steps
     flags = env.error_flags()
     assert not flags.any(), f"engine error flags set: {np.unique(flags)}"
+    if dumped is not None:
+        write_outputs(a.dump_outputs, dumped, rank)
+        del dumped
+    uni_fused = uniform and mode["uni_fused"]
+    total_games = E * world
+    value = total_games * a.steps / t
+    out = {
+        "metric": METRIC,
+        "value": value,
+        "unit": "env-steps/s",
+        "n_gpus": world,
+        "rccl_world_size": rccl_world,
+        "steps": a.steps,
+        "warmup": a.warmup,
+        "ms_per_step": 1e3 * t / a.steps,
+        "higher_is_better": True,
+        "scaling": "weak",
+        "vs_baseline": None,
+        "dtype": "int32",
+        "data": ("synthetic (unmasked uniform random rows for every cell, Philox seed 0x5EEDC0DE)" if uniform
+                 else "synthetic (masked uniform random policy, Philox seed 0x5EEDC0DE)"),
+        "parity": "bit-exact: the reference's 280 recorded games (data/traces, 17,085 entries) replay through these HIP "
+                  "kernels with every PhysicalGameState equal to the trace's (tests/test_gpu_traces.py); every output vs the "
+                  "trace-pinned C++ oracle (tests/test_gpu_parity.py, test_headline_parity.py at this config's full size, "
+                  "test_kats.py); Java itself cannot run in this image",
+        "config": {
+            "workload": f"{a.config}: {a.map} self-play, {E} games/GPU ({2 * E} player slots), "
+                        + ("obs every step, no masks (SURVEY §8(d) c2)" if uniform else "masks+obs every step")
+                        + (", partial observability" if a.po else "")
+                        + (f", max_units {a.max_units} (capacity errors checked)" if a.max_units else "")
+                        + (f", UTT version {a.utt}" if a.utt != 1 else ""),
+            "envs_per_gpu": E,
+            "utt": utt_name,
+            "reward_functions": "[WinLossRewardFunction] (with one reward function Java's self-play reset throws, "
+                                "JNIGridnetClientSelfPlay.java:235-238; here the one slot is zeroed — DESIGN.md §8)",
+            "max_steps": 2000,
+            "burnin_steps": a.burnin,
+            "mask_mode": "off" if uniform else a.mask_mode,
+            "launch": (f"one {'mrts_rollout_uniform_dev' if uniform else 'mrts_rollout_fused_dev'} call: ONE k_env launch runs the K steps of every game (multi-step "
+                       "launch, each game's state kept in LDS between its steps; every step's observation, masks, "
+                       "rewards, dones and next action rows written to HBM)" if multi
+                       else "one mrts_rollout_uniform_dev call (K fused policy+step launches from C++)" if native and uni_fused
+                       else "one mrts_rollout_uniform_dev call (K policy + K step launches from C++)" if native and uniform
+                       else "one mrts_rollout_fused_dev call (K step launches from C++)" if native
+                       else "hipGraph replay of the K timed steps" if graph is not None else "eager"),
+            "policy": ("unmasked uniform rows drawn and written by the step kernel (mrts_step_uniform_dev, "
+                       "bit-identical to a policy launch + a step launch)" if uni_fused
+                       else "unmasked uniform rows, separate kernel before each step (mrts_policy_uniform_dev, inside the "
+                       "timed window)" if uniform
+                       else "fused into the step kernel (mrts_step_fused_dev)" if fused
+                       else "separate masked-uniform policy kernel before each step (mrts_policy_dev)"),
+            "kernel_timing": (f"{event_kind} recorded by the multi-step launch's own dispatch in the timed window "
+                              "(mrts_set_rollout_events: hipExtLaunchKernelGGL start / stop events), / K" if launch_ms is not None
+                              else "not taken (--full adds an eager event pass)" if kern_ms is None
+                              else f"{event_kind} around each step-kernel launch, eager pass over the next K steps"
+                              if (native or graph is not None) else f"{event_kind} around each step-kernel launch in the timed window"),
+            "parallelism": f"dp{world} (independent env shards)" + (
+                f", per-step RCCL int16 observation {a.gather_obs} overlapped on a comm stream"
+                + (" (int16 transport written by the step kernel)" if kernel16 else "") if gather_buf is not None
+                else ", no collective in the step"),
+        },
+        "step_kernel_ms": kern_ms,
+        "launch_ms": launch_ms,
+    }
+
+    def finish():  # release the handle and the process group, then the one JSON line (rank 0)
+        env.close()
+        if use_pg:
+            dist.destroy_process_group()
+        if rank == 0 and a.full and world == 1 and a.config == "c3" and not a.no_other_configs and a.utt == 1 \
+                and a.envs == CONFIGS["c3"][1]:
+            out["configs"] = other_configs(a)
+        if rank == 0:
+            sys.stdout.flush()
+            os.write(json_fd, (json.dumps(out) + "\n").encode())
+
+    if not a.full:  # the plain run ends here: everything below takes runs of its own
+        return finish()
 
     # Roofline bytes per step-kernel launch.  The step's HBM contract under the persistent-buffer
     # (delta) mask mode — what any implementation must move:
@@ -969,7 +1107,6 @@ def main():
     # step writes that word next to the 28-B row it leaves in the action tensor
     # fused uniform policy: no row is read (the idle units' rows are drawn in registers), and every row
     # of the action tensor is written by the step kernel
-    uni_fused = uniform and mode["uni_fused"]
     row_in = 4 if fused else 0 if uni_fused else 28
     # per game: the state (header + unit rows) read and written, the terrain read, both players' row sets
     # read and written — per step; a multi-step launch keeps state, terrain, row sets and forwarded
@@ -1064,64 +1201,7 @@ def main():
                                         "bytes)".format(issue["frac"], issue.get("games_per_simd") or 0, hbm_frac))
     else:
         bound, bound_note = "hbm", "HBM step-contract bytes (no counter file of this library for this workload)"
-    total_games = E * world
-    value = total_games * a.steps / t
-    out = {
-        "metric": METRIC,
-        "value": value,
-        "unit": "env-steps/s",
-        "n_gpus": world,
-        "rccl_world_size": rccl_world,
-        "steps": a.steps,
-        "warmup": a.warmup,
-        "ms_per_step": 1e3 * t / a.steps,
-        "higher_is_better": True,
-        "scaling": "weak",
-        "vs_baseline": None,
-        "dtype": "int32",
-        "data": ("synthetic (unmasked uniform random rows for every cell, Philox seed 0x5EEDC0DE)" if uniform
-                 else "synthetic (masked uniform random policy, Philox seed 0x5EEDC0DE)"),
-        "parity": "bit-exact: the reference's 280 recorded games (data/traces, 17,085 entries) replay through these HIP "
-                  "kernels with every PhysicalGameState equal to the trace's (tests/test_gpu_traces.py); every output vs the "
-                  "trace-pinned C++ oracle (tests/test_gpu_parity.py, test_headline_parity.py at this config's full size, "
-                  "test_kats.py); Java itself cannot run in this image",
-        "config": {
-            "workload": f"{a.config}: {a.map} self-play, {E} games/GPU ({2 * E} player slots), "
-                        + ("obs every step, no masks (SURVEY §8(d) c2)" if uniform else "masks+obs every step")
-                        + (", partial observability" if a.po else "")
-                        + (f", max_units {a.max_units} (capacity errors checked)" if a.max_units else "")
-                        + (f", UTT version {a.utt}" if a.utt != 1 else ""),
-            "envs_per_gpu": E,
-            "utt": utt_name,
-            "reward_functions": "[WinLossRewardFunction] (with one reward function Java's self-play reset throws, "
-                                "JNIGridnetClientSelfPlay.java:235-238; here the one slot is zeroed — DESIGN.md §8)",
-            "max_steps": 2000,
-            "burnin_steps": a.burnin,
-            "mask_mode": "off" if uniform else a.mask_mode,
-            "launch": (f"one {'mrts_rollout_uniform_dev' if uniform else 'mrts_rollout_fused_dev'} call: ONE k_env launch runs the K steps of every game (multi-step "
-                       "launch, each game's state kept in LDS between its steps; every step's observation, masks, "
-                       "rewards, dones and next action rows written to HBM)" if multi
-                       else "one mrts_rollout_uniform_dev call (K fused policy+step launches from C++)" if native and uni_fused
-                       else "one mrts_rollout_uniform_dev call (K policy + K step launches from C++)" if native and uniform
-                       else "one mrts_rollout_fused_dev call (K step launches from C++)" if native
-                       else "hipGraph replay of the K timed steps" if graph is not None else "eager"),
-            "policy": ("unmasked uniform rows drawn and written by the step kernel (mrts_step_uniform_dev, "
-                       "bit-identical to a policy launch + a step launch)" if uni_fused
-                       else "unmasked uniform rows, separate kernel before each step (mrts_policy_uniform_dev, inside the "
-                       "timed window)" if uniform
-                       else "fused into the step kernel (mrts_step_fused_dev)" if fused
-                       else "separate masked-uniform policy kernel before each step (mrts_policy_dev)"),
-            "kernel_timing": (f"{event_kind} recorded by the multi-step launch's own dispatch in the timed window "
-                              "(mrts_set_rollout_events: hipExtLaunchKernelGGL start / stop events), / K" if launch_ms is not None
-                              else f"{event_kind} around each step-kernel launch, eager pass over the next K steps"
-                              if (native or graph is not None) else f"{event_kind} around each step-kernel launch in the timed window"),
-            "parallelism": f"dp{world} (independent env shards)" + (
-                f", per-step RCCL int16 observation {a.gather_obs} overlapped on a comm stream"
-                + (" (int16 transport written by the step kernel)" if kernel16 else "") if gather_buf is not None
-                else ", no collective in the step"),
-        },
-        "step_kernel_ms": kern_ms,
-        "launch_ms": launch_ms,
+    out.update({
         "single_step_launch_kernel_ms": single_kern_ms,
         "mean_units": mean_units,
         "decoded_rows_per_slot": rows,
@@ -1146,7 +1226,7 @@ def main():
             "survey_8d_bytes_per_launch": survey,
             "survey_8d_equivalent_GBps": survey / (kern_ms * 1e-3) / 1e9,
         },
-    }
+    })
     if traffic:
         # the PMC bytes against the contract: below it, the outputs rewritten every step stay in L2 / MALL between
         # launches (c2: 1024 games' planes), so frac is a fraction of the contract's bytes, not of HBM bytes moved
@@ -1245,14 +1325,7 @@ def main():
     if rank == 0 and world == 1 and not a.no_cpu_baseline:
         out["cpu_baseline"] = cpu_baseline(os.path.join(ROOT, a.map), a.cpu_threads or all_cores(), a.burnin, uniform, po=a.po,
                                            utt=a.utt)
-    env.close()
-    if use_pg:
-        dist.destroy_process_group()
-    if rank == 0 and world == 1 and a.config == "c3" and not a.no_other_configs and a.utt == 1 and a.envs == CONFIGS["c3"][1]:
-        out["configs"] = other_configs(a)
-    if rank == 0:
-        sys.stdout.flush()
-        os.write(json_fd, (json.dumps(out) + "\n").encode())
+    finish()
 
 
 if __name__ == "__main__":

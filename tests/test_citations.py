@@ -2,7 +2,10 @@
 point at this reference snapshot (Weak #3: citations copied from upstream-microRTS line
 numbers pointed past the end of files or at the wrong method).
 
-Three checks, CPU-only, skipped where /root/reference is absent (the GPU box):
+The reference's side of the checks is tests/golden/java_index.json (tests/golden/make_java_index.py: every Java
+file's path in the reference tree, its line count and its methods' line spans), so they run from the checkout.
+
+Three checks, CPU-only:
 1. every cited file exists in the reference and every cited line range lies inside it;
 2. where a citation directly follows a Java method name — `name (File.java:N-M)` — the range overlaps
    that method's body in the cited file;
@@ -12,33 +15,34 @@ Three checks, CPU-only, skipped where /root/reference is absent (the GPU box):
    method is defined there — with a test that each resolution form reports a wrong citation.
 """
 import collections
-import glob
+import json
 import os
 import re
-import subprocess
 
-import pytest
-
-REF = "/root/reference"
 ROOT = os.path.dirname(os.path.dirname(os.path.abspath(__file__)))
+# "/<path in the reference tree>" -> [lines, {method: [[first, last], ...]}]
+JAVA = {"/" + k: v for k, v in json.load(open(os.path.join(ROOT, "tests", "golden", "java_index.json"))).items()}
 CANONICAL = ("/src/tests/", "/src/rts/", "/src/ai/jni/", "/src/ai/reward/", "/src/util/", "/test/")
 CITE = re.compile(r"((?:[\w.]+/)*)(\w+\.java):(\d+(?:-\d+)?(?:,\s?\d+(?:-\d+)?)*)")
 # `Class.method (File.java:N-M)`: a method named with its class (or in backticks) right before it
 CALLED = re.compile(r"(?:\.|`)([a-z]\w{3,})`?\s*\(\s*(?:[\w.]+/)*(\w+\.java):(\d+(?:-\d+)?(?:,\s?\d+(?:-\d+)?)*)")
-DEF = re.compile(r"^\s*(?:public|private|protected|static|final|synchronized|abstract|\s)*[\w<>\[\],\s]+?\s(\w+)\s*\([^;]*$")
-
-pytestmark = pytest.mark.skipif(not os.path.isdir(os.path.join(REF, "src")), reason="reference tree not present")
 
 
 def _sources():
-    out = subprocess.check_output(["git", "ls-files", "oracle", "microrts_amd", "include", "tests", "tools", "bench.py",
-                                   "__graft_entry__.py", "DESIGN.md", "INTEGRATION.md", "README.md"], cwd=ROOT).decode()
-    return [f for f in out.split() if f.endswith((".cpp", ".hpp", ".hip", ".h", ".py", ".md", ".sh"))]
+    """The source files of the tree, by walking it (a checkout need not carry git's metadata); build outputs
+    and scratch files (oracle/build, oracle/_ref, caches, tools/_*) are no sources."""
+    out = ["bench.py", "__graft_entry__.py", "DESIGN.md", "INTEGRATION.md", "README.md"]
+    for top in ("oracle", "microrts_amd", "include", "tests", "tools"):
+        for d, dirs, files in os.walk(os.path.join(ROOT, top)):
+            dirs[:] = sorted(x for x in dirs if x not in ("build", "_ref", "__pycache__") and not x.startswith("."))
+            rel = os.path.relpath(d, ROOT)
+            out += [os.path.join(rel, f) for f in sorted(files) if not (rel == "tools" and f.startswith("_"))]
+    return [f for f in out if f.endswith((".cpp", ".hpp", ".hip", ".h", ".py", ".md", ".sh"))]
 
 
 def _index():
     idx = collections.defaultdict(list)
-    for p in glob.glob(os.path.join(REF, "**", "*.java"), recursive=True):
+    for p in sorted(JAVA):
         idx[os.path.basename(p)].append(p)
     return idx
 
@@ -58,25 +62,10 @@ def _spans(text):
         yield int(a), int(b) if b else int(a)
 
 
-def _methods(path, cache={}):
-    if path not in cache:
-        lines = open(path, errors="replace").read().split("\n")
-        out = collections.defaultdict(list)
-        for i, line in enumerate(lines):
-            m = DEF.match(line)
-            if not m or m.group(1) in ("if", "for", "while", "switch", "catch", "return", "new"):
-                continue
-            depth, started, j = 0, False, i
-            while j < len(lines):
-                for ch in lines[j]:
-                    depth += (ch == "{") - (ch == "}")
-                    started = started or ch == "{"
-                if (started and depth <= 0) or (not started and lines[j].rstrip().endswith(";")):
-                    break
-                j += 1
-            out[m.group(1)].append((i + 1, j + 1))
-        cache[path] = (out, len(lines) - (lines[-1] == ""))
-    return cache[path]
+def _methods(path):
+    """-> ({method name: [[first line, last line], ...]}, number of lines) of an indexed Java file."""
+    n, defs = JAVA[path]
+    return defs, n
 
 
 def test_citations_point_into_the_reference():
@@ -92,7 +81,7 @@ def test_citations_point_into_the_reference():
                 n = _methods(path)[1]
                 for a, b in _spans(m.group(3)):
                     if a < 1 or b < a or b > n:
-                        bad.append(f"{f}:{ln}: {m.group(0)}: {os.path.relpath(path, REF)} has {n} lines")
+                        bad.append(f"{f}:{ln}: {m.group(0)}: {path[1:]} has {n} lines")
     assert not bad, "\n".join(bad)
 
 
@@ -151,7 +140,7 @@ def _check_bare(text_lines, idx, name):
     for ln, spans, path, meth in _bare_citations(text_lines, idx):
         methods, n = _methods(path)
         sp = list(_spans(spans))
-        rel = os.path.relpath(path, REF)
+        rel = path[1:]
         if any(a < 1 or b < a or b > n for a, b in sp):
             bad.append(f"{name}:{ln}: :{spans} resolved to {rel}, which has {n} lines")
             continue

@@ -1,5 +1,5 @@
 #!/bin/bash
-# Per-config GPU profile (run through gpurun): the bench line, rocprofv3 kernel-trace stats of the
+# Per-config GPU profile (results under $MRTS_OUT, default out/): the bench line, rocprofv3 kernel-trace stats of the
 # same command, the FETCH_SIZE and WRITE_SIZE passes (separate: TCC slots), and one SQ issue pass
 # (VALU / SALU instruction counts, VALU-active and thread cycles = lane utilisation, dual-issue
 # quad-cycles, wave cycles; GRBM_GUI_ACTIVE for the clock).  Summarise with tools/profile_summary.py.
@@ -10,9 +10,9 @@ CFG=${2:-c3}
 shift 2
 cd "${GRAFT_REPO_ROOT:-.}"
 export TMPDIR=/tmp
-OUT=gpurun_out/$TAG/$CFG
+OUT=${MRTS_OUT:-out}/$TAG/$CFG
 mkdir -p "$OUT"
-BARGS="--config $CFG --steps 100 --warmup 10 --burnin 1000 --no-cpu-baseline --no-compare --no-gather-window --no-full-contract --no-other-configs $*"
+BARGS="--full --config $CFG --steps 100 --warmup 10 --burnin 1000 --no-cpu-baseline --no-compare --no-gather-window --no-full-contract --no-other-configs $*"
 SQ="SQ_INSTS_VALU SQ_INSTS_SALU SQ_ACTIVE_INST_VALU SQ_THREAD_CYCLES_VALU SQ_ACTIVE_INST_VALU2 SQ_WAVE_CYCLES SQ_ACTIVE_INST_SCA SQ_INSTS_LDS GRBM_GUI_ACTIVE"
 # the counters describe THIS library: bench.py ignores a pmc_<cfg>.json whose hash differs
 python -c "from microrts_amd._lib import device_code_sha256; print(device_code_sha256())" > "$OUT/code.sha256" || exit $?

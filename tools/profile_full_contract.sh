@@ -1,14 +1,14 @@
 #!/bin/bash
-# The full-contract leg under rocprofv3 (run through gpurun): an unprofiled pass (its JSON line), the
+# The full-contract leg under rocprofv3 (results under $MRTS_OUT, default out/): an unprofiled pass (its JSON line), the
 # kernel trace, and the FETCH_SIZE / WRITE_SIZE passes (separate: TCC slots).  Summarise with
-# python tools/full_contract_pmc.py summarize gpurun_out/<tag>/fc_<cfg> <tag>.
+# python tools/full_contract_pmc.py summarize $MRTS_OUT/<tag>/fc_<cfg> <tag>.
 # Usage: bash tools/profile_full_contract.sh <tag> [c3]
 set -o pipefail
 TAG=${1:?tag}
 CFG=${2:-c3}
 cd "${GRAFT_REPO_ROOT:-.}"
 export TMPDIR=/tmp
-OUT=gpurun_out/$TAG/fc_$CFG
+OUT=${MRTS_OUT:-out}/$TAG/fc_$CFG
 mkdir -p "$OUT"
 A="tools/full_contract_pmc.py run --config $CFG --steps 20"
 python -c "from microrts_amd._lib import device_code_sha256; print(device_code_sha256())" > "$OUT/code.sha256" || exit $?

@@ -1,13 +1,13 @@
 #!/bin/bash
 # SQ instruction-mix counters of the bench command, one rocprofv3 --pmc pass per counter group
-# (run through gpurun).  Usage: bash tools/sq_counters.sh <tag>; summarise with tools/sq_summary.py.
+# (results under $MRTS_OUT, default out/).  Usage: bash tools/sq_counters.sh <tag>; summarise with tools/sq_summary.py.
 set -o pipefail
 TAG=${1:-sq}
 cd "${GRAFT_REPO_ROOT:-.}"
 export TMPDIR=/tmp
-OUT=gpurun_out/$TAG
+OUT=${MRTS_OUT:-out}/$TAG
 mkdir -p "$OUT"
-BARGS=${SQ_BARGS:-"--steps 100 --warmup 10 --burnin 1000 --no-cpu-baseline --no-graph"}
+BARGS=${SQ_BARGS:-"--full --steps 100 --warmup 10 --burnin 1000 --no-cpu-baseline --no-graph"}
 i=0
 for grp in "SQ_WAVE_CYCLES SQ_ACTIVE_INST_ANY SQ_WAIT_ANY SQ_WAIT_INST_ANY" \
            "SQ_INSTS_VALU SQ_INSTS_SALU SQ_INSTS_LDS SQ_INSTS_SMEM" \
