@@ -234,6 +234,9 @@ DEV int lane_id() { return (int)threadIdx.x; }
 #ifndef MRTS_CONF_LDS  // acceptChainReg's parallel-path conflict test through an LDS copy of the reservations (round 5)
 #define MRTS_CONF_LDS 1
 #endif
+#ifndef MRTS_ISSUE_BOTH  // selfPlayFast issues both players' rows in one pass when no row of either interacts (round 7)
+#define MRTS_ISSUE_BOTH 1
+#endif
 #ifndef MRTS_XOR3  // Philox's xors as one three-input bit op (round 5); 0 = plain C
 #define MRTS_XOR3 1
 #endif
@@ -1157,7 +1160,40 @@ struct Game {
         const uint32_t adec = pack_ua(t, ut, tx, ty);
         const int c = uy(cu) * W + ux(cu);
         MPHASE(1);
-        for (int p = 0; p < 2; p++) {
+        bool merged = false;
+#if MRTS_ISSUE_BOTH
+        // both players' rows in one pass when none interacts (issueBothTest); not with the reward counters
+        // (issueBatch books them per player)
+        if (useIx && MRTS_LIKELY(!(D.reward_need & RN_COUNTS))) {
+            int s0, s1, mc0, mc1;
+            const bool both = issueBothTest(idle && !bad, cu, adec, pr, s0, s1, mc0, mc1);
+#ifdef MRTS_PHASE_TIMING
+#ifndef MRTS_SPAN_ONLY
+            phAcc[25] += 1000;  // merged issue: attempts, and hits (x1000 each)
+            if (both) phAcc[26] += 1000;
+#endif
+#endif
+            MPHASE(2);
+            if (both) {
+#ifdef MRTS_ABLATE
+                if (ab(AB_ISSUE)) {  // the merged pass once more: the test (scratch only), then the writes (idempotent)
+                    int q0, q1, d0, d1;
+                    keepv((int)issueBothTest(idle && !bad, launder(cu), launder(adec), launder(pr), q0, q1, d0, d1));
+                    const int seqS = seq, sp0 = sumProd0, sp1 = sumProd1, mp0 = maxProd0, mp1 = maxProd1;
+                    const bool amp = anyMP;
+                    issueBothWrite(idle && !bad, bad, launder(cu), launder(adec), launder(pr), q0, q1, d0, d1);
+                    seq = seqS, sumProd0 = sp0, sumProd1 = sp1, maxProd0 = mp0, maxProd1 = mp1, anyMP = amp;
+                }
+#endif
+                issueBothWrite(idle && !bad, bad, cu, adec, pr, s0, s1, mc0, mc1);
+                MPHASE(3);
+                merged = true;
+            }
+        }
+#endif
+        // (the merged pass skips the loop rather than returning: with the early return the c3 kernel's register
+        // allocation spilled 19 VGPRs in the mask phase instead of 4)
+        for (int p = merged ? 2 : 0; p < 2; p++) {
             if (po) {  // the views, in Java's order (see above)
                 if (p == 0) {
                     if (!snapTaken) snapshotBoth();
@@ -1234,6 +1270,119 @@ struct Game {
             wsync();
             MPHASE(3);
         }
+    }
+    // The PRODUCE lanes' costs per player (sum, largest) added to s0 / s1 / mc0 / mc1: a walk over their
+    // lanes, or whole-wave reductions (see `walk`)
+    DEV void prodCosts(bool np, int cost, int pl, int& s0, int& s1, int& mc0, int& mc1) const {
+        if (walk) {
+            for (uint64_t mm = ballot(np); mm; mm &= mm - 1) {
+                const int kv = uni(rl(cost | (pl << 16), __builtin_ctzll(mm)));
+                const int k = kv & 0xFFFF;
+                if ((kv >> 16) == 0) {
+                    mc0 = max(mc0, k);
+                    s0 += k;
+                } else {
+                    mc1 = max(mc1, k);
+                    s1 += k;
+                }
+            }
+        } else if (ballot(np)) {
+            mc0 = max(mc0, -wave_min(np && pl == 0 ? -cost : 1));
+            mc1 = max(mc1, -wave_min(np && pl == 1 ? -cost : 1));
+            s0 += wave_sum(np && pl == 0 ? cost : 0);
+            s1 += wave_sum(np && pl == 1 ? cost : 0);
+        }
+    }
+    // selfPlayFast's two issueSafe passes as one (round 7), for the step in which no
+    // candidate row of either player interacts with a reservation or with another row:
+    //  (a) no MOVE / PRODUCE candidate of either player uses a position that is reserved already or that
+    //      another candidate uses (the ResourceUsage positions, PlayerAction.java:400-415), and
+    //  (b) per player, the present PRODUCE costs plus every candidate's cost fit the resources
+    //      (ResourceUsage.java:31-50).
+    // Then player 0's acceptance chain accepts every row (its parallel form's own condition), so does
+    // player 1's against the reservations with player 0's rows added ((a) covers them, (b) keeps either
+    // player's running sum from blocking the other), and every GameState.issue (GameState.java:252-326)
+    // of either pa takes its no-conflict branch: each cost test there is a single or pairwise sum bounded
+    // by (b)'s totals.  issueSafe's legality rewrite (:338-408) only turns rows into NONE, which removes
+    // users of (a) and (b).  The state after both passes is then a function of the union of the rows:
+    // the insertion order is [p0 accepted, by cell][p0 fills][p1 accepted, by cell][p1 fills].
+    // The test writes nothing but the `rseq` scratch; false = not taken, nothing changed.
+    DEV bool issueBothTest(bool cand, uint32_t cu, uint32_t adec, int pr, int& s0, int& s1, int& mc0, int& mc1) const {
+        const int l = lid();
+        const int NB = (HW + 2 * W + 31) / 32;
+        const int t = ua_type(adec);
+        const bool up = cand && (t == T_MOVE || t == T_PRODUCE), prod = cand && t == T_PRODUCE;
+        const int tpos = (uy(cu) + dyo(pr) + 1) * W + ux(cu) + dxo(pr);  // ResourceUsage position, as acceptChain
+        uint32_t* cp = (uint32_t*)rseq;  // free here (acceptChainReg's own copy lives there too)
+        if (l < NB) cp[l] = bits[l];
+        wsync();
+        bool conf = false;
+        if (up) conf = (atomicOr(&cp[tpos >> 5], 1u << (tpos & 31)) >> (tpos & 31)) & 1u;
+        wsync();
+        s0 = sumProd0;
+        s1 = sumProd1;
+        mc0 = maxProd0;
+        mc1 = maxProd1;
+        prodCosts(prod, prod ? U.cost[ua_ut(adec)] : 0, uplay(cu), s0, s1, mc0, mc1);
+        return !ballot(conf) && s0 <= pres0 && s1 <= pres1;
+    }
+    // the writes of both pa's after issueBothTest passed: s0 / s1 / mc0 / mc1 are its PRODUCE sums
+    DEV void issueBothWrite(bool cand, bool bad, uint32_t cu, uint32_t adec, int pr, int s0, int s1, int mc0, int mc1) {
+        const int l = lid();
+        const int pl = uplay(cu);
+        const uint64_t mU = ballot(cand);
+        const int n1 = __popcll(ballot(cand && pl == 1)), n0 = __popcll(mU) - n1;
+        // rank among the union by (player, cell): player 0's rows are ranked by cell as cellRank does,
+        // player 1's follow (their rank by cell + n0)
+        const int key = (int)(((cu >> 20) & 3) << 16 | (cu & 0xFFFFu));  // player + 1, y, x
+        int r = 0;
+        for (uint64_t mm = mU; mm; mm &= mm - 1) r += rl(key, __builtin_ctzll(mm)) < key;
+        // fillWithNones of each player: its idle units left without a row (bad produce type), list order
+        const uint64_t mfU = ballot(bad);
+        int f0 = 0;
+        if (MRTS_UNLIKELY(mfU != 0)) {
+            const uint64_t mf1 = ballot(bad && pl == 1), mf0 = mfU & ~mf1;
+            f0 = __popcll(mf0);
+            if (bad) {
+                ua[l] = pack_ua(T_NONE, 0, 0, 0) | UA_PRESENT;
+                par[l] = 1;
+                at[l] = time;
+                as[l] = seq + (pl == 0 ? n0 + lanes_below(mf0) : n0 + f0 + n1 + lanes_below(mf1));
+            }
+        }
+        const bool prodRow = cand && ua_type(adec) == T_PRODUCE;
+        if (!fwdOn) {  // as selfPlayFast: forwarded rows are legal, any other is tested
+            int t = ua_type(adec), ut = ua_ut(adec), tx = ua_tx(adec), ty = ua_ty(adec);
+            if (cand) legality(l, cu, t, pr, tx, ty, ut);
+            adec = pack_ua(t, ut, tx, ty);
+            wsync();
+        }
+        const int t = ua_type(adec);
+        const bool mp = cand && (t == T_MOVE || t == T_PRODUCE), np = cand && t == T_PRODUCE;
+        if (cand) {
+            ua[l] = adec | UA_PRESENT;
+            par[l] = (int16_t)pr;
+            at[l] = time;
+            as[l] = seq + r + (pl == 0 ? 0 : f0);
+            // a legal MOVE / PRODUCE keeps its direction: the issue index takes the position the test used
+            const int tpos = (uy(cu) + dyo(pr) + 1) * W + ux(cu) + dxo(pr);
+            if (mp) atomicOr(&bits[tpos >> 5], 1u << (tpos & 31));
+        }
+        seq += __popcll(mU) + __popcll(mfU);
+        if (ballot(mp)) anyMP = true;
+        if (!fwdOn && ballot(prodRow && !np)) {  // a PRODUCE row became NONE: the sums of those that stayed
+            s0 = sumProd0;
+            s1 = sumProd1;
+            mc0 = maxProd0;
+            mc1 = maxProd1;
+            prodCosts(np, np ? U.cost[ua_ut(adec)] : 0, pl, s0, s1, mc0, mc1);
+        }
+        sumProd0 = s0;
+        sumProd1 = s1;
+        maxProd0 = mc0;
+        maxProd1 = mc1;
+        curP = 1;
+        wsync();
     }
     // Row of cell c of slot `slot` (rows = that slot's rows): the action tensor's, or, in a fused
     // uniform-policy step (KDyn.uni_actions), the Philox row the launch also writes there
@@ -2725,6 +2874,18 @@ struct Game {
             const int t0 = at[l];
             if (a & UA_PRESENT) ready = (MRTS_ETA_FLAT ? etaFlat(ua_type(a), prm, ua_ut(a), utyp(cu)) : eta(ua_type(a), prm, ua_ut(a), utyp(cu))) + t0 <= time;
         }
+#ifdef MRTS_ABLATE
+        if (ab(AB_CYCLERANK)) {  // the ready test and the rank by sequence number once more (nothing written)
+            bool rd = false;
+            const uint32_t a2 = launder(a), c2 = launder(cu);
+            const int p2 = launder(prm), q2 = launder(sq);
+            if (l < nu && (a2 & UA_PRESENT))
+                rd = (MRTS_ETA_FLAT ? etaFlat(ua_type(a2), p2, ua_ut(a2), utyp(c2)) : eta(ua_type(a2), p2, ua_ut(a2), utyp(c2))) + launder(at[l]) <= time;
+            int rk = 0;
+            for (uint64_t m = ballot(rd && ua_type(a2) != T_NONE); m; m &= m - 1) rk += rl(q2, __builtin_ctzll(m)) < q2;
+            keepv(rk);
+        }
+#endif
         if (ready) ua[l] = a & ~(UA_READY | UA_PRESENT);
         const bool wk = ready && ua_type(a) != T_NONE;
         const uint64_t work = ballot(wk);

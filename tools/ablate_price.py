@@ -21,7 +21,9 @@ L.mrts_set_ablate.argtypes = [ctypes.c_uint]
 from microrts_amd import DeviceVecEnv  # noqa: E402
 
 NAMES = ["load", "obs", "store", "maskbits", "record", "policy", "accept", "legality", "outcome+rewards", "index",
-         "gone", "tables", "rank", "decode", "(issue)", "(cyclerank)", "SKIP obs", "SKIP records",
+         # issue: the merged issue pass of both players (issueBothTest + issueBothWrite, the steps that take it);
+         # cyclerank: cycleLanes' ready test and rank
+         "gone", "tables", "rank", "decode", "issue", "cyclerank", "SKIP obs", "SKIP records",
          "SKIP PO render pass", "PO render without its stores", "SKIP PO disk painting", "SKIP PO cell map",
          "SKIP PO render record", "(snapshot)"]
 SEED = 0x5EEDC0DE

@@ -30,6 +30,11 @@ WHY = {
                         "outside the list)",
     "cellRank": "uniform loop over the candidate mask m (a ballot); c is the caller's per-lane cell, defined on every "
                 "lane (decode / issue paths compute it before the candidate test)",
+    "prodCosts": "called in uniform flow; cost | player << 16 is computed on every lane before the uniform loop over "
+                 "ballot(np), which reads only np lanes; the reductions take every lane's value (0 / 1 outside np)",
+    "issueBothWrite": "called in uniform flow (the merged test is wave-uniform); key is derived from the lane's unit "
+                      "word on every lane before the uniform loop over ballot(cand), which reads only cand lanes "
+                      "(l < nu: a loaded unit word)",
     "acceptChainReg": "tpos / cost / keyR / bv are defined on every lane before the uniform loops over ballots or "
                       "r < n; the readlanes sit outside the lane tests (round 5 moved the collision scan's read out "
                       "of `if (up && ...)`); bv's conditional update is on its own lane",

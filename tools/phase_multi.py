@@ -29,7 +29,9 @@ SHAPES = {"c3": ("maps/16x16/basesWorkers16x16.xml", 4096, False, 0, False),
 NAMES = {0: "head", 1: "predecode", 2: "decode", 3: "issue", 4: "cycle", 5: "outcome+rewards", 6: "obs+handoff",
          7: "compact", 8: "mask_setup", 9: "masks+policy", 10: "launch_end", 11: "wm11", 12: "wm12:after_bits",
          13: "wm13:record", 14: "wm14:policy", 16: "wml16:tables", 17: "wml17", 18: "wml18:bits", 19: "wml19:far",
-         20: "load20", 21: "load21", 22: "load22", 23: "dec23", 24: "dec24"}
+         20: "load20", 21: "load21", 22: "load22", 23: "dec23", 24: "dec24",
+         # counters, not cycles: the merged issue pass (MRTS_ISSUE_BOTH) per game-step, x1000; hits / attempts = hit rate
+         25: "issueBoth_attempts(x1000)", 26: "issueBoth_hits(x1000)"}
 NPH = 32
 SEED = 0x5EEDC0DE
 cfg = os.environ.get("CFG", "c5")
