@@ -128,160 +128,30 @@ DEV int lane_id() { return (int)threadIdx.x; }
 // hot straight-line code, which then packs into fewer instruction-cache lines
 #define MRTS_LIKELY(x) __builtin_expect(!!(x), 1)
 #define MRTS_UNLIKELY(x) __builtin_expect(!!(x), 0)
-// Output stores.  WT = streaming (`nt`) stores, so output lines do not sit dirty in the XCD's L2
-// until the end-of-kernel write-back.  Builtins, not inline asm: the wait-count and store-data
-// hazard passes must see the stores.  MRTS_WT bits (measured on c3 / c5 / --mask-mode full,
-// profiles/r12_summary.md): 1 full-observability planes (c3 +4.5 %, full masks +3 %: on),
-// 2 delta mask records + policy rows (c3 -1.3 %), 4 full-rewrite mask chunks (-15 %),
-// 8 state block (neutral), 16 partial-observability planes (c5 -18 %).  Round 2: write-through
-// (`sc1`) buffer stores leave no line in the XCD's L2, so the next step's state and action-row
-// reads (the same game runs on the same XCD every launch: tools/xcd_placement.py) keep theirs:
-// 32 full-observability planes (c3 +3.2 %), 128 partially observable planes (c5 +3.4 %), 64 delta
-// mask records (byte-granular partial lines: c3 -5 %, off).  profiles/round2_store_policy.md.
-#ifndef MRTS_MULTI_NOPRIO
-#define MRTS_MULTI_NOPRIO 0
+// The build switches that remain: the diagnostic builds above and below (MRTS_LANE_AUDIT), and the two that a
+// committed test or tool builds at the other value.  An experiment's switch lives for the pull request that
+// measures it (`make x1 XFLAGS1=-D...`); the code then keeps the measured choice.
+#ifndef MRTS_ISSUE_BOTH  // selfPlayFast issues both players' rows in one pass when no row of either interacts (round 7);
+#define MRTS_ISSUE_BOTH 1  // 0: tests/test_gpu_issue_both.py's comparison build
 #endif
-// 0: multi-step launches take the unit-count thresholds only, not the rank among the SIMD's waves (A/B)
-#ifndef MRTS_SIMD_RANK
-#define MRTS_SIMD_RANK 1
-#endif
-// 1: the rank also on c5's partially observable kernel (measured -4 %: its games outrank their own
-// helper waves, which then reach the handoff barriers late; round3q)
-// the rank's remaining-work estimate: (units + own idle units + MRTS_RANK_C) x steps left.  One game
-// alone on a SIMD takes ~ a + b x units per step with a / b ~ 75 units (E = 1024 span data), so the
-// steps left dominate: the games that fell behind issue first (c3, same box, 3 runs each: C = 0
-// 315.5 / 285.3 M at K = 200 / 20, C = 75 334.4 / 285.5 M, C = 150 334.1 / 280.7, C = 400 333.6 / 284.5;
-// later, with balanced placement and the byte image, C = 4000 vs 400: K = 20 kernel 11.95 vs 12.08 us
-// per step over 4 pairs, K = 200 equal — a game one step behind always outranks, units break ties)
-#ifndef MRTS_RANK_C
-#define MRTS_RANK_C 4000
-#endif
-// 0: multi-step launches keep game g on block g (no balanced placement, A/B builds)
-#ifndef MRTS_BALANCE
-#define MRTS_BALANCE 1
-#endif
-// k_env's step body reads KDyn through the laundered pointer too (round 6: SGPR spills 153 -> 136, no VGPR spills,
-// but c3 / c5 / c2 +-0 to -0.6 %: the re-read fields wait on scalar loads where the spilled ones were a readlane)
-#ifndef MRTS_BODY_LAUNDER
-#define MRTS_BODY_LAUNDER 0
-#endif
-#ifndef MRTS_BAL_MIN_ITER
-#define MRTS_BAL_MIN_ITER 64
-#endif
-// c5 (partially observable 32x32 self-play with helper waves) placed the same way: the dispatcher puts the game
-// waves of blocks b and b + n / 2 on one SIMD (round 6 span data, profiles/round6/placement_c5.json); c5 +0.6 %
-#ifndef MRTS_BALANCE_PO
-#define MRTS_BALANCE_PO 1
-#endif
-#ifndef MRTS_BAL_PO_GS
-#define MRTS_BAL_PO_GS 2
-#endif
-// the cost a game posts for the next placement: 0 = its unit count, 1 = units + own idle units at the launch's
-// last step (the estimate the SIMD rank uses: a step's decode / issue / mask / policy work grows with the idle
-// ones; round 6: c3 K = 20 kernel -0.6 %, c5 +0.4 % over 0; the estimate averaged over the launch's steps was worse)
-#ifndef MRTS_BAL_COST_IDLE
-#define MRTS_BAL_COST_IDLE 1
-#endif
-// 1: rollout timing events ride on the kernel dispatch (hipExtLaunchKernelGGL); 0: separate records
-#ifndef MRTS_EXT_EVENTS
-#define MRTS_EXT_EVENTS 1
-#endif
-#ifndef MRTS_SIMD_RANK_PO
-#define MRTS_SIMD_RANK_PO 0
-#endif
-#ifndef MRTS_SAMPLE_UNIFIED
-#define MRTS_SAMPLE_UNIFIED 1
-#endif
-#ifndef MRTS_PO_ROWS  // PO maps up to 32 wide: the ranged attack bits from unit row bitmaps too (round 6)
-#define MRTS_PO_ROWS 1
-#endif
-#ifndef MRTS_MASK_QUADS  // c3: each idle unit's mask bits computed by a quad of lanes, one per direction (round 6)
-#define MRTS_MASK_QUADS 1
-#endif
-#ifndef MRTS_REC_LANES  // delta mask records stored lane-parallel (storeRecordsLanes, round 5); 0 = by their own lanes
-#define MRTS_REC_LANES 1
-#endif
-#ifndef MRTS_PHILOX_UNROLL
-#define MRTS_PHILOX_UNROLL 1
-#endif
-#ifndef MRTS_POS_CHECKED  // selfPlayFast's issueBatch skips the position pairs acceptChain settled (round 5)
-#define MRTS_POS_CHECKED 1
-#endif
-#ifndef MRTS_SAMPLE32  // the sampler's type / produce-type picks in 32-bit operations, the packed word direct (round 5)
-#define MRTS_SAMPLE32 1
-#endif
-#ifndef MRTS_PO_VRES  // PO self-play: the views' base reservations in their own bitmap (round 6: measured -0.5 %, off)
-#define MRTS_PO_VRES 0
-#endif
-#ifndef MRTS_QUADS_PO  // the quads on the partially observable 32x32 instances too (round 6)
-#define MRTS_QUADS_PO 1
-#endif
-#ifndef MRTS_WALK32  // the cost walks on the 32x32 partially observable instances too, base reservations included (round 6)
-#define MRTS_WALK32 1
-#endif
-#ifndef MRTS_INDEX_WALK  // buildIndex's PRODUCE costs by a walk over their lanes (round 5); 0 = wave reductions
-#define MRTS_INDEX_WALK 1
-#endif
-#ifndef MRTS_PICK_SPLIT  // the sampler's direction picks as 32-bit picks apart from the attack pick (round 5)
-#define MRTS_PICK_SPLIT 1
-#endif
-#ifndef MRTS_ETA_FLAT  // cycleLanes' ready test with the branch-free duration lookup (round 5)
-#define MRTS_ETA_FLAT 1
-#endif
-#ifndef MRTS_DECODE_FWD  // selfPlayFast decodes forwarded words directly (decodeFwd, round 5)
-#define MRTS_DECODE_FWD 1
-#endif
-#ifndef MRTS_CONF_LDS  // acceptChainReg's parallel-path conflict test through an LDS copy of the reservations (round 5)
-#define MRTS_CONF_LDS 1
-#endif
-#ifndef MRTS_ISSUE_BOTH  // selfPlayFast issues both players' rows in one pass when no row of either interacts (round 7)
-#define MRTS_ISSUE_BOTH 1
-#endif
-#ifndef MRTS_XOR3  // Philox's xors as one three-input bit op (round 5); 0 = plain C
-#define MRTS_XOR3 1
-#endif
-// c2's helper-wave launches: the game wave issues at priority >= 1, ahead of its helper wave (at 0) — round 6:
-// c2 +1.6 % / +0.4 % (two rounds of interleaved runs; the helper at 3 instead: -4.5 %); on c5 +0.5 % / -0.6 %, so
-// c5 keeps its unit-count priorities (which already put most of its games above their helpers: without any
-// priority c5 lost 9 %)
-#ifndef MRTS_GAME_OVER_HELPER
-#define MRTS_GAME_OVER_HELPER 1
-#endif
-#ifndef MRTS_HELPER_PRIO
-#define MRTS_HELPER_PRIO 0
-#endif
-// 1: partially observable multi-step launches without the render helper wave (A/B builds only).  Round 4
+// 1: partially observable multi-step launches without the render helper wave (tools/po_helper_repro.py).  Round 4
 // had made it the default after its full-size soak found 2 of 2048 c5 games with one stale observation value
 // for a unit that died in the observed step; round 5 found the cause (the renders read the dead unit's
 // fields by readlane inside their divergent chunk loop, from a lane that was off there — writeObsPOFast)
 // and the helper is back on.
-#ifndef MRTS_PO_FAST  // partially observable self-play games through selfPlayFast (round 5); 0 = the generic path
-#define MRTS_PO_FAST 1
-#endif
-#ifndef MRTS_RESP_RING  // the per-step Responses ring (mrts_set_step_responses); 0 = A/B builds without it
-#define MRTS_RESP_RING 1
-#endif
 #ifndef MRTS_NO_PO_HELPER
 #define MRTS_NO_PO_HELPER 0
 #endif
-// issue-priority thresholds on a game's unit count (k_env): 1 / 2 / 3 from T1 / T2 / T3 units
-// (units + own idle units; measured against units alone at 24 / 30 / 36: c3 +1.8 % at K = 200,
-// +0.8 % at K = 20)
-#ifndef MRTS_PRIO_IDLE
-#define MRTS_PRIO_IDLE 1
+// PO self-play: the views' base reservations in a bitmap of their own (selfPlayFast's `vres`; round 6: measured
+// -0.5 % on c5, off).  Rejected, and still a switch: with its dead arm folded away the default library's device code
+// stays byte-identical but the `timing` and `ablate` builds' does not (the early inliner sees other code), and the
+// fold that retired the other switches rested on that identity.
+#ifndef MRTS_PO_VRES
+#define MRTS_PO_VRES 0
 #endif
-#ifndef MRTS_PRIO_T1
-#define MRTS_PRIO_T1 29
-#endif
-#ifndef MRTS_PRIO_T2
-#define MRTS_PRIO_T2 35
-#endif
-#ifndef MRTS_PRIO_T3
-#define MRTS_PRIO_T3 41
-#endif
-#ifndef MRTS_WT
-#define MRTS_WT 161
-#endif
+// Output stores.  WT = streaming (`nt`) stores, so output lines do not sit dirty in the XCD's L2
+// until the end-of-kernel write-back.  Builtins, not inline asm: the wait-count and store-data
+// hazard passes must see the stores.
 typedef int32_t i32x4v __attribute__((ext_vector_type(4)));
 typedef int32_t i32x4u __attribute__((ext_vector_type(4), aligned(4)));
 typedef int32_t i32x3u __attribute__((ext_vector_type(3), aligned(4)));
@@ -308,14 +178,21 @@ DEV void st1(int32_t* p, int a) {
     if (WT) __builtin_nontemporal_store(a, p);
     else *p = a;
 }
-constexpr bool WT_OBS = (MRTS_WT & 1) != 0, WT_MASK = (MRTS_WT & 2) != 0, WT_FULLMASK = (MRTS_WT & 4) != 0,
-               WT_STATE = (MRTS_WT & 8) != 0, WT_POOBS = (MRTS_WT & 16) != 0;
-// MRTS_WT bit 32: full-observability planes as write-through (`sc1`) buffer stores, which leave no
-// line in the XCD's L2 (MI355X_MICROARCH.md, store flavours), so the next step's state and action
-// reads keep their L2 lines; `rsrc` = a raw buffer over the stored region (gfx9 descriptor word 3)
-constexpr bool SC1_OBS = (MRTS_WT & 32) != 0;
-// MRTS_WT bit 64: delta mask records (and zero records) likewise; bit 128: partially observable planes
-constexpr bool SC1_MASK = (MRTS_WT & 64) != 0, SC1_POOBS = (MRTS_WT & 128) != 0;
+// The store policy, measured on c3 / c5 / --mask-mode full (profiles/r12_summary.md).  Streaming stores for:
+constexpr bool WT_OBS = true,        // full-observability planes (c3 +4.5 %, full masks +3 %)
+               WT_MASK = false,      // delta mask records + policy rows (c3 -1.3 %)
+               WT_FULLMASK = false,  // full-rewrite mask chunks (-15 %)
+               WT_STATE = false,     // the state block (neutral)
+               WT_POOBS = false;     // partially observable planes (c5 -18 %)
+// Round 2 (profiles/round2_store_policy.md): write-through (`sc1`) buffer stores leave no line in the XCD's L2,
+// so the next step's state and action-row reads (the same game runs on the same XCD every launch:
+// tools/xcd_placement.py) keep theirs; `rsrc` = a raw buffer over the stored region (gfx9 descriptor word 3).
+constexpr bool SC1_OBS = true,     // full-observability planes (c3 +3.2 %)
+               SC1_POOBS = true,   // partially observable planes (c5 +3.4 %)
+               SC1_MASK = false;   // delta mask records (byte-granular partial lines: c3 -5 %)
+// The plane stores are written for this policy: where a writer has the sc1 form it calls st4sc1 (or the b32
+// builtin) directly, which takes precedence over WT_OBS / WT_POOBS.
+static_assert(WT_OBS && SC1_OBS && SC1_POOBS, "plane stores: sc1 buffer stores");
 DEV __amdgpu_buffer_rsrc_t bufRsrc(void* base, uint32_t bytes) {
     return __builtin_amdgcn_make_buffer_rsrc(base, (short)0, (int)bytes, 0x00020000);
 }
@@ -456,7 +333,7 @@ static_assert(sizeof(DevUtt) % 4 == 0 && UTT_WORDS <= 192, "DevUtt copy: 3 words
 // two v_xor_b32 for it).  k MUST be wave-uniform (a Philox key word, in an SGPR): the "s" constraint would
 // silently readfirstlane a per-lane value.  Other targets (ARCH overridden) take the plain C form.
 DEV uint32_t xor3s(uint32_t a, uint32_t b, uint32_t k) {
-#if MRTS_XOR3 && defined(__gfx950__)
+#if defined(__gfx950__)
     uint32_t d;
     asm("v_bitop3_b32 %0, %1, %2, %3 bitop3:0x96" : "=v"(d) : "v"(a), "v"(b), "s"(k));
     return d;
@@ -467,11 +344,7 @@ DEV uint32_t xor3s(uint32_t a, uint32_t b, uint32_t k) {
 // Philox4x32-10, the ten rounds unrolled (rolled, the loop carried two v_mov per round and the xors
 // were not fused: 8 VALU per round against 4)
 DEV void philox(uint32_t c[4], uint32_t k0, uint32_t k1) {
-#if MRTS_PHILOX_UNROLL
 #pragma unroll
-#else
-#pragma unroll 1
-#endif
     for (int r = 0; r < 10; r++) {
         const uint64_t p0 = (uint64_t)0xD2511F53u * c[0];
         const uint64_t p1 = (uint64_t)0xCD9E8D57u * c[2];
@@ -498,11 +371,6 @@ DEV int pickBit(uint32_t r, uint64_t bitsv, int n) {
 // (slot id, step, cell, 0)
 // Masked-uniform random policy of one cell (the bench / rollout agent): mask slots 1..K-1 as bits
 // (lo: slots 1..64, hi: 65..), Philox4x32-10 with key = seed, counter = (slot id, step, cell, 0)
-DEV uint32_t packFwdFree(const int32_t a[7]) {  // = packFwd (defined with the forwarded words below)
-    return ((uint32_t)a[0] & 7u) | (((uint32_t)(a[1] + 1) & 7u) << 3) | (((uint32_t)(a[2] + 1) & 7u) << 6) |
-           (((uint32_t)(a[3] + 1) & 7u) << 9) | (((uint32_t)(a[4] + 1) & 7u) << 12) | (((uint32_t)(a[5] + 1) & 15u) << 15) |
-           (((uint32_t)(a[6] + 1) & 127u) << 19);
-}
 // pickBit of a field of at most 32 bits (already masked): the same pick in 32-bit operations
 DEV int pickBit32(uint32_t r, uint32_t bitsv) {
     const int cnt = __popc(bitsv);
@@ -514,21 +382,21 @@ DEV int pickBit32(uint32_t r, uint32_t bitsv) {
 // packFwd of a row with every value 0 (each parameter field holds value + 1)
 constexpr uint32_t FWD_ZERO = (1u << 3) | (1u << 6) | (1u << 9) | (1u << 12) | (1u << 15) | (1u << 19);
 // packed (optional): packFwd(a) of the drawn row, built from the picks (no field repacking)
+// The parameter comes from ONE pick over the chosen type's field, not one pick per case of a switch over the type:
+// the lanes of a wave hold several types, and a switch runs its cases one after the other.
 DEV void sampleBitsRaw(uint64_t seed, uint32_t step, uint32_t slotId, int ntypes, int K, uint64_t lo, uint64_t hi, int c,
                        int32_t a[7], uint32_t* packed = nullptr) {
-#if MRTS_SAMPLE_UNIFIED && MRTS_SAMPLE32
     uint32_t ctr[4] = {slotId, step, (uint32_t)c, 0u};
     philox(ctr, (uint32_t)seed, (uint32_t)(seed >> 32));
     // mask slots 1..K-1 as bits of lo:hi (slot k -> bit k - 1): the type field is bits 0..5, the produce
     // types bits 22.., the direction fields bits 6 + 4 (t - 1).., the attack window bits 22 + ntypes..
     const int t = pickBit32(ctr[0], (uint32_t)lo & 63u);
     int pv = 0, ut = 0;
-    if (MRTS_PICK_SPLIT && t > 0 && t < 5) {
+    if (t > 0 && t < 5) {
         // a direction: 4 bits at 2 + 4 t (below 32) — one 32-bit pick
         pv = pickBit32(ctr[1], ((uint32_t)lo >> (2 + 4 * t)) & 15u);
     } else if (t > 0) {
-        // the attack window: K - 23 - ntypes bits from 22 + ntypes (across lo / hi); without
-        // MRTS_PICK_SPLIT every type's field in this one 64-bit pick
+        // the attack window: K - 23 - ntypes bits from 22 + ntypes (across lo / hi), a 64-bit pick
         const int b = t == 5 ? 22 + ntypes : 2 + 4 * t, n = t == 5 ? K - 23 - ntypes : 4;
         uint64_t v = b >= 64 ? hi >> (b - 64) : ((lo >> b) | (hi << (64 - b)));
         v &= n >= 64 ? ~0ull : ((1ull << n) - 1);
@@ -545,55 +413,6 @@ DEV void sampleBitsRaw(uint64_t seed, uint32_t step, uint32_t slotId, int ntypes
     if (packed)
         *packed = FWD_ZERO + (uint32_t)(t > 0 ? t : 0) + (t > 0 ? (uint32_t)pv << (t == 5 ? 19 : 3 * t) : 0u) +
                   ((uint32_t)ut << 15);
-#else
-    for (int k = 0; k < 7; k++) a[k] = 0;
-    uint32_t ctr[4] = {slotId, step, (uint32_t)c, 0u};
-    philox(ctr, (uint32_t)seed, (uint32_t)(seed >> 32));
-    auto field = [&](int off, int n) -> uint64_t {  // mask slots [off, off+n) (off >= 1)
-        const int b = off - 1;
-        uint64_t v;
-        if (b >= 64) v = hi >> (b - 64);
-        else v = (lo >> b) | (b ? (hi << (64 - b)) : 0ull);
-        return n >= 64 ? v : (v & ((1ull << n) - 1));
-    };
-    const int t = pickBit(ctr[0], field(1, 6), 6);
-    if (t < 0) {
-        if (packed) *packed = FWD_ZERO;
-        return;
-    }
-    a[0] = t;
-#if MRTS_SAMPLE_UNIFIED
-    // the parameter of type t from ONE pick over that type's field (move / harvest / return / produce
-    // direction: 4 slots at 7 + 4 (t - 1); attack: the K - 23 - ntypes slots after the unit types), not
-    // one pick per case: the lanes of a wave hold several types, and a switch runs its cases one after
-    // the other.  Same words of the same Philox block, same picks: identical rows.
-    if (t > 0) {
-        const int off = t == 5 ? 23 + ntypes : 3 + 4 * t, n = t == 5 ? K - 23 - ntypes : 4;
-        const int pv = pickBit(ctr[1], field(off, n), n);
-        a[1] = t == 1 ? pv : 0;
-        a[2] = t == 2 ? pv : 0;
-        a[3] = t == 3 ? pv : 0;
-        a[4] = t == 4 ? pv : 0;
-        a[6] = t == 5 ? pv : 0;
-    }
-    if (t == 4) a[5] = pickBit(ctr[2], field(23, ntypes), ntypes);
-#else
-    switch (t) {
-        case 1: a[1] = pickBit(ctr[1], field(7, 4), 4); break;
-        case 2: a[2] = pickBit(ctr[1], field(11, 4), 4); break;
-        case 3: a[3] = pickBit(ctr[1], field(15, 4), 4); break;
-        case 4:
-            a[4] = pickBit(ctr[1], field(19, 4), 4);
-            a[5] = pickBit(ctr[2], field(23, ntypes), ntypes);
-            break;
-        case 5: {
-            const int off = 23 + ntypes, n = K - off;
-            a[6] = pickBit(ctr[1], field(off, n), n);
-        } break;
-    }
-#endif
-    if (packed) *packed = packFwdFree(a);
-#endif
 }
 
 // Unmasked uniform random row (BASELINE config c2) of cell c of slot id slotId:
@@ -636,10 +455,7 @@ DEV void unpackFwd(uint32_t w, int32_t a[7]) {
 // loop makes it opaque once per iteration (freshLane), so the compiler re-reads a field with a scalar
 // load (SMEM) where the step uses it, instead of loading every field at kernel entry and keeping it
 // live across the loop: that spilled ~240 SGPRs into VGPR lanes, and every reload was a v_readlane —
-// a VALU instruction in a VALU-issue-bound kernel (MRTS_DYN_LAUNDER = 0: the old form).
-#ifndef MRTS_DYN_LAUNDER
-#define MRTS_DYN_LAUNDER 1
-#endif
+// a VALU instruction in a VALU-issue-bound kernel.
 typedef const __attribute__((address_space(4))) KDyn* KDynPtr;
 // k_env's KDyn argument: its third kernel argument, after the two pointers, at byte 16 of the kernarg
 // segment.  The offset is laundered (not the address: an address escaping into asm makes the compiler
@@ -745,7 +561,7 @@ struct Game {
         // multi-step kernels: the kernel argument's address made opaque again each step, so the fields
         // and addresses derived from it are re-read (SMEM) in the phase that uses them rather than held
         // across the step in spilled SGPRs (each reload a v_readlane)
-        if (iter && MRTS_DYN_LAUNDER) Dp = kdynArg(true);
+        if (iter) Dp = kdynArg(true);
     }
     // the helper wave of a HELP launch (threads 64..127) runs Game methods as lanes 0..63
     DEV void helperLane() { asm volatile("" : "=v"(lidv) : "0"((int)threadIdx.x - 64)); }
@@ -1125,13 +941,9 @@ struct Game {
         const int pl = l < nu ? uplay(cu) : -1;
         const bool idle = pl >= 0 && !(lua & UA_PRESENT);
         int32_t a[7] = {0, 0, 0, 0, 0, 0, 0};
-        if (fwdOn) {
-            // the previous launch's fused policy sampled this unit's row (the values it wrote to the
-            // action tensor at this cell) and forwarded it in the state block (decoded below)
-            if (!MRTS_DECODE_FWD && idle) unpackFwd(lfwd, a);
-        } else if (idle) {
-            fetchRow(pl == 0 ? rows0 : rows1, s0 + pl, uy(cu) * W + ux(cu), a);
-        }
+        // fwdOn: the previous launch's fused policy sampled this unit's row (the values it wrote to the
+        // action tensor at this cell) and forwarded it in the state block (decodeFwd below, no fetch)
+        if (!fwdOn && idle) fetchRow(pl == 0 ? rows0 : rows1, s0 + pl, uy(cu) * W + ux(cu), a);
         const bool useIx = !po && (HW + 2 * W + 31) / 32 <= 64;  // PO: the view's reservations (baseReservations)
         if (useIx) buildIndex();  // while the rows are in flight
         // PO (round 6): each view's base reservations go to a bitmap of their own in the top words of `scell` (free
@@ -1155,7 +967,7 @@ struct Game {
             keepv(t2 + pr2 + ut2 + tx2 + ty2 + (int)bad2);
         }
 #endif
-        if (idle) bad = (MRTS_DECODE_FWD && fwdOn) ? decodeFwd(cu, lfwd, t, pr, ut, tx, ty) : decodeFields(cu, a, t, pr, ut, tx, ty);
+        if (idle) bad = fwdOn ? decodeFwd(cu, lfwd, t, pr, ut, tx, ty) : decodeFields(cu, a, t, pr, ut, tx, ty);
         if (ballot(bad)) addErr(E_PRODUCE_TYPE);
         const uint32_t adec = pack_ua(t, ut, tx, ty);
         const int c = uy(cu) * W + ux(cu);
@@ -1255,7 +1067,7 @@ struct Game {
                 }
                 wsync();
                 MPHASE(24);
-                if (acc) issueBatch(isPA, irank, __popcll(acc), l, tt, prm, ttx, tty, tut, false, &cu, nullptr, MRTS_POS_CHECKED);
+                if (acc) issueBatch(isPA, irank, __popcll(acc), l, tt, prm, ttx, tty, tut, false, &cu, nullptr, true);
             }
             // fillWithNones(gs, p, 1): p's idle units left without an action, list order
             const bool fill = mine && !isPA;
@@ -1777,23 +1589,15 @@ struct Game {
             const bool cand = rank >= 0, up = cand && usesPos;
             if (!(runQ != 0 && runQ > 0 && runQ > presQ)) {
                 bool conf = false;
-                if (MRTS_CONF_LDS) {
-                    // reserved already, or used by another candidate: each candidate ORs its position into a
-                    // copy of the reservation words (rseq, free here) and is in conflict when the bit was set —
-                    // by the base reservations or by another candidate (one of each equal pair sees it)
-                    uint32_t* cp = (uint32_t*)rseq;
-                    if (l < NB) cp[l] = RB[l];
-                    wsync();
-                    if (up) conf = (atomicOr(&cp[tpos >> 5], 1u << (tpos & 31)) >> (tpos & 31)) & 1u;
-                    wsync();
-                } else {
-                    conf = up && ((RB[tpos >> 5] >> (tpos & 31)) & 1u);
-                    for (uint64_t mm = ballot(up); mm; mm &= mm - 1) {
-                        const int k = __builtin_ctzll(mm);
-                        const int tk = rl(tpos, k);  // read in uniform flow: lane k itself is off inside the test below
-                        if (up && k != l && tk == tpos) conf = true;
-                    }
-                }
+                // reserved already, or used by another candidate: each candidate ORs its position into a
+                // copy of the reservation words (rseq, free here) and is in conflict when the bit was set —
+                // by the base reservations or by another candidate (one of each equal pair sees it; round 5,
+                // in place of a readlane walk over the candidates)
+                uint32_t* cp = (uint32_t*)rseq;
+                if (l < NB) cp[l] = RB[l];
+                wsync();
+                if (up) conf = (atomicOr(&cp[tpos >> 5], 1u << (tpos & 31)) >> (tpos & 31)) & 1u;
+                wsync();
                 int sumc = 0;
                 if (walk) {  // the candidates' PRODUCE costs (a few lanes): one lane read each
                     for (uint64_t mm = ballot(cand && cost > 0); mm; mm &= mm - 1) sumc += uni(rl(cost, __builtin_ctzll(mm)));
@@ -2872,7 +2676,7 @@ struct Game {
             prm = par[l];
             sq = as[l];
             const int t0 = at[l];
-            if (a & UA_PRESENT) ready = (MRTS_ETA_FLAT ? etaFlat(ua_type(a), prm, ua_ut(a), utyp(cu)) : eta(ua_type(a), prm, ua_ut(a), utyp(cu))) + t0 <= time;
+            if (a & UA_PRESENT) ready = etaFlat(ua_type(a), prm, ua_ut(a), utyp(cu)) + t0 <= time;
         }
 #ifdef MRTS_ABLATE
         if (ab(AB_CYCLERANK)) {  // the ready test and the rank by sequence number once more (nothing written)
@@ -2880,7 +2684,7 @@ struct Game {
             const uint32_t a2 = launder(a), c2 = launder(cu);
             const int p2 = launder(prm), q2 = launder(sq);
             if (l < nu && (a2 & UA_PRESENT))
-                rd = (MRTS_ETA_FLAT ? etaFlat(ua_type(a2), p2, ua_ut(a2), utyp(c2)) : eta(ua_type(a2), p2, ua_ut(a2), utyp(c2))) + launder(at[l]) <= time;
+                rd = etaFlat(ua_type(a2), p2, ua_ut(a2), utyp(c2)) + launder(at[l]) <= time;
             int rk = 0;
             for (uint64_t m = ballot(rd && ua_type(a2) != T_NONE); m; m &= m - 1) rk += rl(q2, __builtin_ctzll(m)) < q2;
             keepv(rk);
@@ -3033,7 +2837,7 @@ struct Game {
         const int k0 = (int)(D.reward_kinds4 & 15u);
         // the Responses ring (mrts_set_step_responses): reward / done point at the call's ring and each
         // iteration writes its own step there (resp_stride = n_slots * n_rewards; 0 = the plain buffers)
-        const size_t ro = MRTS_RESP_RING ? (size_t)((uint32_t)it * (uint32_t)D.resp_stride) : 0;
+        const size_t ro = (size_t)((uint32_t)it * (uint32_t)D.resp_stride);
         const bool done0 = k0 == RF_WINLOSS ? gameover : (k0 == RF_RESOURCE_GATHER ? !resLeft : false);
         const int L = lid();
         if (R == 1 && k0 == RF_WINLOSS) {  // WinLoss alone (the common case): a wave-uniform branch, no switch
@@ -3145,8 +2949,7 @@ struct Game {
                 for (int j = 0; j < 4; j++)  // the other player's owners: 0, 1, 2 -> 0, 2, 1 (bits 2v.. of 0b011000)
                     w[j] = (i && q == 2) ? (int)__builtin_amdgcn_ubfe(24u, 2u * (uint32_t)v[q][j], 2u) : v[q][j];
                 const uint32_t off = (uint32_t)((i * D.C + q) * HW + c4);
-                if (SC1_OBS) st4sc1(rs, off * 4u, w[0], w[1], w[2], w[3]);
-                else st4<WT_OBS>(o0 + off, w[0], w[1], w[2], w[3]);
+                st4sc1(rs, off * 4u, w[0], w[1], w[2], w[3]);
             }
         }
         if (MRTS_UNLIKELY(D.obs8 != nullptr)) {  // the uint8 transport (mrts_set_exchange_bytes): every plane
@@ -3222,8 +3025,7 @@ struct Game {
                         // the other player's view differs only in the owner plane
                         const int x = (i && q == 2 && v[2]) ? 3 - v[2] : v[q];
                         const uint32_t off = (uint32_t)((i * D.C + q) * HW + c);
-                        if (SC1_OBS) __builtin_amdgcn_raw_buffer_store_b32(x, rs, (int)(off * 4u), 0, 16);
-                        else st1<WT_OBS>(o0 + off, x);
+                        __builtin_amdgcn_raw_buffer_store_b32(x, rs, (int)(off * 4u), 0, 16);
                     }
                 }
                 if (MRTS_UNLIKELY(D.obs16 != nullptr)) {  // the int16 transport copy (mrts_set_obs16)
@@ -3277,8 +3079,7 @@ struct Game {
 #pragma unroll
                 for (int pl = 0; pl < 6; pl++) {
                     if (pl >= npl) break;
-                    if (SC1_OBS) st4sc1(rs, (uint32_t)(pl * HW + c4) * 4u, v[0][pl], v[1][pl], v[2][pl], v[3][pl]);
-                    else st4<WT_OBS>(o0 + (size_t)pl * HW + c4, v[0][pl], v[1][pl], v[2][pl], v[3][pl]);
+                    st4sc1(rs, (uint32_t)(pl * HW + c4) * 4u, v[0][pl], v[1][pl], v[2][pl], v[3][pl]);
                 }
                 if (MRTS_UNLIKELY(D.obs16 != nullptr)) {  // the int16 transport copy (mrts_set_obs16)
                     int16_t* h0 = D.obs16 + (size_t)slot0 * D.C * HW;
@@ -3298,7 +3099,6 @@ struct Game {
                     }
                 }
                 if (nslots == 2) {  // the other player's view differs only in the owner plane
-                    int32_t* o1 = o0 + (size_t)D.C * HW;
 #pragma unroll
                     for (int pl = 0; pl < 6; pl++) {
                         if (pl >= npl) break;
@@ -3309,8 +3109,7 @@ struct Game {
                             w.z = w.z ? 3 - w.z : 0;
                             w.w = w.w ? 3 - w.w : 0;
                         }
-                        if (SC1_OBS) st4sc1(rs, (uint32_t)((D.C + pl) * HW + c4) * 4u, w.x, w.y, w.z, w.w);
-                        else st4<WT_OBS>(o1 + (size_t)pl * HW + c4, w.x, w.y, w.z, w.w);
+                        st4sc1(rs, (uint32_t)((D.C + pl) * HW + c4) * 4u, w.x, w.y, w.z, w.w);
                     }
                 }
             }
@@ -3563,14 +3362,9 @@ struct Game {
                 v[j][6] = (int)((mr >> (x0 + j)) & 1u);
                 v[j][7] = (int)((tr >> (x0 + j)) & 1u);
             }
-            if (SC1_POOBS) {
-                const __amdgpu_buffer_rsrc_t rs = bufRsrc(out, (uint32_t)(D.C * HW * 4));
+            const __amdgpu_buffer_rsrc_t rs = bufRsrc(out, (uint32_t)(D.C * HW * 4));
 #pragma unroll
-                for (int k = 0; k < 8; k++) st4sc1(rs, (uint32_t)(k * HW + 4 * c4) * 4u, v[0][k], v[1][k], v[2][k], v[3][k]);
-            } else {
-#pragma unroll
-                for (int k = 0; k < 8; k++) st4<WT_POOBS>(out + k * HW + 4 * c4, v[0][k], v[1][k], v[2][k], v[3][k]);
-            }
+            for (int k = 0; k < 8; k++) st4sc1(rs, (uint32_t)(k * HW + 4 * c4) * 4u, v[0][k], v[1][k], v[2][k], v[3][k]);
         }
         wsync();
     }
@@ -3777,14 +3571,8 @@ struct Game {
                 continue;
             }
 #endif
-            if (SC1_POOBS) {
 #pragma unroll
-                for (int k = 0; k < 8; k++) st4sc1(rs, base + (uint32_t)(k * HW) * 4u, vv[0][k], vv[1][k], vv[2][k], vv[3][k]);
-            } else {
-                int32_t* o = out + base / 4;
-#pragma unroll
-                for (int k = 0; k < 8; k++) st4<WT_POOBS>(o + k * HW, vv[0][k], vv[1][k], vv[2][k], vv[3][k]);
-            }
+            for (int k = 0; k < 8; k++) st4sc1(rs, base + (uint32_t)(k * HW) * 4u, vv[0][k], vv[1][k], vv[2][k], vv[3][k]);
         }
         wsync();
     }
@@ -3795,16 +3583,14 @@ struct Game {
     DEV void storeRecordsHelp(const uint32_t* rb) {
         const int l = (int)threadIdx.x - 64;
         const int total = HW * K, slot0 = 2 * g;
-        const uint8_t* mbase = D.masks + (size_t)slot0 * total;
-        const __amdgpu_buffer_rsrc_t mrs = bufRsrc((void*)mbase, (uint32_t)(2 * total));
+        uint8_t* const masks = D.masks;  // read ahead of the early return: where this load sits is part of the measured code
         if (!(uniu(rb[5 * 64]) >> 31)) return;  // the game wave stored this step's masks itself
         const uint32_t e = rb[l];
         if (e != ~0u) {
             const int si = (int)(e >> 16), c = (int)(e & 0xFFFFu), slot = slot0 + si;
             const uint64_t lo = (uint64_t)rb[64 + l] | ((uint64_t)rb[128 + l] << 32);
             const uint32_t w2 = rb[192 + l];
-            if (SC1_MASK) storeRecordSc1(mrs, mbase, (uint32_t)(si * total + c * K), lo, w2);
-            else storeRecord(D.masks + (size_t)slot * total + (size_t)c * K, lo, w2);
+            storeRecord(masks + (size_t)slot * total + (size_t)c * K, lo, w2);
             if (D.pol_actions && D.pol_delta) {
                 int32_t a[7];
                 unpackFwd(rb[256 + l], a);
@@ -3818,8 +3604,7 @@ struct Game {
         if (l < ngone) {
             const uint32_t ge = gl[l];
             const int slot = slot0 + (int)(ge >> 15), cz = (int)(ge & 0x7FFFu);
-            if (SC1_MASK) storeRecordSc1(mrs, mbase, (uint32_t)((slot - slot0) * total + cz * K), 0ull, 0u);
-            else storeRecord(D.masks + (size_t)slot * total + (size_t)cz * K, 0ull, 0u);
+            storeRecord(masks + (size_t)slot * total + (size_t)cz * K, 0ull, 0u);
             if (D.pol_actions && D.pol_delta) {
                 int32_t* dst = D.pol_actions + ((size_t)slot * HW + cz) * 7;
                 st4u<WT_MASK>(dst, 0, 0, 0, 0);
@@ -4008,9 +3793,6 @@ struct Game {
         int32_t* out = D.obs + (size_t)(2 * g) * D.C * HW;
         const __amdgpu_buffer_rsrc_t rs = bufRsrc(out, (uint32_t)(2 * D.C * HW * 4));
         const uint64_t deadAny = deadM0 | deadM1;
-#ifdef MRTS_DIAG_HELPER_NORENDER  // diagnostic build only: the helper skips the render items (output wrong)
-        n = 0;
-#endif
         for (int it = l; it < n; it += 64) {
             const uint32_t e = poList[it];
             const int v = (int)(e >> 15), c4 = (int)(e & 0x7FFFu);  // lane = 4 consecutive cells of one row
@@ -4074,14 +3856,8 @@ struct Game {
                 vv[j][7] = (int)((tr >> (x0 + j)) & 1u);
             }
             const uint32_t base = (uint32_t)(v * D.C * HW + 4 * c4) * 4u;
-            if (SC1_POOBS) {
 #pragma unroll
-                for (int k = 0; k < 8; k++) st4sc1(rs, base + (uint32_t)(k * HW) * 4u, vv[0][k], vv[1][k], vv[2][k], vv[3][k]);
-            } else {
-                int32_t* o = out + base / 4;
-#pragma unroll
-                for (int k = 0; k < 8; k++) st4<WT_POOBS>(o + k * HW, vv[0][k], vv[1][k], vv[2][k], vv[3][k]);
-            }
+            for (int k = 0; k < 8; k++) st4sc1(rs, base + (uint32_t)(k * HW) * 4u, vv[0][k], vv[1][k], vv[2][k], vv[3][k]);
         }
         wsync();
     }
@@ -4767,40 +4543,6 @@ struct Game {
     // One cell's K-byte mask record (byte k = bit k of lo:hi) at dst, byte-exact: up to 3 head bytes to
     // reach dword alignment, whole dwords (dwordx4 / dwordx3 stores, 4-byte aligned), then the tail
     // bytes — neighbouring records written by other lanes are never touched.
-    // storeRecord as write-through (`sc1`) buffer stores (SC1_MASK): byte offset `off` into the raw
-    // buffer `r` whose base address is `base`
-    DEV void storeRecordSc1(__amdgpu_buffer_rsrc_t r, const uint8_t* base, uint32_t off, uint64_t lo, uint32_t hi) const {
-        const int head = (int)((4u - (((uint32_t)(uintptr_t)base + off) & 3u)) & 3u);
-#pragma unroll
-        for (int i = 0; i < 3; i++)
-            if (i < head) __builtin_amdgcn_raw_buffer_store_b8((char)((lo >> i) & 1u), r, (int)(off + i), 0, 16);
-        const uint64_t sl = (lo >> head) | (head ? ((uint64_t)hi << (64 - head)) : 0ull);
-        const uint32_t sh = hi >> head;
-        const uint32_t v[3] = {(uint32_t)sl, (uint32_t)(sl >> 32), sh};
-        const int nd = (K - head) >> 2;
-        const uint32_t dwo = off + (uint32_t)head;
-        auto nib = [&](int k) -> int { return (int)expand4(v[k >> 3] >> (4 * (k & 7))); };
-        if (K == 79) {
-#pragma unroll
-            for (int q = 0; q < 4; q++) {
-                const i32x4v w = {nib(4 * q), nib(4 * q + 1), nib(4 * q + 2), nib(4 * q + 3)};
-                __builtin_amdgcn_raw_buffer_store_b128(w, r, (int)(dwo + 16 * q), 0, 16);
-            }
-            typedef int32_t i32x3v __attribute__((ext_vector_type(3)));
-            const i32x3v w3 = {nib(16), nib(17), nib(18)};
-            __builtin_amdgcn_raw_buffer_store_b96(w3, r, (int)(dwo + 64), 0, 16);
-        } else {
-            for (int k = 0; k < nd; k++) __builtin_amdgcn_raw_buffer_store_b32(nib(k), r, (int)(dwo + 4 * k), 0, 16);
-        }
-        const int t0 = head + 4 * nd;
-#pragma unroll
-        for (int i = 0; i < 3; i++) {
-            const int b = t0 + i;
-            if (b < K)
-                __builtin_amdgcn_raw_buffer_store_b8((char)((b < 64 ? (lo >> b) : (uint64_t)(hi >> (b - 64))) & 1u), r,
-                                                     (int)(off + b), 0, 16);
-        }
-    }
     DEV void storeRecord(uint8_t* dst, uint64_t lo, uint32_t hi) const {
         const int head = (int)((4u - ((uint32_t)(uintptr_t)dst & 3u)) & 3u);
 #pragma unroll
@@ -4899,7 +4641,7 @@ struct Game {
         // the general render's scratch map is done with, and a helper wave's packs and cell map end at word 896 of
         // 32x32's 1,024 (round 6: c5's ranged units had taken farAttackBits' walk over every live unit))
         const bool rowS = W <= 32 && 2 * H <= 32;
-        const bool rowP = MRTS_PO_ROWS && !rowS && po && W <= 32 && W >= 16 && 2 * H <= 64;
+        const bool rowP = !rowS && po && W <= 32 && W >= 16 && 2 * H <= 64;
         uint32_t* rows = rowS ? (uint32_t*)rslot : rowP ? scell + (HW - 2 * H) : nullptr;
         const bool rowB = rowS || rowP;
         if (rowB && l < 2 * H) rows[l] = 0;
@@ -4934,25 +4676,25 @@ struct Game {
             // while the new row sets nb take <= 16 words, else (32x32 views) the 48 words of scell's tail below
             // the rows (past a helper wave's packs and cell map, which end at word 896 of 1,024)
             uint32_t* const qb = NW <= 16 ? (uint32_t*)rseq + 16 : (rowP && HW - 2 * H - 48 >= 896) ? rows - 48 : nullptr;
-            if (MRTS_MASK_QUADS && rowB && qb && (MRTS_QUADS_PO || !po)) {
+            if (rowB && qb) {
                 wsync();
                 maskBitsQuads(T, si, cu, carried, rows, w0, w1, w2, qb);
             } else {
-            if (si >= 0) maskBitsFast(T, cu, carried, w0, w1, w2);
-            MPHASE(18);
-            const bool far = si >= 0 && ((T.attackFar >> utyp(cu)) & 1u);
-            if (rowB) {
-                wsync();
-                farAttackRows(far, cu, rows, w0, w1, w2);
-            } else {
-                farAttackBits(far, cu, cu, ballot(l < nu && !(cu & UC_DEAD) && uplay(cu) >= 0), w0, w1, w2);
-            }
+                if (si >= 0) maskBitsFast(T, cu, carried, w0, w1, w2);
+                MPHASE(18);
+                const bool far = si >= 0 && ((T.attackFar >> utyp(cu)) & 1u);
+                if (rowB) {
+                    wsync();
+                    farAttackRows(far, cu, rows, w0, w1, w2);
+                } else {
+                    farAttackBits(far, cu, cu, ballot(l < nu && !(cu & UC_DEAD) && uplay(cu) >= 0), w0, w1, w2);
+                }
             }
 #ifdef MRTS_ABLATE
             if (ab(AB_MASKBITS) && rowB) {  // a second copy of whichever form ran above
                 uint32_t v0 = 0, v1 = 0, v2 = 0;
                 const uint32_t cu2 = launder(cu);
-                if (MRTS_MASK_QUADS && qb && (MRTS_QUADS_PO || !po)) {
+                if (qb) {
                     wsync();
                     maskBitsQuads(T, launder(si), cu2, launder(carried), rows, v0, v1, v2, qb);
                 } else {
@@ -4981,7 +4723,7 @@ struct Game {
         // forward the sampled rows of a self-play game (read by selfPlayFast next launch); K - 23 - NT
         // attack slots fit packFwd's 7-bit field
         const bool fwdW = pol && nslots == 2 && K - 23 - NT <= 126;
-        const uint8_t* mbase = D.masks + (size_t)slot0 * total;  // this game's records (SC1_MASK buffer)
+        const uint8_t* mbase = D.masks + (size_t)slot0 * total;  // this game's records
         const __amdgpu_buffer_rsrc_t mrs = bufRsrc((void*)mbase, (uint32_t)(nslots * total));
         // the kernel's full policy pass (writePolicyAll, no delta base) reads the parked bits
         if (si >= 0 && D.pol_actions && !(D.pol_delta && D.mask_delta && (total & 15) == 0)) {
@@ -4991,7 +4733,7 @@ struct Game {
         }
         if (recOut && si < 0) recOut[l] = ~0u;  // (no record from this lane)
         // the records stored lane-parallel (storeRecordsLanes) rather than each by its own lane
-        const bool lanePar = MRTS_REC_LANES && !recOut && K == 79 && NW <= 16;
+        const bool lanePar = !recOut && K == 79 && NW <= 16;
         if (lanePar) {
 #ifdef MRTS_ABLATE
             if (!ab(AB_SKIP_RECORD))
@@ -5014,8 +4756,7 @@ struct Game {
 #ifdef MRTS_ABLATE
             if (!ab(AB_SKIP_RECORD))
 #endif
-            if (SC1_MASK) storeRecordSc1(mrs, mbase, (uint32_t)(si * total + c * K), lo, w2);
-            else storeRecord(D.masks + (size_t)slot * total + (size_t)c * K, lo, w2);
+            storeRecord(D.masks + (size_t)slot * total + (size_t)c * K, lo, w2);
 #ifdef MRTS_ABLATE
             if (ab(AB_RECORD)) storeRecord(D.masks + (size_t)slot * total + (size_t)c * K, launder(lo), launder(w2));
 #endif
@@ -5081,8 +4822,7 @@ struct Game {
             if (b0 + l < ngone) {
                 const uint32_t e = rslot[l];
                 const int slot = slot0 + (int)(e >> 15), cz = (int)(e & 0x7FFFu);
-                if (SC1_MASK) storeRecordSc1(mrs, mbase, (uint32_t)((slot - slot0) * total + cz * K), 0ull, 0u);
-                else storeRecord(D.masks + (size_t)slot * total + (size_t)cz * K, 0ull, 0u);
+                storeRecord(D.masks + (size_t)slot * total + (size_t)cz * K, 0ull, 0u);
                 if (pol) {
                     int32_t* dst = D.pol_actions + ((size_t)slot * HW + cz) * 7;
                     st4u<WT_MASK>(dst, 0, 0, 0, 0);
@@ -5191,8 +4931,7 @@ DEV void helperLoop(const KDyn& D, uint8_t* smem, int g, int niter) {
             for (int q = 0; q < 6; q++) {
                 if (q >= npl) break;
                 const uint32_t off = (uint32_t)((i * D.C + q) * HW + l);
-                if (SC1_OBS) __builtin_amdgcn_raw_buffer_store_b32(v[q], rs, (int)(off * 4u), 0, 16);
-                else st1<WT_OBS>(o0 + off, v[q]);
+                __builtin_amdgcn_raw_buffer_store_b32(v[q], rs, (int)(off * 4u), 0, 16);
             }
             if (MRTS_UNLIKELY(D.obs16 != nullptr)) {
                 int16_t* h0 = D.obs16 + (size_t)(slot0 + i) * D.C * HW;
@@ -5225,6 +4964,12 @@ DEV void helperLoop(const KDyn& D, uint8_t* smem, int g, int niter) {
 // launch stamp into its SIMD's row of the table (key from HW_ID / XCC_ID, slot = wave id), reads the
 // row back, and at its next step sets s_setprio 3 - rank.  The reads may be a step old or see a
 // neighbour's entry mid-update: priority never changes what a game computes, only when it issues.
+// The estimate is (units + own idle units + RANK_C) x steps left.  One game alone on a SIMD takes ~ a + b x units
+// per step with a / b ~ 75 units (E = 1024 span data), so the steps left dominate: the games that fell behind issue
+// first (c3, 3 runs each: C = 0 315.5 / 285.3 M at K = 200 / 20, C = 75 334.4 / 285.5, C = 150 334.1 / 280.7, C = 400
+// 333.6 / 284.5; later, with balanced placement and the byte image, C = 4000 vs 400: K = 20 kernel 11.95 vs 12.08 us
+// per step over 4 pairs, K = 200 equal — a game one step behind always outranks, units break ties).
+constexpr int RANK_C = 4000;
 struct SimdRank {
     uint32_t* row;  // this SIMD's 16 entries (stamp << 24 | estimate; 0 = free)
     int me;         // this wave's slot in the row
@@ -5262,15 +5007,19 @@ DEV int simdRankStep(SimdRank& r, uint32_t est) {
 // mean.  The dispatcher places blocks b, b + n/4, b + 2n/4, b + 3n/4 on one SIMD (one dispatch round of
 // four waves per SIMD; identical in every launch and process measured; c5's 128-thread blocks: the game waves
 // of b and b + n/2), so a permutation of games over blocks that gives each such group a heavy-to-light mix
-// balances the SIMDs.  Each game posts its cost (units + own idle units, MRTS_BAL_COST_IDLE) at the end of a launch; the last wave of each XCD class counting-sorts that class's posted
+// balances the SIMDs.  Each game posts its cost (units + own idle units) at the end of a launch; the last wave of each XCD class counting-sorts that class's posted
 // counts and writes its part of the permutation for the next launches — snake order over the groups,
 // so a group gets one game from each quarter of the order, heavy paired with light — and the stamp.  A launch whose predecessor on the
 // handle left a permutation uses it (block b runs game perm[b]), else identity.  The permutation is
-// sticky: only launches of at least MRTS_BAL_MIN_ITER steps post costs and write a new one, shorter
+// sticky: only launches of at least BAL_MIN_ITER steps post costs and write a new one, shorter
 // ones reuse the last (a game that changes CU pays cold TLB misses for its output pages: moving games
 // at every launch cost a 20-step launch ~12 us, round 3 span data).  Which block runs a
 // game never changes what the game computes: correctness needs only that perm is a permutation
 // (a counting sort's output is one), and a missing or stale posted cost leaves the old stamp in place.
+// c5 (partially observable 32x32 self-play with helper waves) is placed the same way, BAL_PO_GS games per group: the
+// dispatcher puts the game waves of blocks b and b + n / 2 on one SIMD (round 6 span data,
+// profiles/round6/placement_c5.json); c5 +0.6 %.
+constexpr int BAL_MIN_ITER = 64, BAL_PO_GS = 2;
 DEV int balancedGame(const KDyn& D) {
     const int n = (int)gridDim.x;
     const int32_t hdr1 = __builtin_nontemporal_load(D.bal + 1);
@@ -5283,7 +5032,7 @@ DEV void balancePerm(const KDyn& D, uint32_t* hist, int c, int GS) {
     // left in that XCD's L2 stays near; round 6: one permutation over all games, balancing the XCDs' loads
     // too, was 1.2 % slower on c3 and -0.5 % on c5), and each class's LAST wave sorts that class alone: n / 8
     // games, n / 32 SIMD groups, the snake order as above (1/8 of the work on the launch's tail)
-    // GS: games per SIMD group (c3: four game waves per SIMD; c5: MRTS_BAL_PO_GS), blocks n / GS apart
+    // GS: games per SIMD group (c3: four game waves per SIMD; c5: BAL_PO_GS), blocks n / GS apart
     const int n = (int)gridDim.x, l = lane_id(), Q = (int)((uint32_t)n / (8u * (uint32_t)GS)), per = n >> 9;  // per: games per lane
     int32_t* const cost = D.bal + BAL_COST;
     int32_t* const perm = cost + n;
@@ -5371,7 +5120,6 @@ DEV void helperLoopPO(Game& G, uint32_t* hdr, int niter) {
     uint32_t* const recs = hdr + PO_HELP_REC;
     G.helperLane();
     const int l = G.lid();
-    if (MRTS_HELPER_PRIO) __builtin_amdgcn_s_setprio(3);  // the games wait for it at the handoff barriers
     for (int k = 0; k < niter; k++) {
         ldsBarrier();  // B_k
         const uint32_t* ph = hdr + (k & 1) * 4;
@@ -5384,9 +5132,7 @@ DEV void helperLoopPO(Game& G, uint32_t* hdr, int niter) {
             }
             G.renderPOPacked(pk, ph, rows0, hcell, k == niter - 1);
             if (k + 1 == niter) ldsBarrier();  // S_last: the game's masks of the last step are out
-#ifndef MRTS_DIAG_HELPER_NORECORDS  // diagnostic build only: the helper skips the record stores (output wrong)
             G.storeRecordsHelp(recs);  // step k's mask records and policy rows (written before S_k)
-#endif
         } else if (f & 8u) {
             // the game's live state, as its own writeObsPO call would see it (the general render
             // overwrites `scell`, so the pack's record words are taken first)
@@ -5416,14 +5162,13 @@ __global__ __launch_bounds__(HELP ? 128 : 64, (HELP || FIX == 16) ? 4 : 1) void 
     const KStatic& P = *PS;
     // balanced placement (c3's and c5's multi-step kernels): this block's game from the previous launch's permutation
     // (balancePerm: a multiple of 512 games, at most 8 per lane and class)
-    const bool balanced = MULTI && MRTS_BALANCE && ((FIX == 16 && !FPO) || (MRTS_BALANCE_PO && FIX == 32 && FPO && HELP)) &&
-                          D.bal != nullptr && (gridDim.x & 511) == 0 &&
-                          gridDim.x <= 4096;
-    const bool rebalance = balanced && D.n_iter >= MRTS_BAL_MIN_ITER;  // this launch writes the next permutation
+    const bool balanced = MULTI && ((FIX == 16 && !FPO) || (FIX == 32 && FPO && HELP)) && D.bal != nullptr &&
+                          (gridDim.x & 511) == 0 && gridDim.x <= 4096;
+    const bool rebalance = balanced && D.n_iter >= BAL_MIN_ITER;  // this launch writes the next permutation
     const int game = balanced ? balancedGame(D) : -1;
     Game G(P, D, stateArg, FIX ? stateWords(FCAP, FIX * FIX) : D.state_words, smem, FIX ? FIX : D.H, FIX ? FIX : D.W, FIX ? FIX * FIX : D.HW, FIX ? FCAP : D.CAP,
            FIX ? FPO : P.partial_obs != 0, FIX ? 79 : P.utt.K, FIX ? 7 : P.utt.ntypes, FIX ? 7 : P.utt.maxAttackRadius, MULTI, game,
-           MRTS_INDEX_WALK && (FIX == 16 || (MRTS_WALK32 && FIX == 32)));
+           FIX == 16 || FIX == 32);  // `walk`: the 16x16 instances (round 5) and c5's 32x32 (round 6: c5 +2.8 %)
     // the partially observable helper wave: one packed render per step (helperLoopPO)
     uint32_t* const poHelpHdr = (HELP && FPO) ? (uint32_t*)(smem + D.help_off) : nullptr;
     if (HELP && FPO && threadIdx.x >= 64) {
@@ -5487,9 +5232,9 @@ __global__ __launch_bounds__(HELP ? 128 : 64, (HELP || FIX == 16) ? 4 : 1) void 
 #endif
     uint32_t* const helpBuf = (HELP && !FPO) ? (uint32_t*)(smem + D.help_off) : nullptr;  // helperLoop's layout
     bool poPacked = false;  // HELP && FPO: the previous iteration handed its render to the helper (packPO, flag 4)
-    // c3 (four games per SIMD) and c5 (two games + their helper waves, which keep priority 0)
-    const bool ranked = MULTI && MRTS_SIMD_RANK && (FIX == 16 || (FIX == 32 && FPO && MRTS_SIMD_RANK_PO)) &&
-                        D.prio_tab != nullptr && niter > 1;
+    // c3 (four games per SIMD) only: on c5 the rank measured -4 % (its games outrank their own helper
+    // waves, which then reach the handoff barriers late; round 3)
+    const bool ranked = MULTI && FIX == 16 && D.prio_tab != nullptr && niter > 1;
     SimdRank srank;
     if (ranked) srank = simdRankInit(D.prio_tab, D.fwd_stamp);
     if (HELP && !FPO) __syncthreads();  // A_0: the helper drew step 0's rows
@@ -5498,40 +5243,37 @@ __global__ __launch_bounds__(HELP ? 128 : 64, (HELP || FIX == 16) ? 4 : 1) void 
         G.nextStep();
         freshObs = true;
     }
-#if MRTS_BODY_LAUNDER
-    // the step body reads the kernel argument through the Game's per-iteration opaque pointer too (as its
-    // methods do, freshLane): the by-value argument's fields and the conditions derived from them were
-    // loaded once before the loop and held across it in spilled SGPRs — a v_readlane per use, every step
-    auto& D = *G.Dp;
-#endif
+    // (the step body reads the by-value argument D, not the Game's per-iteration opaque pointer as its methods
+    // do, freshLane: through the pointer SGPR spills went 153 -> 136 but c3 / c5 / c2 lost 0 to 0.6 %, the
+    // re-read fields waiting on scalar loads where the spilled ones were a readlane; round 6)
     if (HELP && !FPO) G.helpRows = helpBuf + (it & 1) * 2 * 64;
     G.lastIt = it == niter - 1;
     G.firstIt = it == 0;
     bool snapTaken = false;
-    if (MODE != MODE_RESET && !(MULTI && MRTS_MULTI_NOPRIO)) {
+    if (MODE != MODE_RESET) {
         // Issue priority by game size: a SIMD runs several games at once and the kernel ends with its
         // slowest one, so the games with the most units (the longest serial chains) issue first.
         int q;
-        if (MRTS_PRIO_IDLE && FIX == 16) {
+        constexpr int PRIO_T1 = 29, PRIO_T2 = 35, PRIO_T3 = 41;  // priority 1 / 2 / 3 from this many units + idle units
+        if (FIX == 16) {
             // the c3 shape (four games per SIMD): units + own idle units (the step's decode / issue /
-            // mask / policy work grows with the idle ones)
+            // mask / policy work grows with the idle ones; against units alone at 24 / 30 / 36: c3 +1.8 % at
+            // K = 200, +0.8 % at K = 20)
             const int wq = G.nu + (int)__popcll(ballot(G.lid() < G.nu && !(G.lua & UA_PRESENT) && uplay(G.lcu) >= 0));
-            q = wq >= MRTS_PRIO_T3 ? 3 : wq >= MRTS_PRIO_T2 ? 2 : wq >= MRTS_PRIO_T1 ? 1 : 0;
+            q = wq >= PRIO_T3 ? 3 : wq >= PRIO_T2 ? 2 : wq >= PRIO_T1 ? 1 : 0;
             if (ranked) {  // from the second step on: the rank among the SIMD's waves by remaining work
-                const int rk = simdRankStep(srank, (uint32_t)(wq + MRTS_RANK_C) * (uint32_t)(niter - it));
+                const int rk = simdRankStep(srank, (uint32_t)(wq + RANK_C) * (uint32_t)(niter - it));
                 if (it > 0) q = 3 - (rk < 3 ? rk : 3);
             }
         } else {  // units (the idle count's ballot costs the latency-bound one-game-per-SIMD c2 4.5 %)
             // (c5, two games + their helper waves per SIMD: without any priority -9 %, the games all at 3 or all
             // above the helpers' 0 +-0.5 % — what counts is the games issuing before the helpers, round 6)
             q = G.nu >= 36 ? 3 : G.nu >= 30 ? 2 : G.nu >= 24 ? 1 : 0;
-            if (ranked) {
-                const int wq = G.nu + (int)__popcll(ballot(G.lid() < G.nu && !(G.lua & UA_PRESENT) && uplay(G.lcu) >= 0));
-                const int rk = simdRankStep(srank, (uint32_t)(wq + MRTS_RANK_C) * (uint32_t)(niter - it));
-                if (it > 0) q = 3 - (rk < 3 ? rk : 3);
-            }
         }
-        if (HELP && !FPO && MRTS_GAME_OVER_HELPER) q = q < 1 ? 1 : q;
+        // c2's helper-wave launches: the game wave issues at priority >= 1, ahead of its helper wave (at 0) — round 6:
+        // c2 +1.6 % / +0.4 % over two rounds of interleaved runs (the helper at 3 instead: -4.5 %); on c5 +0.5 % /
+        // -0.6 %, so c5 keeps its unit-count priorities, which already put most of its games above their helpers
+        if (HELP && !FPO) q = q < 1 ? 1 : q;
         if (q == 0) {
             if (it > 0) __builtin_amdgcn_s_setprio(0);
         } else if (q == 1) __builtin_amdgcn_s_setprio(1);
@@ -5544,10 +5286,8 @@ __global__ __launch_bounds__(HELP ? 128 : 64, (HELP || FIX == 16) ? 4 : 1) void 
     if (G.po) G.clearSnap();
     if (HELP && FPO && poPacked) {  // S_{it-1}: the helper's snapshot of this step (snapFromPack)
         ldsBarrier();
-#ifndef MRTS_PO_HELPER_NOSNAP  // diagnostic build: the game wave takes its own snapshot
         G.takeSnap((const uint8_t*)(poHelpHdr + 8 + 2 * G.H));
         snapTaken = true;
-#endif
     }
     PHASE(0);
 
@@ -5644,7 +5384,7 @@ __global__ __launch_bounds__(HELP ? 128 : 64, (HELP || FIX == 16) ? 4 : 1) void 
             G.issuePlayer(1 - side, 10, true);
         } else if (gtype == GT_SELFPLAY) {
             // JNIGridnetClientSelfPlay.gameStep (tests/JNIGridnetClientSelfPlay.java:159-189)
-            if (MRTS_LIKELY(G.nu <= 64 && (!G.po || (MRTS_PO_FAST && G.snapBothOk())))) {
+            if (MRTS_LIKELY(G.nu <= 64 && (!G.po || G.snapBothOk()))) {
                 G.selfPlayFast(D.actions + (size_t)slot0 * rowStride, D.actions + (size_t)(slot0 + 1) * rowStride, slot0,
                                snapTaken);
             } else {
@@ -5706,7 +5446,7 @@ __global__ __launch_bounds__(HELP ? 128 : 64, (HELP || FIX == 16) ? 4 : 1) void 
         const bool done0 = G.writeRewards(slot0, nslots, selfplay ? 0 : side, selfplay ? 1 : side, gameover, winner, it);
         const bool reset = done0 || steps >= D.max_steps;
         if (reset && D.done && lane_id() < nslots)
-            D.done[(MRTS_RESP_RING ? (size_t)((uint32_t)it * (uint32_t)D.resp_stride) : 0) + (size_t)(slot0 + lane_id()) * D.n_rewards] = 1;
+            D.done[(size_t)((uint32_t)it * (uint32_t)D.resp_stride) + (size_t)(slot0 + lane_id()) * D.n_rewards] = 1;
         if (MRTS_UNLIKELY(reset)) {
             G.hset(H_STEPS, 0);  // envSteps[i] = 0 (JNIGridnetVecClient.java:229,264-265,285)
             G.resetFromTemplate();
@@ -5825,8 +5565,10 @@ __global__ __launch_bounds__(HELP ? 128 : 64, (HELP || FIX == 16) ? 4 : 1) void 
     if (rebalance) {  // post this game's final unit count; the launch's LAST wave writes the next placement
         const uint32_t tag = D.fwd_stamp & 0xFFFFu;
         uint32_t last = 0;
-        const int cost = MRTS_BAL_COST_IDLE ? G.nu + (int)__popcll(ballot(G.lid() < G.nu && !(G.lua & UA_PRESENT) && uplay(G.lcu) >= 0))
-                                            : G.nu;
+        // the cost posted for the next placement: units + own idle units at the launch's last step, the estimate
+        // the SIMD rank uses (round 6, against the unit count: c3 K = 20 kernel -0.6 %, c5 +0.4 %; the estimate
+        // averaged over the launch's steps was worse)
+        const int cost = G.nu + (int)__popcll(ballot(G.lid() < G.nu && !(G.lua & UA_PRESENT) && uplay(G.lcu) >= 0));
         if (lane_id() == 0) {
             // agent scope, written through: the last wave may sit on another XCD (another L2)
             __hip_atomic_store(D.bal + BAL_COST + G.g, (int32_t)((tag << 16) | (uint32_t)(cost < 255 ? cost : 255)),
@@ -5840,7 +5582,7 @@ __global__ __launch_bounds__(HELP ? 128 : 64, (HELP || FIX == 16) ? 4 : 1) void 
         }
         if (uniu(last)) {
             wsync();
-            balancePerm(D, (uint32_t*)smem, (int)(blockIdx.x & 7u), FIX == 16 ? 4 : MRTS_BAL_PO_GS);
+            balancePerm(D, (uint32_t*)smem, (int)(blockIdx.x & 7u), FIX == 16 ? 4 : BAL_PO_GS);
         }
     }
     PHASE(10);
@@ -6310,16 +6052,11 @@ __global__ __launch_bounds__(256) void k_render_records_po(const KStatic* __rest
         for (int p = 0; p < 2; p++) {
             if (!((sb >> p) & 1u)) continue;
             atomicMax(&sc[p * HW + c], (uint32_t)(i + 1));
-#ifdef MRTS_RENDER_NOPAINT  // diagnostic build: the render without its sight disks
-            if (false)
-#else
             if (pl >= 0 && !rowPaint)
-#endif
                 paintDiskRows(rows + (2 * p + (pl == p ? 0 : 1)) * NR, H, W, x, y, P.utt.sight[ty], P.utt.diskLo[ty],
                               P.utt.diskHi[ty]);
         }
     }
-#ifndef MRTS_RENDER_NOPAINT
     if (rowPaint) {
         // every (unit, row offset) pair on its own thread: 8 units x 32 row offsets per pass (2 SM + 1 <= 31),
         // one atomicOr per view the unit is in — not one thread looping over a unit's rows
@@ -6339,7 +6076,6 @@ __global__ __launch_bounds__(256) void k_render_records_po(const KStatic* __rest
             }
         }
     }
-#endif
     __syncthreads();
     const uint32_t* terr = (const uint32_t*)(P.tmpl + P.tmpl_off[g] + T_TERR);
     const int WPR = (W + 31) >> 5;
@@ -6550,16 +6286,7 @@ hipError_t launchEnv(int mode, const KStatic& hs, const KStatic* ds, const KDyn&
     const bool fixable = hs.n_sp_games == hs.n_games && D.rows == nullptr && hs.utt.K == 79 && hs.utt.ntypes == 7 &&
                          hs.utt.maxAttackRadius == 7 && hs.H == hs.W;
     auto is = [&](int w, int cap, bool po) { return fixable && hs.W == w && hs.CAP == cap && (hs.partial_obs != 0) == po; };
-#if MRTS_EXT_EVENTS
 #define LAUNCH(kern, g_, b_, l_, s_, ...) hipExtLaunchKernelGGL(kern, g_, b_, (uint32_t)(l_), s_, e0, e1, 0, __VA_ARGS__)
-#else  // events as separate records around the launch (A/B builds)
-#define LAUNCH(kern, g_, b_, l_, s_, ...)                                 \
-    do {                                                                  \
-        if (e0) (void)hipEventRecord(e0, s_);                             \
-        hipLaunchKernelGGL(kern, g_, b_, (uint32_t)(l_), s_, __VA_ARGS__); \
-        if (e1) (void)hipEventRecord(e1, s_);                             \
-    } while (0)
-#endif
     switch (mode) {
         case MODE_STEP:
             if (D.n_iter > 1 && is(16, 320, false)) LAUNCH((k_env<MODE_STEP, 16, 320, false, true>), grid, block, lds, stream, D.state, ds, D);
