@@ -32,7 +32,10 @@ extern "C" {
 
 typedef struct mrts_env mrts_env;
 
-enum { MRTS_BOT_PASSIVE = 0, MRTS_BOT_RANDOM_BIASED = 1 };
+/* native AIs.  LIGHT_RUSH = ai.abstraction.LightRush(utt) (A* pathfinding): bot-only clients and the opponent of
+   an agent-vs-bot environment; maps of at most 1024 cells, a unit-type table with types named Base, Barracks,
+   Worker and Light; refused (-ENOTSUP) as a forward-model playout policy and, as an opponent, with partial_obs */
+enum { MRTS_BOT_PASSIVE = 0, MRTS_BOT_RANDOM_BIASED = 1, MRTS_BOT_LIGHT_RUSH = 2 };
 
 /* reward functions, a_rfs (:106): the classes of src/ai/reward */
 enum {
@@ -64,7 +67,8 @@ typedef struct {
     int32_t partial_obs;        /* partial_obs (:107) — 8 observation planes when set */
     int32_t utt_version;        /* new UnitTypeTable(version, crs): 1 ORIGINAL, 2 FINETUNED, 3 NON_DETERMINISTIC */
     int32_t conflict_policy;    /* 1 CANCEL_BOTH, 2 CANCEL_RANDOM, 3 CANCEL_ALTERNATING (UnitTypeTable.java:46-57) */
-    const int32_t* bot_kinds;   /* a_ai2s (:107): per bot env, MRTS_BOT_* ; NULL = all passive */
+    const int32_t* bot_kinds;   /* a_ai2s (:107): per bot env, MRTS_BOT_* (PASSIVE, RANDOM_BIASED or
+                                   LIGHT_RUSH); NULL = all passive */
     const int32_t* ai1_kinds;   /* non-NULL selects the bot-only client (:157-177, JNIBotClient): per env the
                                    MRTS_BOT_* of a_ai1s (bot_kinds = a_ai2s); n_selfplay_slots must be 0;
                                    observations and masks are not produced (Java returns null) */

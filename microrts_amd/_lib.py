@@ -6,7 +6,7 @@ import os
 HERE = os.path.dirname(os.path.abspath(__file__))
 LIB_PATH = os.environ.get("MRTS_LIB_PATH") or os.path.join(HERE, "libmrts.so")  # override: diagnostics builds only
 
-MRTS_BOT_PASSIVE, MRTS_BOT_RANDOM_BIASED = 0, 1
+MRTS_BOT_PASSIVE, MRTS_BOT_RANDOM_BIASED, MRTS_BOT_LIGHT_RUSH = 0, 1, 2
 MRTS_MAX_HORIZON = 65536
 # a_rfs names (src/ai/reward/*.java) -> MRTS_RF_* ids
 REWARD_FUNCTIONS = {"WinLossRewardFunction": 0, "ResourceGatherRewardFunction": 1, "ProduceWorkerRewardFunction": 2,

@@ -23,6 +23,7 @@ using namespace mrts;
 
 namespace mrts {
 size_t ldsBytes(int HW, int W, int CAP, int po);
+size_t lrLdsBytes(int HW, int W, int CAP);
 hipError_t launchEnv(int mode, const KStatic& hs, const KStatic* ds, const KDyn& D, hipStream_t stream, hipEvent_t e0 = nullptr,
                      hipEvent_t e1 = nullptr);
 bool envIterable(const KStatic& hs);
@@ -45,7 +46,7 @@ hipError_t launchWiden(const uint8_t* in, int32_t* out, size_t n, hipStream_t st
 hipError_t launchOneHot(const int32_t* obs, uint8_t* out, int n_slots, int HW, int C, int ntypes, hipStream_t stream);
 hipError_t prepareLds(size_t bytes);
 hipError_t launchCopyGames(int32_t* dst, const int32_t* src, const int32_t* pairs, int n, int n_dst, int n_src,
-                           int CAP, int HW, hipStream_t stream);
+                           int CAP, int HW, int src_words, hipStream_t stream);
 hipError_t launchEvaluate(const KStatic& hs, const KStatic* ds, int maxplayer, float* out, hipStream_t stream);
 hipError_t launchRenderRecords(const KStatic& hs, const KStatic* ds, const uint32_t* rec, int units, int n_ranks,
                                int64_t rank_stride, void* out, int out_bytes, int32_t* err, hipStream_t stream);
@@ -456,6 +457,15 @@ struct mrts_env {
     int nSlots = 0, nGames = 0, nSpGames = 0, maxSteps = 0, partialObs = 0;
     int forwardModel = 0;  // games advance through mrts_playout* only (GT_PLAYOUT)
     int maxUnits = 0;      // live-unit bound (H*W unless mrts_config.max_units)
+    // native LightRush: the handle has a LightRush game, so every state block carries the bot's memory
+    // (mrts_internal.h botWords) after its stateWords; botTypes = the types named Base, Barracks, Worker, Light
+    int hasLightRush = 0;
+    uint32_t botTypes = 0;
+    size_t blockWords() const { return (size_t)stateWords(CAP, HW) + (hasLightRush ? (size_t)botWords(CAP) : 0); }
+    size_t ldsNeed() const {
+        const size_t base = (ldsBytes(HW, W, CAP, partialObs) + 15) & ~(size_t)15;
+        return hasLightRush ? base + lrLdsBytes(HW, W, CAP) : ldsBytes(HW, W, CAP, partialObs);
+    }
     uint32_t slotIdBase = 0;
     DevUtt utt;
     UttInfo uttInfo;
@@ -593,11 +603,14 @@ struct mrts_env {
         hstatic.tmpl = d_tmpl;
         hstatic.tmpl_off = d_tmplOff;
         hstatic.game_kind = d_gameKind;
+        hstatic.bot_off = hasLightRush ? stateWords(CAP, HW) : 0;
+        hstatic.bot_lds = hasLightRush ? (int32_t)((ldsBytes(HW, W, CAP, partialObs) + 15) & ~(size_t)15) : 0;
+        hstatic.bot_types = botTypes;
     }
     hipError_t launch(int mode, const KDyn& Din, hipStream_t s, hipEvent_t e0 = nullptr, hipEvent_t e1 = nullptr) const {
         KDyn D = Din;
         D.state = d_state;
-        D.state_words = stateWords(CAP, HW);
+        D.state_words = (int32_t)blockWords();
         D.H = H;
         D.W = W;
         D.HW = HW;
@@ -706,8 +719,30 @@ int mrts_create(const mrts_config* cfg, mrts_env** out) {
         for (int j = 0; j < cfg->n_bot_envs; j++) {
             const int k2 = cfg->bot_kinds ? cfg->bot_kinds[j] : MRTS_BOT_PASSIVE;
             const int k1 = cfg->ai1_kinds ? cfg->ai1_kinds[j] : MRTS_BOT_PASSIVE;
-            if (k1 < 0 || k1 > 1 || k2 < 0 || k2 > 1) throw Fail{-ENOTSUP, "only PassiveAI / RandomBiasedAI are native"};
+            if (k1 < 0 || k1 > MRTS_BOT_LIGHT_RUSH || k2 < 0 || k2 > MRTS_BOT_LIGHT_RUSH)
+                throw Fail{-ENOTSUP, "only PassiveAI / RandomBiasedAI / LightRush are native"};
             const int type = env->forwardModel ? 3 : (cfg->ai1_kinds ? 2 : 1);  // GT_PLAYOUT / BOT_VS_BOT / AGENT_VS_BOT
+            if (k1 == MRTS_BOT_LIGHT_RUSH || k2 == MRTS_BOT_LIGHT_RUSH) {
+                // refused, not approximated: a playout policy has no memory to carry between copies of a game, and
+                // JNIGridnetClient.gameStep runs the opponent on its PartiallyObservableGameState
+                // (tests/JNIGridnetClient.java:164-173) — LightRush on a view is a different bot
+                if (env->forwardModel)
+                    throw Fail{-ENOTSUP, "LightRush is not available as a forward-model playout policy (its memory of abstract "
+                                         "actions is not part of a copied game)"};
+                if (cfg->partial_obs && type == 1)
+                    throw Fail{-ENOTSUP, "partial_obs + LightRush opponent: Java runs the bot on the player's partially "
+                                         "observable view, which this build does not compute for LightRush"};
+                int ids[4] = {-1, -1, -1, -1};
+                static const char* const need[4] = {"Base", "Barracks", "Worker", "Light"};
+                for (int q = 0; q < 4; q++)
+                    for (int t = 0; t < env->utt.ntypes; t++)
+                        if (env->uttInfo.names[(size_t)t] == need[q] && ids[q] < 0) ids[q] = t;
+                for (int q = 0; q < 4; q++)
+                    if (ids[q] < 0)
+                        throw Fail{-ENOTSUP, std::string("LightRush needs a unit type named ") + need[q] + " in the unit-type table"};
+                env->botTypes = (uint32_t)ids[0] | ((uint32_t)ids[1] << 4) | ((uint32_t)ids[2] << 8) | ((uint32_t)ids[3] << 12);
+                env->hasLightRush = 1;
+            }
             env->gameKindHost[(size_t)(env->nSpGames + j)] = type | (k1 << 4) | (k2 << 8);
             // JNIGridnetClient.gameStep runs the opponent on its PartiallyObservableGameState
             // (tests/JNIGridnetClient.java:164-173).  The GPU RandomBiasedAI takes getUnitActions of an
@@ -758,12 +793,14 @@ int mrts_create(const mrts_config* cfg, mrts_env** out) {
         env->maxUnits = maxUnits;
         if (env->CAP > 0xFFF0) throw Fail{-EINVAL, "map too large"};
         if ((size_t)env->nSlots * env->HW >= (size_t)1 << 31) throw Fail{-EINVAL, "n_slots * H * W must be < 2^31"};
+        if (env->hasLightRush && env->HW > LR_MAX_CELLS)
+            throw Fail{-ENOTSUP, "LightRush: the map has more than 1024 cells (the size limit of the native A* pathfinder)"};
         // everything above is host-only validation (testable without a GPU); device work starts here
         HIPCHK(hipSetDevice(cfg->device));
         HIPCHK(hipStreamCreateWithFlags(&env->stream, hipStreamNonBlocking));
         hipDeviceProp_t prop;
         HIPCHK(hipGetDeviceProperties(&prop, cfg->device));
-        const size_t lds = ldsBytes(env->HW, env->W, env->CAP, env->partialObs);
+        const size_t lds = env->ldsNeed();
         if (lds > 160 * 1024) throw Fail{-EINVAL, "map too large for LDS"};
         if (lds > 64 * 1024) HIPCHK(prepareLds(lds));
         for (auto& m : maps)
@@ -816,7 +853,7 @@ int mrts_create(const mrts_config* cfg, mrts_env** out) {
             mix(env->rewardKinds.data(), env->rewardKinds.size() * sizeof(env->rewardKinds[0]));
             env->cfgHash = hv;
         }
-        const size_t sw = (size_t)stateWords(env->CAP, env->HW);
+        const size_t sw = env->blockWords();
         HIPCHK(hipMalloc(&env->d_state, sw * env->nGames * 4));
         if (env->partialObs && poDeltaShape(env->H, env->W)) {  // PO render records (delta observations)
             env->poWords = poPrevWords(env->CAP, env->H, env->HW);
@@ -1922,7 +1959,7 @@ int mrts_get_state(mrts_env* env, int32_t slot, int32_t* buf, int32_t cap) {
         if (slot < 0 || slot >= env->nSlots) throw Fail{-EINVAL, "slot out of range"};
         int pl;
         const int g = env->gameOfSlot(slot, &pl);
-        const size_t sw = (size_t)stateWords(env->CAP, env->HW);
+        const size_t sw = env->blockWords();
         std::vector<int32_t> s(sw);
         HIPCHK(hipStreamSynchronize(env->stream));
         HIPCHK(hipMemcpy(s.data(), env->d_state + (size_t)g * sw, sw * 4, hipMemcpyDeviceToHost));
@@ -1980,7 +2017,7 @@ int mrts_utt_json(int32_t utt_version, int32_t conflict_policy, const char* utt_
 }
 
 static int readHeaderWord(mrts_env* env, int word, int32_t* out_per_slot) {
-    const size_t sw = (size_t)stateWords(env->CAP, env->HW);
+    const size_t sw = env->blockWords();
     HIPCHK(hipStreamSynchronize(env->stream));
     std::vector<int32_t> w((size_t)env->nGames);
     HIPCHK(hipMemcpy2D(w.data(), 4, env->d_state + word, sw * 4, 4, (size_t)env->nGames, hipMemcpyDeviceToHost));
@@ -2052,7 +2089,7 @@ void mrts_destroy(mrts_env* env) {
 
 // ---------------------------------------------------------------- state serialisation (checkpoint / interop)
 static void readBlock(mrts_env* env, int g, std::vector<int32_t>& s) {
-    const size_t sw = (size_t)stateWords(env->CAP, env->HW);
+    const size_t sw = env->blockWords();
     s.resize(sw);
     HIPCHK(hipStreamSynchronize(env->stream));
     HIPCHK(hipDeviceSynchronize());
@@ -2224,6 +2261,8 @@ int mrts_set_state_json(mrts_env* env, int32_t slot, const char* json) {
         std::vector<int32_t> s;
         readBlock(env, g, s);
         jsonToBlock(env, json, s);
+        // an injected state starts with fresh AIs: the LightRush memory of this game is cleared
+        std::fill(s.begin() + stateWords(env->CAP, env->HW), s.end(), 0);
         env->noteValues(s.data());
         const size_t sw = s.size();
         HIPCHK(hipMemcpy(env->d_state + (size_t)g * sw, s.data(), sw * 4, hipMemcpyHostToDevice));
@@ -2256,7 +2295,7 @@ uint32_t uttHash(const DevUtt& u) {
 
 int64_t mrts_checkpoint_size(const mrts_env* env) {
     if (!env) return -EINVAL;
-    return (int64_t)sizeof(CkptHeader) + (int64_t)stateWords(env->CAP, env->HW) * env->nGames * 4;
+    return (int64_t)sizeof(CkptHeader) + (int64_t)env->blockWords() * env->nGames * 4;
 }
 
 int mrts_checkpoint(mrts_env* env, void* buf, int64_t cap) {
@@ -2272,7 +2311,7 @@ int mrts_checkpoint(mrts_env* env, void* buf, int64_t cap) {
         h.CAP = env->CAP;
         h.nGames = env->nGames;
         h.nSpGames = env->nSpGames;
-        h.words = stateWords(env->CAP, env->HW);
+        h.words = (int32_t)env->blockWords();
         h.uttHash = uttHash(env->utt);
         h.cfgHash = env->cfgHash;
         std::memcpy(buf, &h, sizeof(h));
@@ -2292,7 +2331,7 @@ int mrts_restore(mrts_env* env, const void* buf, int64_t size) {
         std::memcpy(&h, buf, sizeof(h));
         if (std::memcmp(h.magic, "MRTSCKP1", 8) != 0 || h.version != 3) throw Fail{-EINVAL, "not a checkpoint"};
         if (h.H != env->H || h.W != env->W || h.CAP != env->CAP || h.nGames != env->nGames || h.nSpGames != env->nSpGames ||
-            h.words != stateWords(env->CAP, env->HW) || h.uttHash != uttHash(env->utt))
+            h.words != (int32_t)env->blockWords() || h.uttHash != uttHash(env->utt))
             throw Fail{-EINVAL, "checkpoint of a different configuration"};
         if (h.cfgHash != env->cfgHash)
             throw Fail{-EINVAL, "checkpoint of a different configuration (opponents, maps, max_steps, reward functions "
@@ -2316,6 +2355,8 @@ int mrts_restore(mrts_env* env, const void* buf, int64_t size) {
 static void checkCopy(const mrts_env* dst, const mrts_env* src) {
     if (!dst || !src) throw Fail{-EINVAL, "null handle"};
     if (!dst->forwardModel) throw Fail{-EINVAL, "copy destination must be a forward-model handle"};
+    // launchCopyGames writes destination blocks of stateWords: a forward model never has LightRush memory (mrts_create)
+    if (dst->hasLightRush) throw Fail{-ENOTSUP, "copy destination carries LightRush memory"};
     if (src->H != dst->H || src->W != dst->W || src->CAP != dst->CAP) throw Fail{-EINVAL, "handles differ in map size"};
     if (std::memcmp(&src->utt, &dst->utt, sizeof(DevUtt)) != 0) throw Fail{-EINVAL, "handles differ in unit-type table"};
     if (src->device != dst->device) throw Fail{-EINVAL, "handles live on different devices"};
@@ -2328,7 +2369,7 @@ int mrts_copy_games_dev(mrts_env* dst, const mrts_env* src, const int32_t* d_pai
         if (n < 0 || (n > 0 && !d_pairs)) throw Fail{-EINVAL, "bad pairs"};
         HIPCHK(hipSetDevice(dst->device));
         HIPCHK(launchCopyGames(dst->d_state, src->d_state, d_pairs, n, dst->nGames, src->nGames, dst->CAP, dst->HW,
-                               pickStream(dst, stream)));
+                               (int)src->blockWords(), pickStream(dst, stream)));
         dst->lastObsPtr = nullptr;
         return 0;
     } catch (const Fail& f) {
@@ -2364,7 +2405,7 @@ int mrts_copy_games(mrts_env* dst, const mrts_env* src, const int32_t* pairs, in
         }
         HIPCHK(hipMemcpyAsync(dst->d_copyPairs, pairs, (size_t)n * 2 * 4, hipMemcpyHostToDevice, dst->stream));
         HIPCHK(launchCopyGames(dst->d_state, src->d_state, dst->d_copyPairs, n, dst->nGames, src->nGames, dst->CAP,
-                               dst->HW, dst->stream));
+                               dst->HW, (int)src->blockWords(), dst->stream));
         dst->lastObsPtr = nullptr;
         HIPCHK(hipStreamSynchronize(dst->stream));
         return 0;

@@ -75,6 +75,26 @@ constexpr int stateTerrOff(int cap, int hw) { return H_WORDS + N_ARRAYS * cap + 
 constexpr int FWD_WORDS = 64;
 constexpr int stateFwdOff(int cap, int hw) { return stateTerrOff(cap, hw) + (hw + 3) / 4; }
 constexpr int stateWords(int cap, int hw) { return stateFwdOff(cap, hw) + FWD_WORDS; }  // host + device
+// Handles with a LightRush game only (KStatic.bot_off != 0): every state block is followed by the bot's memory,
+// AbstractionLayerAI.actions (ai/abstraction/AbstractionLayerAI.java:36) of either player — per player BOT_HDR
+// words ([0] = the next insertion rank) and three arrays of CAP words indexed by the unit's slot:
+//   BA_ACT  kind (BK_*) | Train.completed << 3 | unit type << 4 | (Build.x + 1) << 8 | Build.y << 16
+//   BA_REF  target slot | base slot << 16 (Attack.target, Harvest.target / base; BR_NULL, BR_DEAD)
+//   BA_RANK the entry's LinkedHashMap insertion rank
+// Entries of slots >= H_NU are not meaningful (a load treats them as empty).  Self-play handles do not have it:
+// their stateWords, and so their kernels, are unchanged.
+constexpr int BOT_HDR = 4;
+enum { BA_ACT = 0, BA_REF = 1, BA_RANK = 2, BA_ARRAYS = 3 };
+enum { BK_NONE = 0, BK_TRAIN = 1, BK_BUILD = 2, BK_HARVEST = 3, BK_ATTACK = 4 };
+constexpr uint32_t BR_NULL = 0xFFFFu, BR_DEAD = 0xFFFEu;
+constexpr int botPlayerWords(int cap) { return BOT_HDR + BA_ARRAYS * cap; }
+constexpr int botWords(int cap) { return 2 * botPlayerWords(cap); }
+// the A* size limit of the native LightRush (its per-cell arrays are 16-bit, its open keys 12 + 13 bits)
+constexpr int LR_MAX_CELLS = 1024;
+// LDS of a LightRush handle after the game's own (KStatic.bot_lds): the bot memory, then the A* arrays (open key
+// u32, open cell / parent / cost u16 per cell), three position bitmaps of (HW + 2W) bits (the game state's
+// reservations, the running ResourceUsage, the PlayerAction's), the gs.free bitmap (HW bits), and per player the
+// accepted desires in order (u16 per slot) — lrLdsBytes in mrts_kernels.hip
 
 // unit core word
 constexpr uint32_t UC_DEAD = 1u << 31;
@@ -104,6 +124,11 @@ struct KStatic {
     int32_t n_rewards;             // reward functions per slot (a_rfs), 1..MAX_REWARDS
     int32_t reward_kinds[MAX_REWARDS];  // MRTS_RF_* in a_rfs order; reward / done are [n_slots][n_rewards]
     uint32_t reward_need;          // RN_* bits: which per-step bookkeeping the kinds need
+    // native LightRush (0 = the handle has no LightRush game): word offset of the bot memory in a state block
+    // (= stateWords(CAP, HW); a block is then bot_off + botWords(CAP) words), byte offset of the bot's LDS area,
+    // and the types named Base | Barracks << 4 | Worker << 8 | Light << 12
+    int32_t bot_off, bot_lds;
+    uint32_t bot_types;
 };
 enum : uint32_t { RN_COUNTS = 1, RN_CLOSER = 2, RN_RESOURCES = 4 };
 // Per-call buffers (kernel arguments by value)

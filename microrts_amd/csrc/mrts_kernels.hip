@@ -114,7 +114,7 @@ DEV int prodCategory(uint32_t typeFlags) {  // the reward functions' name tests 
     return (typeFlags & N_WORKER) ? RC_PROD_WORKER : (typeFlags & N_BUILDING) ? RC_PROD_BUILDING
                                                    : (typeFlags & N_COMBAT) ? RC_PROD_COMBAT : -1;
 }
-enum { GK_PASSIVE = 0, GK_RANDOM_BIASED = 1 };                    // AI kinds (bits 4-7 ai1, 8-11 ai2)
+enum { GK_PASSIVE = 0, GK_RANDOM_BIASED = 1, GK_LIGHT_RUSH = 2 };  // AI kinds (bits 4-7 ai1, 8-11 ai2)
 enum : uint32_t {
     E_CAPACITY = 1u << 0, E_ADDUNIT = 1u << 1, E_PRODUCE_TYPE = 1u << 2, E_OLDER = 1u << 3,
     E_NEG_RES = 1u << 4, E_COLLISION = 1u << 5, E_RECORD = 1u << 6
@@ -4873,13 +4873,591 @@ struct Game {
         }
         wsync();
     }
+
+    // ------------------------------------------------------------------ LightRush
+    // ai.abstraction.LightRush with AStarPathFinding, the bot of the reference's LightRush traces
+    // (src/tests/GenerateTestTraces.java:84-123), restated for one wave per game.  Generic kernel only, and only
+    // in games whose kind names it (k_env: `lr`); the members below are set by lrInit.
+    // The bot's memory — AbstractionLayerAI.actions (AbstractionLayerAI.java:36), a LinkedHashMap keyed by Unit —
+    // is indexed by unit slot (mrts_internal.h BA_*): an entry's insertion rank orders translateActions'
+    // iteration, put() on a live entry keeps its rank, a removed entry that is put again takes a new one.  Java
+    // holds Unit references (identity: Unit defines no equals); here a reference is the unit's slot, and
+    // lrCompact moves entries and rewrites references when the end-of-step compaction renumbers the slots.  A
+    // reference to a removed unit becomes BR_DEAD: Java only ever asks such a unit "are you still in the list"
+    // (Attack / Harvest.completed) or compares it with a live unit (LightRush.java:235,246) — both are false.
+    // Every scalar below is wave-uniform; the unit scans, the open-list minimum and the bitmaps use the lanes.
+    uint32_t* lrMem;    // [2][botPlayerWords(CAP)]: the state block's bot memory (hdr [1] = this step's desires)
+    uint32_t* lrKey;    // A*: open key per insertion number
+    uint32_t* lrGs;     // positions of gs.getResourceUsage(), bit pos + W (as `bits`)
+    uint32_t* lrRu;     // translateActions' running ResourceUsage ru
+    uint32_t* lrPa;     // the PlayerAction's ResourceUsage while the desires are composed
+    uint32_t* lrFree;   // !gs.free(x, y) per cell
+    uint16_t* lrCell;   // A*: cell per insertion number
+    uint16_t* lrPar;    // A*: parent cell per cell (0xFFFF = not in open or closed)
+    uint16_t* lrCost;   // A*: cost[] per cell (fixed at first discovery: there is no decrease-key)
+    uint16_t* lrOrd;    // [2][CAP]: per player the accepted desires' slots in pa order (scratch before that)
+    int lrRes0, lrRes1; // resourcesUsed of gs.getResourceUsage()
+    DEV void lrInit(uint8_t* q) {
+        const int NB2 = (HW + 2 * W + 31) / 32;
+        lrMem = (uint32_t*)q; q += 4 * botWords(CAP);
+        lrKey = (uint32_t*)q; q += 4 * HW;
+        lrGs = (uint32_t*)q; q += 4 * NB2;
+        lrRu = (uint32_t*)q; q += 4 * NB2;
+        lrPa = (uint32_t*)q; q += 4 * NB2;
+        lrFree = (uint32_t*)q; q += 4 * maskWords(HW);
+        lrCell = (uint16_t*)q; q += 2 * HW;
+        lrPar = (uint16_t*)q; q += 2 * HW;
+        lrCost = (uint16_t*)q; q += 2 * HW;
+        lrOrd = (uint16_t*)q;
+        lrRes0 = lrRes1 = 0;
+    }
+    DEV uint32_t* lrHdr(int p) const { return lrMem + p * botPlayerWords(CAP); }
+    DEV uint32_t* lrArr(int p, int a) const { return lrHdr(p) + BOT_HDR + a * CAP; }
+    DEV int lrType(int k) const { return (int)((P.bot_types >> (4 * k)) & 15u); }  // 0 Base 1 Barracks 2 Worker 3 Light
+    static DEV uint32_t lrAct(int kind, int ut, int bx, int by) {
+        return (uint32_t)kind | ((uint32_t)ut << 4) | (((uint32_t)(bx + 1) & 0xFFu) << 8) | (((uint32_t)by & 0xFFu) << 16);
+    }
+    static DEV int lrPack(int t, int prm, int ut, int tx, int ty) { return t | (prm & 15) << 4 | ut << 8 | tx << 12 | ty << 20; }
+    // the headers and the entries of the slots in use; slots >= nu are empty (this cycle's new units land there)
+    DEV void lrLoad() {
+        const int32_t* gm = st() + P.bot_off;
+        const int PW = botPlayerWords(CAP);
+        if (lid() < 2 * BOT_HDR) lrMem[(lid() / BOT_HDR) * PW + lid() % BOT_HDR] = (uint32_t)gm[(lid() / BOT_HDR) * PW + lid() % BOT_HDR];
+        for (int p = 0; p < 2; p++) {
+            for (int a = 0; a < BA_ARRAYS; a++)
+                for (int i = lid(); i < nu; i += 64) lrArr(p, a)[i] = (uint32_t)gm[p * PW + BOT_HDR + a * CAP + i];
+            // all three words: lrCompact and lrStore copy a new unit's entry whole, so no LDS leftovers may sit
+            // in it (a checkpoint's bytes are a function of the games played)
+            for (int a = 0; a < BA_ARRAYS; a++)
+                for (int i = nu + lid(); i < CAP; i += 64) lrArr(p, a)[i] = 0u;
+        }
+        wsync();
+    }
+    DEV void lrStore() {
+        int32_t* gm = st() + P.bot_off;
+        const int PW = botPlayerWords(CAP);
+        if (lid() < 2 * BOT_HDR) gm[(lid() / BOT_HDR) * PW + lid() % BOT_HDR] = (int32_t)lrMem[(lid() / BOT_HDR) * PW + lid() % BOT_HDR];
+        for (int p = 0; p < 2; p++)
+            for (int a = 0; a < BA_ARRAYS; a++)
+                for (int i = lid(); i < nu; i += 64) gm[p * PW + BOT_HDR + a * CAP + i] = (int32_t)lrArr(p, a)[i];
+    }
+    DEV void lrClear() {  // AbstractionLayerAI.reset (AbstractionLayerAI.java:53-55) of both sides
+        for (int i = lid(); i < botWords(CAP); i += 64) lrMem[i] = 0u;
+        wsync();
+    }
+    // Before compact(): entries follow their units to the compacted slots, entries of removed units go (Java
+    // deletes them at the next translateActions, AbstractionLayerAI.java:69-71, and nothing reads them before),
+    // references are renumbered.  Units born this cycle sit in slots that held no entry.
+    DEV void lrCompact() {
+        uint16_t* map = lrOrd;  // old slot -> new slot (free between the issue and the next getAction)
+        int base = 0;
+        for (int o0 = 0; o0 < nu; o0 += 64) {
+            const int o = o0 + lid();
+            const bool alive = o < nu && !(uc[o] & UC_DEAD);
+            const uint64_t m = ballot(alive);
+            if (o < nu) map[o] = alive ? (uint16_t)(base + lanes_below(m)) : (uint16_t)BR_DEAD;
+            base += __popcll(m);
+        }
+        wsync();
+        for (int p = 0; p < 2; p++) {
+            uint32_t *A = lrArr(p, BA_ACT), *B = lrArr(p, BA_REF), *R = lrArr(p, BA_RANK);
+            for (int o0 = 0; o0 < nu; o0 += 64) {
+                const int o = o0 + lid();
+                const bool alive = o < nu && !(uc[o] & UC_DEAD);
+                uint32_t a = 0, b = 0, r = 0;
+                if (alive) {
+                    a = A[o];
+                    b = B[o];
+                    r = R[o];
+                }
+                wsync();
+                if (alive) {
+                    uint32_t lo = b & 0xFFFFu, hi = b >> 16;
+                    if (lo < (uint32_t)nu) lo = map[lo];
+                    if (hi < (uint32_t)nu) hi = map[hi];
+                    const int idx = map[o];
+                    A[idx] = a;
+                    B[idx] = lo | (hi << 16);
+                    R[idx] = r;
+                }
+                wsync();
+            }
+            for (int o = base + lid(); o < nu; o += 64) A[o] = 0u;
+        }
+        wsync();
+    }
+    // the first unit in list order at the smallest Manhattan distance from (x, y) (strict `<` in the Java loops):
+    // mode 0 an enemy of p (LightRush.java:142-154, Train.java:113-121), 1 a resource (LightRush.java:210-218,
+    // Train.java:103-111), 2 a stockpile of p (LightRush.java:220-228).  -1 = none.
+    DEV int lrClosest(int x, int y, int p, int mode) const {
+        int best = INF;
+        for (int o = lid(); o < nu; o += 64) {
+            const uint32_t c = uc[o];
+            const int pl = uplay(c);
+            const uint32_t fl = U.flags[utyp(c)];
+            const bool ok = mode == 0 ? (pl >= 0 && pl != p) : mode == 1 ? (fl & F_RESOURCE) != 0 : ((fl & F_STOCKPILE) != 0 && pl == p);
+            if (ok && !(c & UC_DEAD)) best = min(best, ((abs(ux(c) - x) + abs(uy(c) - y)) << 16) | o);
+        }
+        best = wave_min(best);
+        return best == INF ? -1 : (best & 0xFFFF);
+    }
+    DEV int lrCount(int p, int typ, uint32_t flag) const {  // p's units of type typ (flag = 0) or with a type flag
+        int n = 0;
+        for (int o0 = 0; o0 < nu; o0 += 64) {
+            const int o = o0 + lid();
+            bool is = false;
+            if (o < nu) {
+                const uint32_t c = uc[o];
+                is = !(c & UC_DEAD) && uplay(c) == p && (flag ? (U.flags[utyp(c)] & flag) != 0 : utyp(c) == typ);
+            }
+            n += __popcll(ballot(is));
+        }
+        return n;
+    }
+    // actions.put(u, aa) (AbstractionLayerAI.java:119-137): a present key keeps its place in the LinkedHashMap
+    DEV void lrPut(int p, int s, uint32_t act, uint32_t ref) {
+        if (lid() == 0) {
+            if ((lrArr(p, BA_ACT)[s] & 7u) == BK_NONE) lrArr(p, BA_RANK)[s] = lrHdr(p)[0]++;
+            lrArr(p, BA_ACT)[s] = act;
+            lrArr(p, BA_REF)[s] = ref;
+        }
+        wsync();
+    }
+    DEV bool lrBit(const uint32_t* b, int i) const { return (uniu(b[i >> 5]) >> (i & 31)) & 1u; }
+    DEV void lrSetBit(uint32_t* b, int i) {
+        if (lid() == 0) b[i >> 5] |= 1u << (i & 31);
+        wsync();
+    }
+    // gs.getResourceUsage() (rts/GameState.java:652-664) and the cells where gs.free(x, y) is false
+    // (rts/GameState.java:191-207: terrain, a unit, or the target of a pending MOVE / PRODUCE).  The other side's
+    // parked actions are not assignments yet (both getActions precede either issue), only UA_PRESENT counts.
+    DEV void lrGameUsage() {
+        const int NB2 = (HW + 2 * W + 31) / 32;
+        for (int i = lid(); i < NB2; i += 64) lrGs[i] = 0u;
+        for (int i = lid(); i < maskWords(HW); i += 64) lrFree[i] = 0u;
+        wsync();
+        int s0 = 0, s1 = 0;
+        for (int o = lid(); o < nu; o += 64) {
+            const uint32_t c = uc[o], a = ua[o];
+            const int t = ua_type(a);
+            if (!(c & UC_DEAD) && (a & UA_PRESENT) && (t == T_MOVE || t == T_PRODUCE)) {
+                const int d = par[o], nx = ux(c) + dxo(d), ny = uy(c) + dyo(d);
+                const int pos = ny * W + nx + W;
+                atomicOr(&lrGs[pos >> 5], 1u << (pos & 31));
+                if (inb(nx, ny)) atomicOr(&lrFree[(ny * W + nx) >> 5], 1u << ((ny * W + nx) & 31));
+                if (t == T_PRODUCE) {
+                    if (uplay(c) == 0) s0 += U.cost[ua_ut(a)];
+                    else s1 += U.cost[ua_ut(a)];
+                }
+            }
+        }
+        for (int c = lid(); c < HW; c += 64)
+            if (cell[c] != EMPTY) atomicOr(&lrFree[c >> 5], 1u << (c & 31));
+        lrRes0 = wave_sum(s0);
+        lrRes1 = wave_sum(s1);
+        wsync();
+    }
+    // gs.isUnitActionAllowed(u, ua) (rts/GameState.java:434-457) of a MOVE or PRODUCE in direction d
+    DEV bool lrAllowed(int s, int t, int d, int ut) const {
+        const uint32_t c = uniu(uc[s]);
+        const int nx = ux(c) + dxo(d), ny = uy(c) + dyo(d);
+        if (t == T_MOVE && (!inb(nx, ny) || uni(cell[ny * W + nx]) != EMPTY)) return false;
+        if (lrBit(lrGs, ny * W + nx + W)) return false;
+        const int cost = t == T_PRODUCE ? U.cost[ut] : 0, pl = uplay(c);
+        // ResourceUsage.consistentWith (rts/ResourceUsage.java:31-50) with the game's usage as `anotherUsage`
+        if (lrRes0 != 0 && lrRes0 + (pl == 0 ? cost : 0) > 0 && lrRes0 + (pl == 0 ? cost : 0) > pres0) return false;
+        if (lrRes1 != 0 && lrRes1 + (pl == 1 ? cost : 0) > 0 && lrRes1 + (pl == 1 ? cost : 0) > pres1) return false;
+        return true;
+    }
+    // AStarPathFinding.findPathToPositionInRange (AStarPathFinding.java:52-79) over runAStar
+    // (AStarPathFinding.java:175-295): the direction of the first step, or -1 for Java's null (no path, or the
+    // start cell already within range).  The Java keeps `open` sorted by descending heuristic + cost, pops from
+    // its end and inserts a new element just above the last one whose f is >= its own (addToOpen,
+    // AStarPathFinding.java:104-138): the pop is the smallest f, the most recently inserted among equals.  A
+    // cell is inserted at most once (inOpenOrClosed), so an insertion number identifies it; the open list here
+    // is unsorted — key[n] = f << 12 | (4095 - n), popped = INF — and a pop is the minimum key over the lanes.
+    // H * W <= LR_MAX_CELLS: n < 1024, f < 64 + 1024.  (tx, ty) may lie off the map (Build at x = -1): it is
+    // only ever compared with, never read.
+    DEV int lrAStar(int s, int tx, int ty, int range) {
+        MPHASE(27);  // (timing build: 25 behaviours, 26 A*, 27 the rest of translateActions, 28 the issue)
+        const int d = lrAStarRun(s, tx, ty, range);
+        MPHASE(26);
+        return d;
+    }
+    DEV int lrAStarRun(int s, int tx, int ty, int range) {
+        const uint32_t cu = uniu(uc[s]);
+        const int sx = ux(cu), sy = uy(cu), start = sy * W + sx;
+        for (int c = lid(); c < HW; c += 64) lrPar[c] = 0xFFFFu;
+        wsync();
+        if (lid() == 0) {
+            lrCell[0] = (uint16_t)start;
+            lrKey[0] = ((uint32_t)(abs(sx - tx) + abs(sy - ty)) << 12) | 4095u;
+            lrPar[start] = (uint16_t)start;
+            lrCost[start] = 0;
+        }
+        wsync();
+        int n = 1, goal = -1;
+        for (;;) {
+            int best = INF;
+            for (int i = lid(); i < n; i += 64) best = min(best, (int)lrKey[i]);
+            best = wave_min(best);
+            if (best == INF) return -1;  // open list empty: no path
+            const int idx = 4095 - (best & 4095);
+            const int pos = uni(lrCell[idx]);
+            const int x = pos % W, y = pos / W;
+            if ((x - tx) * (x - tx) + (y - ty) * (y - ty) <= range * range) {
+                goal = pos;
+                break;
+            }
+            // the four neighbours in the order up, right, down, left (lanes 0..3): distinct cells, so their
+            // tests are independent and their insertion numbers follow the lane order
+            const int d = lid();
+            bool ok = false;
+            int c2 = 0, h2 = 0;
+            if (d < 4) {
+                const int nx = x + dxo(d), ny = y + dyo(d);
+                if (inb(nx, ny)) {
+                    c2 = ny * W + nx;
+                    h2 = abs(nx - tx) + abs(ny - ty);
+                    ok = lrPar[c2] == 0xFFFFu && !((lrFree[c2 >> 5] >> (c2 & 31)) & 1u) &&
+                         !((lrRu[(c2 + W) >> 5] >> ((c2 + W) & 31)) & 1u);
+                }
+            }
+            const uint64_t m = ballot(ok);
+            const int gc = uni(lrCost[pos]) + 1;
+            if (d == 0) lrKey[idx] = (uint32_t)INF;
+            if (ok) {
+                const int k = n + lanes_below(m);
+                lrCost[c2] = (uint16_t)gc;
+                lrPar[c2] = (uint16_t)pos;
+                lrCell[k] = (uint16_t)c2;
+                lrKey[k] = ((uint32_t)(h2 + gc) << 12) | (uint32_t)(4095 - k);
+            }
+            n += __popcll(m);
+            wsync();
+        }
+        // the first step: walk the parents back from the goal (AStarPathFinding.java:60-78)
+        int pos = goal, last = goal;
+        for (;;) {
+            const int par2 = uni(lrPar[pos]);
+            if (par2 == pos) break;
+            last = pos;
+            pos = par2;
+        }
+        if (last == pos + W) return 2;
+        if (last == pos - 1) return 3;
+        if (last == pos - W) return 0;
+        if (last == pos + 1) return 1;
+        return -1;  // already there
+    }
+    // Train.score (Train.java:98-127): minus the distance to the closest resource (a harvester) or enemy
+    DEV int lrScore(int x, int y, int ut, int p) const {
+        const int o = lrClosest(x, y, p, (U.flags[ut] & F_HARVEST) ? 1 : 0);
+        if (o < 0) return 0;
+        const uint32_t c = uniu(uc[o]);
+        return -(abs(ux(c) - x) + abs(uy(c) - y));
+    }
+    // the direction from (x, y) to the adjacent cell (ax, ay), -1 if it is not adjacent
+    static DEV int lrAdjacent(int x, int y, int ax, int ay) {
+        int d = -1;
+        if (ax == x && ay == y - 1) d = 0;
+        if (ax == x + 1 && ay == y) d = 1;
+        if (ax == x && ay == y + 1) d = 2;
+        if (ax == x - 1 && ay == y) d = 3;
+        return d;
+    }
+    // aa.execute(gs, ru): the UnitAction as lrPack, or -1 for null
+    DEV int lrExecute(int p, int s, uint32_t act, uint32_t ref) {
+        const uint32_t cu = uniu(uc[s]);
+        const int x = ux(cu), y = uy(cu), typ = utyp(cu);
+        const int kind = (int)(act & 7u), ut = (int)((act >> 4) & 15u);
+        if (kind == BK_TRAIN) {  // Train.execute (Train.java:48-96)
+            int bestD = -1, bestS = -1;
+            for (int d = 0; d < 4; d++) {
+                const int nx = x + dxo(d), ny = y + dyo(d);
+                if (!inb(nx, ny) || lrBit(lrFree, ny * W + nx)) continue;
+                const int sc = lrScore(nx, ny, ut, p);
+                if (sc > bestS || bestD == -1) {
+                    bestS = sc;
+                    bestD = d;
+                }
+            }
+            if (lid() == 0) lrArr(p, BA_ACT)[s] = act | 8u;  // completed = true, action or not
+            wsync();
+            if (bestD != -1 && lrAllowed(s, T_PRODUCE, bestD, ut)) return lrPack(T_PRODUCE, bestD, ut, 0, 0);
+            return -1;
+        }
+        if (kind == BK_BUILD) {  // Build.execute (Build.java:54-78)
+            const int bx = (int)((act >> 8) & 0xFFu) - 1, by = (int)((act >> 16) & 0xFFu);
+            const int mv = lrAStar(s, bx, by, 1);
+            if (mv >= 0) return lrAllowed(s, T_MOVE, mv, 0) ? lrPack(T_MOVE, mv, 0, 0, 0) : -1;
+            const int d = lrAdjacent(x, y, bx, by);
+            if (d >= 0 && lrAllowed(s, T_PRODUCE, d, ut)) return lrPack(T_PRODUCE, d, ut, 0, 0);
+            return -1;
+        }
+        if (kind == BK_HARVEST) {  // Harvest.execute (Harvest.java:72-114)
+            const bool carrying = uni(res[s]) != 0;
+            const uint32_t r = carrying ? (ref >> 16) : (ref & 0xFFFFu);
+            if (r >= BR_DEAD) return -1;  // target / base == null
+            const uint32_t tc = uniu(uc[r]);
+            const int mv = lrAStar(s, ux(tc), uy(tc), 1);
+            if (mv >= 0) return lrAllowed(s, T_MOVE, mv, 0) ? lrPack(T_MOVE, mv, 0, 0, 0) : -1;
+            const int d = lrAdjacent(x, y, ux(tc), uy(tc));
+            return d >= 0 ? lrPack(carrying ? T_RETURN : T_HARVEST, d, 0, 0, 0) : -1;
+        }
+        if (kind == BK_ATTACK) {  // Attack.execute (Attack.java:51-65)
+            const uint32_t r = ref & 0xFFFFu;
+            if (r >= BR_DEAD) return -1;
+            const uint32_t tc = uniu(uc[r]);
+            const int dx = ux(tc) - x, dy = uy(tc) - y, rg = U.range[typ];
+            // Math.sqrt(dx * dx + dy * dy) <= attackRange: the integer test (sqrt is monotone, sqrt(r * r) = r exactly)
+            if (dx * dx + dy * dy <= rg * rg) return lrPack(T_ATTACK, -1, 0, ux(tc), uy(tc));
+            const int mv = lrAStar(s, ux(tc), uy(tc), rg);
+            return (mv >= 0 && lrAllowed(s, T_MOVE, mv, 0)) ? lrPack(T_MOVE, mv, 0, 0, 0) : -1;
+        }
+        return -1;
+    }
+    // aa.completed(gs): Train.java:29-31, Build.java:33-37, Harvest.java:42-48, Attack.java:30-33
+    DEV bool lrCompleted(int s, uint32_t act, uint32_t ref) const {
+        switch (act & 7u) {
+            case BK_TRAIN: return (act & 8u) != 0;
+            case BK_BUILD: {
+                const int bx = (int)((act >> 8) & 0xFFu) - 1, by = (int)((act >> 16) & 0xFFu);
+                return inb(bx, by) && uni(cell[by * W + bx]) < CAP;  // getUnitAt(x, y) != null
+            }
+            case BK_HARVEST: return (uni(res[s]) > 0 ? (ref >> 16) : (ref & 0xFFFFu)) >= BR_DEAD;
+            case BK_ATTACK: return (ref & 0xFFFFu) >= BR_DEAD;
+        }
+        return true;
+    }
+    // AbstractionLayerAI.findBuildingPosition (AbstractionLayerAI.java:143-229): rings l = 1.., sides up, right,
+    // down, left, on pgs.getAllFree() (rts/PhysicalGameState.java:512-525: terrain and units only), skipping
+    // the reserved positions; -1 when nothing is free.  Serial on purpose (one uniform LDS read per candidate cell):
+    // it runs only when a Build is newly placed — at most twice per getAction, a handful of times per game — and
+    // the first ring almost always holds a free cell; the order of the scan is the result, so lanes would have to
+    // ballot per ring side to keep it.  Worst case (a full map) is about 4 * max(H, W)^2 reads.
+    DEV int lrBuildingPosition(int r0, int r1, int dx0, int dy0) const {
+        const int L = max(H, W);
+        for (int l = 1; l < L; l++)
+            for (int side = 0; side < 4; side++) {
+                const bool horiz = !(side & 1);
+                const int fixed = side == 0 ? dy0 - l : side == 1 ? dx0 + l : side == 2 ? dy0 + l : dx0 - l;
+                if (fixed < 0 || fixed >= (horiz ? H : W)) continue;
+                for (int k = -l; k <= l; k++) {
+                    const int x = horiz ? dx0 + k : fixed, y = horiz ? fixed : dy0 + k;
+                    if (!inb(x, y)) continue;
+                    const int pos = x + y * W;
+                    if (pos != r0 && pos != r1 && uni(cell[pos]) == EMPTY) return pos;
+                }
+            }
+        return -1;
+    }
+    // AbstractionLayerAI.buildIfNotAlreadyBuilding (AbstractionLayerAI.java:231-245): only the held action's class
+    // and type are compared.  build(u, type, pos % W, pos / W) with Java's % and / : -1 gives x = -1, y = 0.
+    DEV void lrBuild(int p, int s, int ut, int& r0, int& r1) {
+        const uint32_t act = uniu(lrArr(p, BA_ACT)[s]);
+        if ((act & 7u) == BK_BUILD && (int)((act >> 4) & 15u) == ut) return;
+        const uint32_t cu = uniu(uc[s]);
+        const int pos = lrBuildingPosition(r0, r1, ux(cu), uy(cu));
+        lrPut(p, s, lrAct(BK_BUILD, ut, pos < 0 ? -1 : pos % W, pos < 0 ? 0 : pos / W), BR_NULL | (BR_NULL << 16));
+        if (r0 == -2) r0 = pos;
+        else r1 = pos;
+    }
+    // LightRush.meleeUnitBehavior (LightRush.java:142-159)
+    DEV void lrMelee(int p, int s) {
+        const uint32_t cu = uniu(uc[s]);
+        const int e = lrClosest(ux(cu), uy(cu), p, 0);
+        if (e >= 0) lrPut(p, s, lrAct(BK_ATTACK, 0, -1, 0), (uint32_t)e | (BR_NULL << 16));
+    }
+    // LightRush.getAction (LightRush.java:77-121) of player p: the parked actions (UA_PA) and their order (lrOrd,
+    // hdr [1]) are the PlayerAction before its fillWithNones; lrIssue issues it.
+    DEV void lightRush(int p) {
+        const int tBase = lrType(0), tBarracks = lrType(1), tWorker = lrType(2), tLight = lrType(3);
+        const int have = pres(p);
+        MPHASE(2);
+        lrGameUsage();
+        // bases, barracks, melee units: idle ones, in list order (LightRush.java:83-107)
+        const bool trainWorker = lrCount(p, tWorker, 0) < 1 && have >= U.cost[tWorker];  // baseBehavior (LightRush.java:123-134)
+        const bool trainLight = have >= U.cost[tLight];                                  // barracksBehavior (LightRush.java:136-140)
+        for (int pass = 0; pass < 3; pass++)
+            for (int o0 = 0; o0 < nu; o0 += 64) {
+                const int o = o0 + lid();
+                bool is = false;
+                if (o < nu) {
+                    const uint32_t c = uc[o];
+                    const uint32_t fl = U.flags[utyp(c)];
+                    is = !(c & UC_DEAD) && uplay(c) == p && !(ua[o] & UA_PRESENT) &&
+                         (pass == 0 ? utyp(c) == tBase : pass == 1 ? utyp(c) == tBarracks : ((fl & F_ATTACK) && !(fl & F_HARVEST)));
+                }
+                for (uint64_t m = ballot(is); m; m &= m - 1) {
+                    const int s = o0 + __builtin_ctzll(m);
+                    if (pass == 0) {
+                        if (trainWorker) lrPut(p, s, lrAct(BK_TRAIN, tWorker, -1, 0), BR_NULL | (BR_NULL << 16));
+                    } else if (pass == 1) {
+                        if (trainLight) lrPut(p, s, lrAct(BK_TRAIN, tLight, -1, 0), BR_NULL | (BR_NULL << 16));
+                    } else {
+                        lrMelee(p, s);
+                    }
+                }
+            }
+        // workersBehavior (LightRush.java:161-258) over every worker of p, idle or not
+        const int nWorkers = lrCount(p, 0, F_HARVEST);
+        if (nWorkers > 0) {
+            int used = 0, wBase = -1, wBarracks = -1;  // the worker-list index that builds a base / a barracks
+            if (lrCount(p, tBase, 0) == 0 && have >= U.cost[tBase] + used) {
+                wBase = 0;
+                used += U.cost[tBase];
+            }
+            if (lrCount(p, tBarracks, 0) == 0 && have >= U.cost[tBarracks] + used && nWorkers > wBase + 1) {
+                wBarracks = wBase + 1;
+                used += U.cost[tBarracks];
+            }
+            int r0 = -2, r1 = -2, wi = 0, nFree = 0;  // reservedPositions; stillFreeWorkers go to lrOrd
+            uint16_t* stillFree = lrOrd + p * CAP;
+            for (int o0 = 0; o0 < nu; o0 += 64) {
+                const int o = o0 + lid();
+                bool is = false;
+                if (o < nu) {
+                    const uint32_t c = uc[o];
+                    is = !(c & UC_DEAD) && uplay(c) == p && (U.flags[utyp(c)] & F_HARVEST);
+                }
+                for (uint64_t m = ballot(is); m; m &= m - 1, wi++) {
+                    const int s = o0 + __builtin_ctzll(m);
+                    if (wi == wBase) {
+                        lrBuild(p, s, tBase, r0, r1);
+                        continue;
+                    }
+                    if (wi == wBarracks) {
+                        lrBuild(p, s, tBarracks, r0, r1);
+                        continue;
+                    }
+                    const uint32_t cu = uniu(uc[s]);
+                    const int rsrc = lrClosest(ux(cu), uy(cu), p, 1), home = lrClosest(ux(cu), uy(cu), p, 2);
+                    const uint32_t act = uniu(lrArr(p, BA_ACT)[s]), ref = uniu(lrArr(p, BA_REF)[s]);
+                    const bool isH = (act & 7u) == BK_HARVEST;
+                    bool free = true;
+                    if (uni(res[s]) > 0) {
+                        if (home >= 0) {  // harvest(u, null, closestBase) unless it already returns to that base
+                            if (!isH || (ref >> 16) != (uint32_t)home)
+                                lrPut(p, s, lrAct(BK_HARVEST, 0, -1, 0), BR_NULL | ((uint32_t)home << 16));
+                            free = false;
+                        }
+                    } else if (rsrc >= 0 && home >= 0) {
+                        if (!isH || (ref & 0xFFFFu) != (uint32_t)rsrc || (ref >> 16) != (uint32_t)home)
+                            lrPut(p, s, lrAct(BK_HARVEST, 0, -1, 0), (uint32_t)rsrc | ((uint32_t)home << 16));
+                        free = false;
+                    }
+                    if (free) {
+                        if (lid() == 0) stillFree[nFree] = (uint16_t)s;
+                        nFree++;
+                    }
+                }
+            }
+            wsync();
+            for (int i = 0; i < nFree; i++) lrMelee(p, uni(stillFree[i]));
+        }
+        MPHASE(25);
+        lrTranslate(p);
+        MPHASE(27);
+    }
+    // AbstractionLayerAI.translateActions (AbstractionLayerAI.java:58-113)
+    DEV void lrTranslate(int p) {
+        const int NB2 = (HW + 2 * W + 31) / 32;
+        uint32_t *A = lrArr(p, BA_ACT), *B = lrArr(p, BA_REF), *R = lrArr(p, BA_RANK);
+        uint16_t* ord = lrOrd + p * CAP;
+        for (int i = lid(); i < NB2; i += 64) {
+            lrRu[i] = 0u;
+            lrPa[i] = lrGs[i];
+        }
+        wsync();
+        int nd = 0, last = -1;
+        for (;;) {  // the entries in insertion order
+            int best = INF;
+            for (int s = lid(); s < nu; s += 64)
+                if ((A[s] & 7u) != BK_NONE && (int)R[s] > last) best = min(best, (int)R[s]);
+            best = wave_min(best);
+            if (best == INF) break;
+            int sl = INF;
+            for (int s = lid(); s < nu; s += 64)
+                if ((A[s] & 7u) != BK_NONE && (int)R[s] == best) sl = s;
+            sl = wave_min(sl);
+            last = best;
+            const uint32_t act = uniu(A[sl]), ref = uniu(B[sl]);
+            if (lrCompleted(sl, act, ref)) {  // toDelete (removal after the loop: nothing in it reads the map)
+                if (lid() == 0) A[sl] = BK_NONE;
+                wsync();
+                continue;
+            }
+            if (uniu(ua[sl]) & UA_PRESENT) continue;
+            const int r = lrExecute(p, sl, act, ref);
+            if (r < 0) continue;
+            const int t = r & 15, prm = (r >> 4) & 15;
+            if (lid() == 0) {  // the desire, parked without UA_PA until it is accepted
+                ua[sl] = pack_ua(t, (r >> 8) & 15, (r >> 12) & 0xFF, (r >> 20) & 0xFF);
+                par[sl] = (int16_t)(t == T_ATTACK ? -1 : prm);
+                ord[nd] = (uint16_t)sl;
+            }
+            nd++;
+            wsync();
+            if (t == T_MOVE || t == T_PRODUCE) {  // ru.merge(ua.resourceUsage(...)): A* treats these cells as blocked
+                const uint32_t cu = uniu(uc[sl]);
+                lrSetBit(lrRu, (uy(cu) + dyo(prm)) * W + ux(cu) + dxo(prm) + W);
+            }
+        }
+        // the desires consistent with gs.getResourceUsage() and the ones accepted before them
+        // (AbstractionLayerAI.java:101-109, ResourceUsage.consistentWith with the desire as `anotherUsage`)
+        int run = p == 0 ? lrRes0 : lrRes1, na = 0;
+        for (int i = 0; i < nd; i++) {
+            const int sl = uni(ord[i]);
+            const uint32_t a = uniu(ua[sl]), cu = uniu(uc[sl]);
+            const int t = ua_type(a), prm = uni(par[sl]);
+            const bool mp = t == T_MOVE || t == T_PRODUCE;
+            const int pos = (uy(cu) + dyo(prm)) * W + ux(cu) + dxo(prm) + W;
+            const int cost = t == T_PRODUCE ? U.cost[ua_ut(a)] : 0;
+            bool ok = !(mp && lrBit(lrPa, pos));
+            if (cost != 0 && run + cost > 0 && run + cost > pres(p)) ok = false;
+            if (!ok) continue;
+            if (lid() == 0) {
+                ua[sl] = a | UA_PA;
+                ord[na] = (uint16_t)sl;
+            }
+            if (mp) lrSetBit(lrPa, pos);
+            run += cost;
+            na++;
+            wsync();
+        }
+        if (lid() == 0) lrHdr(p)[1] = (uint32_t)na;
+        wsync();
+    }
+    // issueSafe of the PlayerAction: the accepted desires in their order, then fillWithNones(gs, p, 10) in list
+    // order (AbstractionLayerAI.java:111)
+    DEV void lrIssue(int p) {
+        MPHASE(3);
+        curP = p;
+        const int n = (int)uniu(lrHdr(p)[1]);
+        for (int b = 0; b < n; b += 64) {
+            const int i = b + lid();
+            const bool act = i < n;
+            issuePA(act ? (int)lrOrd[p * CAP + i] : 0, act, lid(), min(64, n - b));
+        }
+        issueFills(p, 10);
+        MPHASE(28);
+    }
 #undef D
 };
 
 // PassiveAI.getAction = fillWithNones(gs, p, 10) (ai/PassiveAI.java:41-45): nothing to park, the
-// list-order fill in issuePlayer does it; RandomBiasedAI parks its actions.
+// list-order fill in issuePlayer does it; RandomBiasedAI and LightRush park their actions.
+// LR: the instance can hold a LightRush game (the generic step kernel).
+template <bool LR = false>
 DEV void aiGetAction(Game& G, int kind, int p) {
     if (kind == GK_RANDOM_BIASED) G.randomBiased(p);
+    if (LR && MRTS_UNLIKELY(kind == GK_LIGHT_RUSH)) G.lightRush(p);
+}
+template <bool LR = false>
+DEV void aiIssue(Game& G, int kind, int p) {
+    if (LR && MRTS_UNLIKELY(kind == GK_LIGHT_RUSH)) G.lrIssue(p);
+    else G.issuePlayer(p, 10, true);
 }
 
 // Specialisations (FIX = map width, square maps): batches of self-play games with grid actions and a
@@ -5147,7 +5725,7 @@ DEV void helperLoopPO(Game& G, uint32_t* hdr, int niter) {
     }
 }
 
-template <int MODE, int FIX, int FCAP = 0, bool FPO = false, bool MULTI = false, bool HELP = false>
+template <int MODE, int FIX, int FCAP = 0, bool FPO = false, bool MULTI = false, bool HELP = false, bool LRI = false>
 // stateArg and PS lead the argument list so that kernarg preloading (-amdgpu-kernarg-preload-count,
 // Makefile) hands them over in SGPRs: the first memory round (state block, unit-type table) issues
 // without waiting for a scalar load of the kernel arguments.  The 16x16 instances (c3: four games per
@@ -5226,6 +5804,19 @@ __global__ __launch_bounds__(HELP ? 128 : 64, (HELP || FIX == 16) ? 4 : 1) void 
     const int kind = FIX ? GT_SELFPLAY : G.hget(H_KIND);
     const int gtype = kind & 15, ai1 = (kind >> 4) & 15, ai2 = (kind >> 8) & 15;
     const bool external = gtype != GT_BOT_VS_BOT;  // bot-only clients return no observation / masks
+    // a game with a native LightRush side: the LRI instances of the generic step / reset kernels, which launchEnv
+    // picks for the handles that have the bot's memory — every other handle runs kernels without the bot's code
+    // (with it inlined behind cold branches, agent-vs-PassiveAI steps measured 1.8 % slower, §5l)
+    constexpr bool LRK = LRI && FIX == 0 && (MODE == MODE_STEP || MODE == MODE_RESET);
+    // (from the game's kind alone, which the state block's header holds: no KStatic load in a game without it —
+    // mrts_create gives every handle with such a game the memory, KStatic.bot_off)
+    const bool lr = LRK && ((gtype == GT_BOT_VS_BOT && (ai1 == GK_LIGHT_RUSH || ai2 == GK_LIGHT_RUSH)) ||
+                            (gtype == GT_AGENT_VS_BOT && ai2 == GK_LIGHT_RUSH));
+    if (MRTS_UNLIKELY(lr)) {
+        G.lrInit(smem + P.bot_lds);
+        if (MODE == MODE_RESET) G.lrClear();  // ai.reset() (JNIBotClient.java:149-167)
+        else G.lrLoad();
+    }
     const int niter = MULTI ? D.n_iter : 1;
 #ifdef MRTS_PHASE_TIMING
     int nu0_ = 0;
@@ -5379,9 +5970,9 @@ __global__ __launch_bounds__(HELP ? 128 : 64, (HELP || FIX == 16) ? 4 : 1) void 
                 G.snapshot(1 - side);
             }
             const int np = G.rowsDecode(side, D.rows + (size_t)slot0 * D.n_rows * 8);
-            aiGetAction(G, ai2, 1 - side);
+            aiGetAction<LRK>(G, ai2, 1 - side);
             G.rowsIssue(side, np, 1);
-            G.issuePlayer(1 - side, 10, true);
+            aiIssue<LRK>(G, ai2, 1 - side);
         } else if (gtype == GT_SELFPLAY) {
             // JNIGridnetClientSelfPlay.gameStep (tests/JNIGridnetClientSelfPlay.java:159-189)
             if (MRTS_LIKELY(G.nu <= 64 && (!G.po || G.snapBothOk()))) {
@@ -5418,15 +6009,15 @@ __global__ __launch_bounds__(HELP ? 128 : 64, (HELP || FIX == 16) ? 4 : 1) void 
                 G.snapshot(1 - side);
             }
             G.decode(side);
-            aiGetAction(G, ai2, 1 - side);
+            aiGetAction<LRK>(G, ai2, 1 - side);
             G.issuePlayer(side, 1, false);
-            G.issuePlayer(1 - side, 10, true);
+            aiIssue<LRK>(G, ai2, 1 - side);
         } else {
             // JNIBotClient.gameStep (tests/JNIBotClient.java:108-135): both AIs on the full state
-            aiGetAction(G, ai1, side);
-            aiGetAction(G, ai2, 1 - side);
-            G.issuePlayer(side, 10, true);
-            G.issuePlayer(1 - side, 10, true);
+            aiGetAction<LRK>(G, ai1, side);
+            aiGetAction<LRK>(G, ai2, 1 - side);
+            aiIssue<LRK>(G, ai1, side);
+            aiIssue<LRK>(G, ai2, 1 - side);
         }
         G.cycle();
         PHASE(4);
@@ -5451,6 +6042,7 @@ __global__ __launch_bounds__(HELP ? 128 : 64, (HELP || FIX == 16) ? 4 : 1) void 
             G.hset(H_STEPS, 0);  // envSteps[i] = 0 (JNIGridnetVecClient.java:229,264-265,285)
             G.resetFromTemplate();
             if (G.po) G.clearSnap();
+            if (MRTS_UNLIKELY(lr)) G.lrClear();  // the auto-reset resets the AIs too (JNIBotClient.java:149-167)
         } else {
             freshObs = false;
         }
@@ -5521,7 +6113,10 @@ __global__ __launch_bounds__(HELP ? 128 : 64, (HELP || FIX == 16) ? 4 : 1) void 
         poPacked = poHelpFlags == 4u;
     }
     PHASE(6);
-    if (MODE == MODE_STEP && !freshObs && G.deaths) G.compact();
+    if (MODE == MODE_STEP && !freshObs && G.deaths) {
+        if (MRTS_UNLIKELY(lr)) G.lrCompact();
+        G.compact();
+    }
     PHASE(7);
     if (HELP && FPO) {  // a packed step's mask records go to the helper (storeRecordsHelp)
         G.recOut = poHelpFlags == 4u ? poHelpHdr + PO_HELP_REC : nullptr;
@@ -5561,6 +6156,7 @@ __global__ __launch_bounds__(HELP ? 128 : 64, (HELP || FIX == 16) ? 4 : 1) void 
 #ifdef MRTS_ABLATE
         if (G.ab(AB_STORE)) G.store();
 #endif
+        if (MRTS_UNLIKELY(lr)) G.lrStore();
     }
     if (rebalance) {  // post this game's final unit count; the launch's LAST wave writes the next placement
         const uint32_t tag = D.fwd_stamp & 0xFFFFu;
@@ -5859,6 +6455,11 @@ hipError_t phaseSpans(unsigned long long* out, int n) {  // [11][n]: starts, end
     return e;
 }
 #endif
+// LDS of the native LightRush after the game's own (Game::lrInit)
+size_t lrLdsBytes(int HW, int W, int CAP) {
+    return 4 * (size_t)botWords(CAP) + 4 * (size_t)HW + 3 * 4 * (size_t)((HW + 2 * W + 31) / 32) + 4 * (size_t)maskWords(HW) +
+           3 * 2 * (size_t)HW + 2 * 2 * (size_t)CAP;
+}
 size_t ldsBytes(int HW, int W, int CAP, int po) {
     return (size_t)UTT_LDS + (size_t)16 * CAP + 4 * (size_t)((HW + 2 * W + 31) / 32) + 4 * 64 + 8 * (size_t)maskWords(HW) + 64 + 128 +
            (po ? 4 * (size_t)HW + 8 * (size_t)(HW / W) * (size_t)((W + 31) / 32) : 0) +
@@ -6205,22 +6806,25 @@ hipError_t launchRenderRecords(const KStatic& hs, const KStatic* ds, const uint3
 
 __global__ __launch_bounds__(256) void k_copy_games(int32_t* __restrict__ dst, const int32_t* __restrict__ src,
                                                     const int32_t* __restrict__ pairs, int n_dst, int n_src,
-                                                    int words, int maskLo, int maskHi) {
+                                                    int words, int src_words, int maskLo, int maskHi) {
     const int d = pairs[2 * blockIdx.x], s = pairs[2 * blockIdx.x + 1];
     if (d < 0 || d >= n_dst || s < 0 || s >= n_src) return;
     int32_t* o = dst + (size_t)d * words;
-    const int32_t* i = src + (size_t)s * words;
+    const int32_t* i = src + (size_t)s * src_words;  // a source with LightRush games: longer blocks, same leading words
     for (int w = threadIdx.x; w < words; w += 256) {
         const bool keep = (w >= H_RNG_CANCEL && w <= H_KIND) || (w >= maskLo && w < maskHi);
         if (!keep) o[w] = w == H_STEPS ? 0 : i[w];
     }
 }
 hipError_t launchCopyGames(int32_t* dst, const int32_t* src, const int32_t* pairs, int n, int n_dst, int n_src,
-                           int CAP, int HW, hipStream_t stream) {
+                           int CAP, int HW, int src_words, hipStream_t stream) {
     if (n <= 0) return hipSuccess;
+    // The destination's stride is stateWords: mrts_copy_games' destination is a forward-model handle (checkCopy), and
+    // mrts_create refuses LightRush there, so its blocks never carry bot memory.  A destination with longer blocks
+    // would need its own stride here (and a decision on what a copied game's bot memory is).
     const int lo = H_WORDS + N_ARRAYS * CAP;
     hipLaunchKernelGGL(k_copy_games, dim3((unsigned)n), dim3(256), 0, stream, dst, src, pairs, n_dst, n_src,
-                       stateWords(CAP, HW), lo, lo + 2 * maskWords(HW));
+                       stateWords(CAP, HW), src_words, lo, lo + 2 * maskWords(HW));
     return hipGetLastError();
 }
 
@@ -6273,15 +6877,16 @@ __global__ __launch_bounds__(64) void k_evaluate(const KStatic* __restrict__ PS,
     if (l == 0) out[blockIdx.x] = v;
 }
 hipError_t launchEvaluate(const KStatic& hs, const KStatic* ds, int maxplayer, float* out, hipStream_t stream) {
-    hipLaunchKernelGGL(k_evaluate, dim3((unsigned)hs.n_games), dim3(64), 0, stream, ds, hs.state,
-                       stateWords(hs.CAP, hs.HW), hs.CAP, maxplayer, out);
+    // the handle's block stride: a handle with a LightRush game has the bot memory after every state block
+    const int words = hs.bot_off ? hs.bot_off + botWords(hs.CAP) : stateWords(hs.CAP, hs.HW);
+    hipLaunchKernelGGL(k_evaluate, dim3((unsigned)hs.n_games), dim3(64), 0, stream, ds, hs.state, words, hs.CAP, maxplayer, out);
     return hipGetLastError();
 }
 
 // e0 / e1 (may be null): timing events the launch records itself (hipExtLaunchKernelGGL: the kernel
 // dispatch's own start / end timestamps — no separate marker packets around it; mrts_set_rollout_events)
 hipError_t launchEnv(int mode, const KStatic& hs, const KStatic* ds, const KDyn& D, hipStream_t stream, hipEvent_t e0, hipEvent_t e1) {
-    const size_t lds = ldsBytes(hs.HW, hs.W, hs.CAP, hs.partial_obs);
+    const size_t lds = hs.bot_off ? (size_t)hs.bot_lds + lrLdsBytes(hs.HW, hs.W, hs.CAP) : ldsBytes(hs.HW, hs.W, hs.CAP, hs.partial_obs);
     dim3 grid((unsigned)hs.n_games), block(64);
     const bool fixable = hs.n_sp_games == hs.n_games && D.rows == nullptr && hs.utt.K == 79 && hs.utt.ntypes == 7 &&
                          hs.utt.maxAttackRadius == 7 && hs.H == hs.W;
@@ -6307,9 +6912,13 @@ hipError_t launchEnv(int mode, const KStatic& hs, const KStatic* ds, const KDyn&
             else if (is(16, 320, false)) LAUNCH((k_env<MODE_STEP, 16, 320, false>), grid, block, lds, stream, D.state, ds, D);
             else if (is(8, 128, false)) LAUNCH((k_env<MODE_STEP, 8, 128, false>), grid, block, lds, stream, D.state, ds, D);
             else if (is(32, 320, true)) LAUNCH((k_env<MODE_STEP, 32, 320, true>), grid, block, lds, stream, D.state, ds, D);
+            else if (hs.bot_off) LAUNCH((k_env<MODE_STEP, 0, 0, false, false, false, true>), grid, block, lds, stream, D.state, ds, D);
             else LAUNCH((k_env<MODE_STEP, 0>), grid, block, lds, stream, D.state, ds, D);
             break;
-        case MODE_RESET: LAUNCH((k_env<MODE_RESET, 0>), grid, block, lds, stream, D.state, ds, D); break;
+        case MODE_RESET:
+            if (hs.bot_off) LAUNCH((k_env<MODE_RESET, 0, 0, false, false, false, true>), grid, block, lds, stream, D.state, ds, D);
+            else LAUNCH((k_env<MODE_RESET, 0>), grid, block, lds, stream, D.state, ds, D);
+            break;
         case MODE_PLAYOUT: LAUNCH((k_env<MODE_PLAYOUT, 0>), grid, block, lds, stream, D.state, ds, D); break;
         case MODE_TRACE: {
             // the specialised 16x16 / 8x8 step instances' dimensions (their games' code with constant
@@ -6340,6 +6949,10 @@ hipError_t prepareLds(size_t bytes) {
     if (e == hipSuccess) e = hipFuncSetAttribute((const void*)k_env<MODE_MASKS, 0>, hipFuncAttributeMaxDynamicSharedMemorySize, (int)bytes);
     if (e == hipSuccess) e = hipFuncSetAttribute((const void*)k_env<MODE_PLAYOUT, 0>, hipFuncAttributeMaxDynamicSharedMemorySize, (int)bytes);
     if (e == hipSuccess) e = hipFuncSetAttribute((const void*)k_env<MODE_TRACE, 0>, hipFuncAttributeMaxDynamicSharedMemorySize, (int)bytes);
+    if (e == hipSuccess)
+        e = hipFuncSetAttribute((const void*)k_env<MODE_STEP, 0, 0, false, false, false, true>, hipFuncAttributeMaxDynamicSharedMemorySize, (int)bytes);
+    if (e == hipSuccess)
+        e = hipFuncSetAttribute((const void*)k_env<MODE_RESET, 0, 0, false, false, false, true>, hipFuncAttributeMaxDynamicSharedMemorySize, (int)bytes);
     return e;
 }
 // Unmasked uniform random policy (BASELINE config c2), uniformRow for every cell of

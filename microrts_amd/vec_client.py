@@ -98,12 +98,15 @@ class Responses:
 
 
 def _bot_kind(ai):
-    name = ai if isinstance(ai, str) else type(ai).__name__
+    name = ai if isinstance(ai, str) else (ai.__name__ if isinstance(ai, type) else type(ai).__name__)
     if name in ("PassiveAI", "passive"):
         return _lib.MRTS_BOT_PASSIVE
     if name in ("RandomBiasedAI", "random_biased"):
         return _lib.MRTS_BOT_RANDOM_BIASED
-    raise NotImplementedError(f"opponent AI {name!r} has no native implementation (only PassiveAI / RandomBiasedAI)")
+    if name in ("LightRush", "lightRushAI", "light_rush"):  # ai.abstraction.LightRush(utt): A* pathfinding
+        return _lib.MRTS_BOT_LIGHT_RUSH
+    raise NotImplementedError(f"opponent AI {name!r} has no native implementation "
+                              "(only PassiveAI / RandomBiasedAI / LightRush)")
 
 
 def _check_rfs(rfs):

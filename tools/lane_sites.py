@@ -67,6 +67,14 @@ WHY = {
                    "sum is each lane's 4-bin total",
     "k_policy_delta": "kernel level, before any divergence: every lane's popc(dirty)",
     "k_lane_audit_probe": "the audit build's negative control (reads lane 40 from a branch only lanes 0-31 take)",
+    "lrClosest": "LightRush: wave_min after the per-lane `for (o = lid() ...)` loop has reconverged; `best` starts at "
+                 "INF on every lane; every caller passes wave-uniform arguments from uniform flow",
+    "lrGameUsage": "LightRush: wave_sum of per-lane cost sums (0 on lanes without a PRODUCE) after the per-lane unit "
+                   "loop; called once at the top of lightRush, in uniform flow",
+    "lrAStarRun": "LightRush: wave_min of every lane's smallest open key (INF where a lane scanned nothing) in the pop "
+               "loop, whose exits (open list empty, goal popped) test wave-uniform values (uni / the reduction)",
+    "lrTranslate": "LightRush: wave_min of per-lane minima (INF elsewhere) over the bot memory in the entry loop; "
+                   "`best == INF` and the `continue`s test wave-uniform values (uniu of LDS words, lrExecute's result)",
     "k_evaluate": "uniform `k < n` loop inside the uniform o0 loop; c / hpv / rv are initialised on every lane "
                   "(UC_DEAD / 0) before the `o < nu` loads",
 }
