@@ -493,6 +493,16 @@ DEV void paintDiskRows(uint32_t* rows, int H, int W, int x, int y, int sr, uint3
     }
 }
 
+// KDyn option tests that the steady instance (`steady`: Game's and k_env's template parameter) knows the answer to:
+// D_HAS a buffer the steady state always has, D_OFF one it never has, D_ON a switch that is on, D_ZERO a value
+// that is 0.  Every other instance reads the field.
+#define D_HAS(f) (steady || D.f != nullptr)
+#define D_OFF(f) (steady ? nullptr : D.f)
+#define D_ON(f) (steady || D.f != 0)
+#define D_ZERO(f) (steady ? 0 : D.f)
+// steady: the game of k_env's STEADY instance (launchEnv's steadyLaunch picks it) — the launch is the fused self-play
+// rollout's steady state, so the option tests such a launch never changes are constants
+template <bool steady>
 struct Game {
 #define D (*Dp)
     const KStatic& P;
@@ -755,7 +765,7 @@ struct Game {
         const uint32_t tw = l < TW ? (uint32_t)terr[l] : 0u;
         const uint32_t pv = (wantPrev && l < PW) ? (uint32_t)arr[N_ARRAYS * CAP + l] : 0u;
         // forwarded action words (speculative: used only if H_FWD, in this same round, matches)
-        const uint32_t fw = D.fwd_read ? (uint32_t)s[stateFwdOff(CAP, HW) + l] : 0u;
+        const uint32_t fw = D_ON(fwd_read) ? (uint32_t)s[stateFwdOff(CAP, HW) + l] : 0u;
         // PO delta: the previous render's record, in the same memory round
         const bool poRec = po && D.obs_delta && D.po_prev && poDeltaShape(H, W);
         const int32_t* pr = poRec ? D.po_prev + (size_t)g * D.po_words : nullptr;
@@ -773,7 +783,7 @@ struct Game {
         lcu = (uint32_t)r[A_UC];
         lua = (uint32_t)r[A_UA];
         lfwd = fw;
-        fwdOn = D.fwd_read && (uint32_t)rl(hv, H_FWD) == D.fwd_stamp - 1u;
+        fwdOn = D_ON(fwd_read) && (uint32_t)rl(hv, H_FWD) == D.fwd_stamp - 1u;
         if (poRec) {
             lkey = (uint32_t)(uint16_t)r[A_HP] | ((uint32_t)(uint16_t)r[A_RES] << 16);
             lsnap = ((uint32_t)prsb >> (8 * (l & 3))) & 0xFFu;
@@ -858,7 +868,7 @@ struct Game {
         // every step; an agent-scope __threadfence would also write back the XCD's L2: 4x slower)
         const bool poRec = po && D.obs_delta && D.po_prev && poDeltaShape(H, W);
         const bool poReload = poRec && !poLds;  // a render that kept no LDS copy: re-read the record
-        if (poReload || (!fwdWritten && !D.uni_actions)) __builtin_amdgcn_fence(__ATOMIC_ACQ_REL, "workgroup");
+        if (poReload || (!fwdWritten && !D_OFF(uni_actions))) __builtin_amdgcn_fence(__ATOMIC_ACQ_REL, "workgroup");
         fwdWritten = false;
         poLds = false;
         hset(H_NU, nu);  // "the loaded unit count" of this iteration (PO delta render)
@@ -976,7 +986,7 @@ struct Game {
 #if MRTS_ISSUE_BOTH
         // both players' rows in one pass when none interacts (issueBothTest); not with the reward counters
         // (issueBatch books them per player)
-        if (useIx && MRTS_LIKELY(!(D.reward_need & RN_COUNTS))) {
+        if (useIx && MRTS_LIKELY(!(D_ZERO(reward_need) & RN_COUNTS))) {
             int s0, s1, mc0, mc1;
             const bool both = issueBothTest(idle && !bad, cu, adec, pr, s0, s1, mc0, mc1);
 #ifdef MRTS_PHASE_TIMING
@@ -1845,7 +1855,7 @@ struct Game {
                 } else {  // older assignment: only the new one is cancelled (:298-317)
                     // p.m_b = NONE mutates pa's own Pair unless a cancel already replaced p: the
                     // TraceEntry (pa.clone() after issueSafe) then records NONE, not the PRODUCE
-                    if (orig && tIn == T_PRODUCE && (D.reward_need & RN_COUNTS) && lid() == 0) {
+                    if (orig && tIn == T_PRODUCE && (D_ZERO(reward_need) & RN_COUNTS) && lid() == 0) {
                         const int pc = prodCategory(U.flags[utIn]);
                         if (pc >= 0) rwc[curP * RC_N + pc] -= 1;
                     }
@@ -1973,7 +1983,7 @@ struct Game {
                         const uint32_t* cuKnown = nullptr, bool* putAny = nullptr, bool posChecked = false) {
         const bool mp = act && (t == T_MOVE || t == T_PRODUCE);
         const bool np = act && t == T_PRODUCE;
-        if (MRTS_UNLIKELY(D.reward_need & RN_COUNTS)) {  // the pairs as the TraceEntry records them (legality applied)
+        if (MRTS_UNLIKELY(D_ZERO(reward_need) & RN_COUNTS)) {  // the pairs as the TraceEntry records them (legality applied)
             const int pc = np ? prodCategory(U.flags[ut]) : -1;
             auto cnt = [](bool b) { return (int)__popcll(ballot(b)); };
             const int c[RC_N] = {cnt(act && t == T_HARVEST), cnt(act && t == T_RETURN), cnt(act && t == T_ATTACK),
@@ -2825,33 +2835,33 @@ struct Game {
     // pgs).  Constants are float 1.
     // it: this launch's iteration (the step's place in the Responses ring, KDyn.resp_reward)
     DEV bool writeRewards(int slot0, int nslots, int pl0, int pl1, bool gameover, int winner, int it = 0) {
-        const int R = D.n_rewards;
+        const int R = steady ? 1 : D.n_rewards;
         int newSq0 = INF, newSq1 = INF;
-        if (MRTS_UNLIKELY(D.reward_need & RN_CLOSER)) closerMin(newSq0, newSq1);
+        if (MRTS_UNLIKELY(D_ZERO(reward_need) & RN_CLOSER)) closerMin(newSq0, newSq1);
         bool resLeft = false;
-        if (D.reward_need & RN_RESOURCES)
+        if (D_ZERO(reward_need) & RN_RESOURCES)
             for (int o0 = 0; o0 < nu; o0 += 64) {
                 const int o = o0 + lid();
                 resLeft |= ballot(o < nu && !(uc[o] & UC_DEAD) && (U.flags[utyp(uc[o])] & N_RESOURCE) && res[o] > 0) != 0;
             }
-        const int k0 = (int)(D.reward_kinds4 & 15u);
+        const int k0 = (int)(D_ZERO(reward_kinds4) & 15u);
         // the Responses ring (mrts_set_step_responses): reward / done point at the call's ring and each
         // iteration writes its own step there (resp_stride = n_slots * n_rewards; 0 = the plain buffers)
-        const size_t ro = (size_t)((uint32_t)it * (uint32_t)D.resp_stride);
+        const size_t ro = (size_t)((uint32_t)it * (uint32_t)D_ZERO(resp_stride));
         const bool done0 = k0 == RF_WINLOSS ? gameover : (k0 == RF_RESOURCE_GATHER ? !resLeft : false);
         const int L = lid();
         if (R == 1 && k0 == RF_WINLOSS) {  // WinLoss alone (the common case): a wave-uniform branch, no switch
             if (L < nslots) {
                 const int p = L ? pl1 : pl0;
-                if (D.reward) D.reward[ro + slot0 + L] = gameover ? (winner == p ? 1.0 : -1.0) : 0.0;
-                if (D.done) D.done[ro + slot0 + L] = gameover ? 1 : 0;
+                if (D_HAS(reward)) D.reward[ro + slot0 + L] = gameover ? (winner == p ? 1.0 : -1.0) : 0.0;
+                if (D_HAS(done)) D.done[ro + slot0 + L] = gameover ? 1 : 0;
             }
             return done0;
         }
-        if (L < nslots * R && (D.reward || D.done)) {
+        if (L < nslots * R && (D_HAS(reward) || D_HAS(done))) {
             const int i = L / R, j = L - i * R;
             const int p = i ? pl1 : pl0;
-            const int kind = (int)((D.reward_kinds4 >> (4 * j)) & 15u);
+            const int kind = (int)((D_ZERO(reward_kinds4) >> (4 * j)) & 15u);
             double r = 0.0;
             bool d = false;
             switch (kind) {
@@ -2873,8 +2883,8 @@ struct Game {
                         r = closerDist(hdr[HX_OLDSQ + p]) - closerDist(p == 0 ? newSq0 : newSq1);
                     break;
             }
-            if (D.reward) D.reward[ro + (size_t)(slot0 + i) * R + j] = r;
-            if (D.done) D.done[ro + (size_t)(slot0 + i) * R + j] = d ? 1 : 0;
+            if (D_HAS(reward)) D.reward[ro + (size_t)(slot0 + i) * R + j] = r;
+            if (D_HAS(done)) D.done[ro + (size_t)(slot0 + i) * R + j] = d ? 1 : 0;
         }
         return done0;
     }
@@ -2952,7 +2962,7 @@ struct Game {
                 st4sc1(rs, off * 4u, w[0], w[1], w[2], w[3]);
             }
         }
-        if (MRTS_UNLIKELY(D.obs8 != nullptr)) {  // the uint8 transport (mrts_set_exchange_bytes): every plane
+        if (MRTS_UNLIKELY(D_OFF(obs8) != nullptr)) {  // the uint8 transport (mrts_set_exchange_bytes): every plane
             if (!firstIt)
 #pragma unroll
                 for (int j = 0; j < 4; j++) v[5][j] = cell[c4 + j] == WALL ? 1 : 0;
@@ -2969,7 +2979,7 @@ struct Game {
                     *(uint32_t*)(b0 + (size_t)(i * D.C + q) * HW + c4) = w;
                 }
         }
-        if (MRTS_UNLIKELY(D.obs16 != nullptr)) {  // the int16 transport copy (mrts_set_obs16): every plane
+        if (MRTS_UNLIKELY(D_OFF(obs16) != nullptr)) {  // the int16 transport copy (mrts_set_obs16): every plane
             if (!firstIt)
 #pragma unroll
                 for (int j = 0; j < 4; j++) v[5][j] = cell[c4 + j] == WALL ? 1 : 0;
@@ -2989,7 +2999,7 @@ struct Game {
         }
     }
     DEV void writeObsFull(int slot0, int nslots, int player0) {
-        if (HW == 256 && !po && D.obs_img && nslots <= 2) {
+        if (HW == 256 && !po && D_ON(obs_img) && nslots <= 2) {
             writeObsFullImg(slot0, nslots, player0);
             return;
         }
@@ -3028,14 +3038,14 @@ struct Game {
                         __builtin_amdgcn_raw_buffer_store_b32(x, rs, (int)(off * 4u), 0, 16);
                     }
                 }
-                if (MRTS_UNLIKELY(D.obs16 != nullptr)) {  // the int16 transport copy (mrts_set_obs16)
+                if (MRTS_UNLIKELY(D_OFF(obs16) != nullptr)) {  // the int16 transport copy (mrts_set_obs16)
                     int16_t* h0 = D.obs16 + (size_t)slot0 * D.C * HW;
                     for (int i = 0; i < nslots; i++)
 #pragma unroll
                         for (int q = 0; q < 6; q++)
                             h0[(size_t)(i * D.C + q) * HW + c] = (int16_t)((i && q == 2 && v[2]) ? 3 - v[2] : v[q]);
                 }
-                if (MRTS_UNLIKELY(D.obs8 != nullptr)) {  // the uint8 transport (mrts_set_exchange_bytes)
+                if (MRTS_UNLIKELY(D_OFF(obs8) != nullptr)) {  // the uint8 transport (mrts_set_exchange_bytes)
                     uint8_t* b0 = D.obs8 + (size_t)slot0 * D.C * HW;
                     for (int i = 0; i < nslots; i++)
 #pragma unroll
@@ -3081,7 +3091,7 @@ struct Game {
                     if (pl >= npl) break;
                     st4sc1(rs, (uint32_t)(pl * HW + c4) * 4u, v[0][pl], v[1][pl], v[2][pl], v[3][pl]);
                 }
-                if (MRTS_UNLIKELY(D.obs16 != nullptr)) {  // the int16 transport copy (mrts_set_obs16)
+                if (MRTS_UNLIKELY(D_OFF(obs16) != nullptr)) {  // the int16 transport copy (mrts_set_obs16)
                     int16_t* h0 = D.obs16 + (size_t)slot0 * D.C * HW;
 #pragma unroll
                     for (int pl = 0; pl < 6; pl++) {
@@ -3121,7 +3131,7 @@ struct Game {
                     obsCell(c, player0 + i, v);
 #pragma unroll
                     for (int pl = 0; pl < 6; pl++) o[(size_t)pl * HW + c] = v[pl];
-                    if (D.obs16) {
+                    if (D_OFF(obs16)) {
                         int16_t* h = D.obs16 + (size_t)(slot0 + i) * D.C * HW;
 #pragma unroll
                         for (int pl = 0; pl < 6; pl++) h[(size_t)pl * HW + c] = (int16_t)v[pl];
@@ -3591,7 +3601,7 @@ struct Game {
             const uint64_t lo = (uint64_t)rb[64 + l] | ((uint64_t)rb[128 + l] << 32);
             const uint32_t w2 = rb[192 + l];
             storeRecord(masks + (size_t)slot * total + (size_t)c * K, lo, w2);
-            if (D.pol_actions && D.pol_delta) {
+            if (D_HAS(pol_actions) && D_ON(pol_delta)) {
                 int32_t a[7];
                 unpackFwd(rb[256 + l], a);
                 int32_t* dst = D.pol_actions + ((size_t)slot * HW + c) * 7;
@@ -3605,7 +3615,7 @@ struct Game {
             const uint32_t ge = gl[l];
             const int slot = slot0 + (int)(ge >> 15), cz = (int)(ge & 0x7FFFu);
             storeRecord(masks + (size_t)slot * total + (size_t)cz * K, 0ull, 0u);
-            if (D.pol_actions && D.pol_delta) {
+            if (D_HAS(pol_actions) && D_ON(pol_delta)) {
                 int32_t* dst = D.pol_actions + ((size_t)slot * HW + cz) * 7;
                 st4u<WT_MASK>(dst, 0, 0, 0, 0);
                 st3u<WT_MASK>(dst + 4, 0, 0, 0);
@@ -4442,7 +4452,7 @@ struct Game {
     DEV void writeMasks(int slot0, int nslots, int pl0, int pl1) {
         const int total = HW * K;
         const int MW = maskWords(HW);
-        const bool delta = D.mask_delta && (total & 15) == 0;
+        const bool delta = D_ON(mask_delta) && (total & 15) == 0;
         uint32_t* pg = prevG();
         const int l = lid();
         if (delta && nu <= 64 && nslots * MW <= 64 && writeMasksUnits(slot0, nslots, pl0, pl1)) return;
@@ -4455,7 +4465,7 @@ struct Game {
                 const int w = c0 >> 5;
                 const uint32_t mine = l == 0 ? (uint32_t)m : (uint32_t)(m >> 32);
                 if (l < 2 && w + l < MW) {
-                    if (D.source) D.source[(size_t)slot * MW + w + l] = mine;
+                    if (D_HAS(source)) D.source[(size_t)slot * MW + w + l] = mine;
                     if (lastIt) pg[p * MW + w + l] = mine;
                 }
                 if (delta) {
@@ -4530,7 +4540,7 @@ struct Game {
         const int total = rl(incl, 63);
         if (total > 64) return false;
         if (l < NW) {
-            if (D.source) D.source[(size_t)(slot0 + i) * MW + w] = cur;
+            if (D_HAS(source)) D.source[(size_t)(slot0 + i) * MW + w] = cur;
             if (lastIt) prevG()[(i ? pl1 : pl0) * MW + w] = cur;  // the next launch's copy
             mprev[(i ? pl1 : pl0) * MW + w] = cur;
         }
@@ -4715,18 +4725,18 @@ struct Game {
             w = l - i * MW;
             cur = nb[l];
             old = mprev[(i ? pl1 : pl0) * MW + w];
-            if (D.source) D.source[(size_t)(slot0 + i) * MW + w] = cur;
+            if (D_HAS(source)) D.source[(size_t)(slot0 + i) * MW + w] = cur;
             if (lastIt) prevG()[(i ? pl1 : pl0) * MW + w] = cur;  // the next launch's copy
             mprev[(i ? pl1 : pl0) * MW + w] = cur;  // the next iteration's base (multi-step launch)
         }
-        const bool pol = D.pol_actions && D.pol_delta;
+        const bool pol = D_HAS(pol_actions) && D_ON(pol_delta);
         // forward the sampled rows of a self-play game (read by selfPlayFast next launch); K - 23 - NT
         // attack slots fit packFwd's 7-bit field
         const bool fwdW = pol && nslots == 2 && K - 23 - NT <= 126;
         const uint8_t* mbase = D.masks + (size_t)slot0 * total;  // this game's records
         const __amdgpu_buffer_rsrc_t mrs = bufRsrc((void*)mbase, (uint32_t)(nslots * total));
         // the kernel's full policy pass (writePolicyAll, no delta base) reads the parked bits
-        if (si >= 0 && D.pol_actions && !(D.pol_delta && D.mask_delta && (total & 15) == 0)) {
+        if (si >= 0 && D_HAS(pol_actions) && !(D_ON(pol_delta) && D_ON(mask_delta) && (total & 15) == 0)) {
             at[l] = (int32_t)w0;
             as[l] = (int32_t)w1;
             ua[l] = w2 & 0xFFFFu;
@@ -4868,7 +4878,7 @@ struct Game {
                 const int j = ((c * K) >> 4) + t;
                 if (j <= ((c * K + K - 1) >> 4))
                     *(uint4*)(D.masks + (size_t)(slot0 + i) * total + 16 * j) = maskChunk(j, i ? pl1 : pl0);
-                if (t == 0 && D.pol_actions && D.pol_delta) policyRow(slot0 + i, c, i ? pl1 : pl0);
+                if (t == 0 && D_HAS(pol_actions) && D_ON(pol_delta)) policyRow(slot0 + i, c, i ? pl1 : pl0);
             }
         }
         wsync();
@@ -5449,13 +5459,13 @@ struct Game {
 // PassiveAI.getAction = fillWithNones(gs, p, 10) (ai/PassiveAI.java:41-45): nothing to park, the
 // list-order fill in issuePlayer does it; RandomBiasedAI and LightRush park their actions.
 // LR: the instance can hold a LightRush game (the generic step kernel).
-template <bool LR = false>
-DEV void aiGetAction(Game& G, int kind, int p) {
+template <bool LR = false, class GameT>
+DEV void aiGetAction(GameT& G, int kind, int p) {
     if (kind == GK_RANDOM_BIASED) G.randomBiased(p);
     if (LR && MRTS_UNLIKELY(kind == GK_LIGHT_RUSH)) G.lightRush(p);
 }
-template <bool LR = false>
-DEV void aiIssue(Game& G, int kind, int p) {
+template <bool LR = false, class GameT>
+DEV void aiIssue(GameT& G, int kind, int p) {
     if (LR && MRTS_UNLIKELY(kind == GK_LIGHT_RUSH)) G.lrIssue(p);
     else G.issuePlayer(p, 10, true);
 }
@@ -5598,6 +5608,12 @@ DEV int simdRankStep(SimdRank& r, uint32_t est) {
 // dispatcher puts the game waves of blocks b and b + n / 2 on one SIMD (round 6 span data,
 // profiles/round6/placement_c5.json); c5 +0.6 %.
 constexpr int BAL_MIN_ITER = 64, BAL_PO_GS = 2;
+// an LDS pointer through an opaque scalar copy of its address: what is derived from it is register + offset
+DEV uint8_t* ldsOpaque(uint8_t* p) {
+    uint32_t a = (uint32_t)(uintptr_t)(__attribute__((address_space(3))) uint8_t*)p;
+    asm volatile("" : "+s"(a));
+    return (uint8_t*)(__attribute__((address_space(3))) uint8_t*)(uintptr_t)a;
+}
 DEV int balancedGame(const KDyn& D) {
     const int n = (int)gridDim.x;
     const int32_t hdr1 = __builtin_nontemporal_load(D.bal + 1);
@@ -5691,7 +5707,8 @@ DEV void drainStores() { __builtin_amdgcn_s_waitcnt(0x0F70); }  // s_waitcnt vmc
 // (writeMasksLanes with recOut: [5][64] words + a count word + 64 u16 vacated cells), stored by the
 // helper after S_k (S_last after the last step), so the game wave issues none of those stores.
 constexpr int PO_HELP_REC = 8 + 2 * 32 + 16, PO_HELP_REC_WORDS = 5 * 64 + 1 + 32;
-DEV void helperLoopPO(Game& G, uint32_t* hdr, int niter) {
+template <class GameT>
+DEV void helperLoopPO(GameT& G, uint32_t* hdr, int niter) {
     uint32_t* const rows0 = hdr + 8;
     uint8_t* const hsnap = (uint8_t*)(rows0 + 2 * G.H);
     uint8_t* const hcell = (uint8_t*)(G.scell + 2 * 5 * 64);
@@ -5725,26 +5742,33 @@ DEV void helperLoopPO(Game& G, uint32_t* hdr, int niter) {
     }
 }
 
-template <int MODE, int FIX, int FCAP = 0, bool FPO = false, bool MULTI = false, bool HELP = false, bool LRI = false>
+template <int MODE, int FIX, int FCAP = 0, bool FPO = false, bool MULTI = false, bool HELP = false, bool LRI = false, bool STEADY = false>
 // stateArg and PS lead the argument list so that kernarg preloading (-amdgpu-kernarg-preload-count,
 // Makefile) hands them over in SGPRs: the first memory round (state block, unit-type table) issues
 // without waiting for a scalar load of the kernel arguments.  The 16x16 instances (c3: four games per
 // SIMD, at the 128-VGPR edge) and the helper instances are held to 4 waves per SIMD: one VGPR more
 // silently halves nothing but drops a quarter of the games into a second dispatch round (1.7x slower).
 __global__ __launch_bounds__(HELP ? 128 : 64, (HELP || FIX == 16) ? 4 : 1) void k_env(int32_t* __restrict__ stateArg, const KStatic* __restrict__ PS, KDyn D) {
-    extern __shared__ __align__(16) uint8_t smem[];
+    extern __shared__ __align__(16) uint8_t smemDyn[];
+    // The steady instance addresses its LDS from an opaque copy of the base: one SGPR, and every array base of Game is
+    // that register plus a constant, which folds into the ds_* offset field where the address is per lane.  From the
+    // symbol itself each base is a constant of its own (`smem + offset`), materialised in an SGPR, hoisted out of the
+    // step loop, spilled to a VGPR lane and read back in front of its uses (128 -> 117 VGPRs, no scratch;
+    // the literal address 0 and a copy made again at every step were worse).
+    uint8_t* const smem = STEADY ? ldsOpaque(smemDyn) : smemDyn;
     if (HELP && !FPO && threadIdx.x >= 64) {
         helperLoop(D, smem, (int)blockIdx.x, D.n_iter);
         return;
     }
     const KStatic& P = *PS;
+    constexpr bool steady = STEADY;  // the D_* option tests below are constants in the steady instance
     // balanced placement (c3's and c5's multi-step kernels): this block's game from the previous launch's permutation
     // (balancePerm: a multiple of 512 games, at most 8 per lane and class)
-    const bool balanced = MULTI && ((FIX == 16 && !FPO) || (FIX == 32 && FPO && HELP)) && D.bal != nullptr &&
+    const bool balanced = MULTI && ((FIX == 16 && !FPO) || (FIX == 32 && FPO && HELP)) && D_HAS(bal) &&
                           (gridDim.x & 511) == 0 && gridDim.x <= 4096;
     const bool rebalance = balanced && D.n_iter >= BAL_MIN_ITER;  // this launch writes the next permutation
     const int game = balanced ? balancedGame(D) : -1;
-    Game G(P, D, stateArg, FIX ? stateWords(FCAP, FIX * FIX) : D.state_words, smem, FIX ? FIX : D.H, FIX ? FIX : D.W, FIX ? FIX * FIX : D.HW, FIX ? FCAP : D.CAP,
+    Game<STEADY> G(P, D, stateArg, FIX ? stateWords(FCAP, FIX * FIX) : D.state_words, smem, FIX ? FIX : D.H, FIX ? FIX : D.W, FIX ? FIX * FIX : D.HW, FIX ? FCAP : D.CAP,
            FIX ? FPO : P.partial_obs != 0, FIX ? 79 : P.utt.K, FIX ? 7 : P.utt.ntypes, FIX ? 7 : P.utt.maxAttackRadius, MULTI, game,
            FIX == 16 || FIX == 32);  // `walk`: the 16x16 instances (round 5) and c5's 32x32 (round 6: c5 +2.8 %)
     // the partially observable helper wave: one packed render per step (helperLoopPO)
@@ -5790,7 +5814,7 @@ __global__ __launch_bounds__(HELP ? 128 : 64, (HELP || FIX == 16) ? 4 : 1) void 
             if (D.done) D.done[(size_t)slot0 * D.n_rewards + k] = 0;
         }
     } else {
-        G.load(D.mask_delta && D.masks);
+        G.load(D_ON(mask_delta) && D_HAS(masks));
 #ifdef MRTS_ABLATE
         if (G.ab(AB_LOAD)) G.load(D.mask_delta && D.masks);
 #endif
@@ -5825,7 +5849,7 @@ __global__ __launch_bounds__(HELP ? 128 : 64, (HELP || FIX == 16) ? 4 : 1) void 
     bool poPacked = false;  // HELP && FPO: the previous iteration handed its render to the helper (packPO, flag 4)
     // c3 (four games per SIMD) only: on c5 the rank measured -4 % (its games outrank their own helper
     // waves, which then reach the handoff barriers late; round 3)
-    const bool ranked = MULTI && FIX == 16 && D.prio_tab != nullptr && niter > 1;
+    const bool ranked = MULTI && FIX == 16 && D_HAS(prio_tab) && niter > 1;
     SimdRank srank;
     if (ranked) srank = simdRankInit(D.prio_tab, D.fwd_stamp);
     if (HELP && !FPO) __syncthreads();  // A_0: the helper drew step 0's rows
@@ -5953,10 +5977,10 @@ __global__ __launch_bounds__(HELP ? 128 : 64, (HELP || FIX == 16) ? 4 : 1) void 
         const size_t rowStride = (size_t)G.HW * 7;
         // fused uniform policy: this step's rows go out first (fire-and-forget stores, nothing in the
         // launch reads them back: fetchRow draws the idle units' rows again)
-        if (D.uni_actions && !(HELP && !FPO)) G.writeUniformRows(slot0, nslots);
-        if (MRTS_UNLIKELY(D.reward_need & RN_COUNTS))
+        if (D_OFF(uni_actions) && !(HELP && !FPO)) G.writeUniformRows(slot0, nslots);
+        if (MRTS_UNLIKELY(D_ZERO(reward_need) & RN_COUNTS))
             if (lane_id() < 2 * RC_N) G.rwc[lane_id()] = 0;
-        if (MRTS_UNLIKELY(D.reward_need & RN_CLOSER)) G.closerBefore();
+        if (MRTS_UNLIKELY(D_ZERO(reward_need) & RN_CLOSER)) G.closerBefore();
         const bool rowsMode = FIX ? false : D.rows != nullptr;
         if (rowsMode && gtype == GT_SELFPLAY) {
             for (int p = 0; p < 2; p++) {
@@ -6036,8 +6060,8 @@ __global__ __launch_bounds__(HELP ? 128 : 64, (HELP || FIX == 16) ? 4 : 1) void 
         G.hset(H_STEPS, steps);
         const bool done0 = G.writeRewards(slot0, nslots, selfplay ? 0 : side, selfplay ? 1 : side, gameover, winner, it);
         const bool reset = done0 || steps >= D.max_steps;
-        if (reset && D.done && lane_id() < nslots)
-            D.done[(size_t)((uint32_t)it * (uint32_t)D.resp_stride) + (size_t)(slot0 + lane_id()) * D.n_rewards] = 1;
+        if (reset && D_HAS(done) && lane_id() < nslots)
+            D.done[(size_t)((uint32_t)it * (uint32_t)D_ZERO(resp_stride)) + (size_t)(slot0 + lane_id()) * (steady ? 1 : D.n_rewards)] = 1;
         if (MRTS_UNLIKELY(reset)) {
             G.hset(H_STEPS, 0);  // envSteps[i] = 0 (JNIGridnetVecClient.java:229,264-265,285)
             G.resetFromTemplate();
@@ -6050,13 +6074,13 @@ __global__ __launch_bounds__(HELP ? 128 : 64, (HELP || FIX == 16) ? 4 : 1) void 
     }
 
     uint32_t poHelpFlags = 0;  // HELP && FPO: bit 2 = the helper renders this step, bit 3 = the game does
-    if (MODE != MODE_MASKS && D.obs && external) {
+    if (MODE != MODE_MASKS && D_HAS(obs) && external) {
         if (G.po) {
             // persistent buffer: the views the previous write rendered for this game can be updated
             // in place (writeObsPO's delta)
             const bool canDelta = MODE == MODE_STEP && !freshObs && D.obs_delta && D.po_prev && poDeltaShape(G.H, G.W) &&
                                   G.nu <= 64 && G.hget(H_NU) <= 64;
-            const uint32_t valid = canDelta ? (uint32_t)G.hget(Game::HX_POVALID) : 0u;
+            const uint32_t valid = canDelta ? (uint32_t)G.hget(Game<STEADY>::HX_POVALID) : 0u;
             if (selfplay && G.poFast2()) {
                 if (freshObs) {  // PO views of the reset state (snapshot(p) touches only view p's bits)
                     if (G.snapBothOk()) {
@@ -6104,7 +6128,7 @@ __global__ __launch_bounds__(HELP ? 128 : 64, (HELP || FIX == 16) ? 4 : 1) void 
 #endif
         }
     }
-    if (MODE == MODE_STEP && MRTS_UNLIKELY(D.rec_out != nullptr) && external) G.writeRecord(it);
+    if (MODE == MODE_STEP && MRTS_UNLIKELY(D_OFF(rec_out) != nullptr) && external) G.writeRecord(it);
     if (HELP && !FPO) __syncthreads();  // A_{it+1}: step it's cells packed; the helper's rows of step it + 1 ready
     if (HELP && FPO) {
         if (poHelpFlags == 0u && G.lid() == 0) poHelpHdr[(it & 1) * 4 + 2] = 0u;
@@ -6122,9 +6146,9 @@ __global__ __launch_bounds__(HELP ? 128 : 64, (HELP || FIX == 16) ? 4 : 1) void 
         G.recOut = poHelpFlags == 4u ? poHelpHdr + PO_HELP_REC : nullptr;
         if (poHelpFlags == 4u && G.lid() == 0) G.recOut[5 * 64] = 0u;  // none, unless writeMasksLanes hands them over
     }
-    if (D.masks && external) {
+    if (D_HAS(masks) && external) {
         const int nsl = selfplay ? 2 : 1;
-        if (MRTS_LIKELY(D.mask_delta && G.nu <= 64 && nsl * maskWords(G.HW) <= 64 && G.K <= 96)) {
+        if (MRTS_LIKELY(D_ON(mask_delta) && G.nu <= 64 && nsl * maskWords(G.HW) <= 64 && G.K <= 96)) {
             PHASE(8);
             if (selfplay) G.writeMasksLanes(slot0, 2, 0, 1);
             else G.writeMasksLanes(slot0, 1, D.mask_player, D.mask_player);
@@ -6136,7 +6160,7 @@ __global__ __launch_bounds__(HELP ? 128 : 64, (HELP || FIX == 16) ? 4 : 1) void 
         if (selfplay) G.writeMasks(slot0, 2, 0, 1);
         else G.writeMasks(slot0, 1, D.mask_player, D.mask_player);
         }
-        if (D.pol_actions && !(D.pol_delta && D.mask_delta && ((G.HW * G.K) & 15) == 0)) {  // no dirty-row pass ran
+        if (D_HAS(pol_actions) && !(D_ON(pol_delta) && D_ON(mask_delta) && ((G.HW * G.K) & 15) == 0)) {  // no dirty-row pass ran
             wsync();
             if (selfplay) G.writePolicyAll(slot0, 2, 0, 1);
             else G.writePolicyAll(slot0, 1, D.mask_player, D.mask_player);
@@ -6885,6 +6909,80 @@ hipError_t launchEvaluate(const KStatic& hs, const KStatic* ds, int maxplayer, f
 
 // e0 / e1 (may be null): timing events the launch records itself (hipExtLaunchKernelGGL: the kernel
 // dispatch's own start / end timestamps — no separate marker packets around it; mrts_set_rollout_events)
+// The steady state of the fused self-play rollout on the 16x16 shape (BASELINE c3's launch): a multi-step launch whose
+// masks, policy rows and action rows all continue the previous launch's, with the plain int32 observation, WinLoss
+// alone as the reward and none of the optional outputs.  k_env's STEADY instance compiles these tests as constants
+// (D_HAS / D_OFF / D_ON / D_ZERO), so every condition below is one the instance relies on: a launch that deviates in
+// any of them runs the general instance.  (KDyn.players is not among them: the specialised self-play instances never
+// read it, and the Python front end always passes its players tensor.)
+static bool steadyLaunch(const KStatic& hs, const KDyn& D) {
+    const bool shape = hs.n_sp_games == hs.n_games && hs.utt.K == 79 && hs.utt.ntypes == 7 && hs.utt.maxAttackRadius == 7 &&
+                       hs.H == 16 && hs.W == 16 && hs.CAP == 320 && !hs.partial_obs && !hs.bot_off;
+    const bool on = D.n_iter > 1 && D.mask_delta == 1 && D.pol_delta == 1 && D.fwd_read == 1 && D.obs_img == 1;
+    const bool has = D.actions && D.obs && D.masks && D.source && D.pol_actions && D.reward && D.done && D.prio_tab && D.bal;
+    const bool off = !D.obs8 && !D.obs16 && !D.rec_out && !D.uni_actions && !D.rows;
+    const bool zero = D.resp_stride == 0 && D.n_rewards == 1 && D.reward_kinds4 == (uint32_t)RF_WINLOSS && D.reward_need == 0;
+    return shape && on && has && off && zero;
+}
+// steadyLaunch for a launch that deviates from the steady state in one condition (`dev` < 0: in none): 1 / 0, or -1
+// past the last deviation.  Not part of include/mrts.h: the tests' view of the selection.
+extern "C" int mrts_internal_steady_probe(int dev) {
+    KStatic hs{};
+    hs.n_games = hs.n_sp_games = 512;
+    hs.utt.K = 79;
+    hs.utt.ntypes = 7;
+    hs.utt.maxAttackRadius = 7;
+    hs.H = hs.W = 16;
+    hs.HW = 256;
+    hs.CAP = 320;
+    static int32_t buf[4];
+    void* const some = buf;
+    KDyn D{};
+    D.n_iter = 20;
+    D.mask_delta = D.pol_delta = D.fwd_read = D.obs_img = 1;
+    D.actions = (const int32_t*)some;
+    D.obs = (int32_t*)some;
+    D.masks = (uint8_t*)some;
+    D.source = (uint32_t*)some;
+    D.pol_actions = (int32_t*)some;
+    D.reward = (double*)some;
+    D.done = (uint8_t*)some;
+    D.prio_tab = (uint32_t*)some;
+    D.bal = (int32_t*)some;
+    D.n_rewards = 1;
+    switch (dev) {
+        case 0: D.n_iter = 1; break;
+        case 1: hs.H = hs.W = 8; hs.HW = 64; hs.CAP = 128; break;
+        case 2: hs.partial_obs = 1; break;
+        case 3: hs.n_games = 513; break;
+        case 4: hs.bot_off = 1; break;
+        case 5: D.mask_delta = 0; break;
+        case 6: D.pol_delta = 0; break;
+        case 7: D.fwd_read = 0; break;
+        case 8: D.obs_img = 0; break;
+        case 9: D.obs = nullptr; break;
+        case 10: D.masks = nullptr; break;
+        case 11: D.source = nullptr; break;
+        case 12: D.pol_actions = nullptr; break;
+        case 13: D.reward = nullptr; break;
+        case 14: D.done = nullptr; break;
+        case 15: D.prio_tab = nullptr; break;
+        case 16: D.bal = nullptr; break;
+        case 17: D.obs8 = (uint8_t*)some; break;
+        case 18: D.obs16 = (int16_t*)some; break;
+        case 19: D.rec_out = (uint32_t*)some; break;
+        case 20: D.uni_actions = (int32_t*)some; break;
+        case 21: D.rows = (const int32_t*)some; break;
+        case 22: D.resp_stride = 1024; break;
+        case 23: D.n_rewards = 2; break;
+        case 24: D.reward_kinds4 = (uint32_t)RF_ATTACK; break;
+        case 25: D.reward_need = RN_COUNTS; break;
+        case 26: D.actions = nullptr; break;
+        default: if (dev >= 0) return -1;
+    }
+    return steadyLaunch(hs, D) ? 1 : 0;
+}
+
 hipError_t launchEnv(int mode, const KStatic& hs, const KStatic* ds, const KDyn& D, hipStream_t stream, hipEvent_t e0, hipEvent_t e1) {
     const size_t lds = hs.bot_off ? (size_t)hs.bot_lds + lrLdsBytes(hs.HW, hs.W, hs.CAP) : ldsBytes(hs.HW, hs.W, hs.CAP, hs.partial_obs);
     dim3 grid((unsigned)hs.n_games), block(64);
@@ -6894,7 +6992,9 @@ hipError_t launchEnv(int mode, const KStatic& hs, const KStatic* ds, const KDyn&
 #define LAUNCH(kern, g_, b_, l_, s_, ...) hipExtLaunchKernelGGL(kern, g_, b_, (uint32_t)(l_), s_, e0, e1, 0, __VA_ARGS__)
     switch (mode) {
         case MODE_STEP:
-            if (D.n_iter > 1 && is(16, 320, false)) LAUNCH((k_env<MODE_STEP, 16, 320, false, true>), grid, block, lds, stream, D.state, ds, D);
+            if (is(16, 320, false) && steadyLaunch(hs, D))
+                LAUNCH((k_env<MODE_STEP, 16, 320, false, true, false, false, true>), grid, block, lds, stream, D.state, ds, D);
+            else if (D.n_iter > 1 && is(16, 320, false)) LAUNCH((k_env<MODE_STEP, 16, 320, false, true>), grid, block, lds, stream, D.state, ds, D);
             else if (D.n_iter > 1 && is(8, 128, false) && D.uni_actions && !D.masks) {
                 // c2's fused uniform rollout: a helper wave per game (helperLoop)
                 KDyn D2 = D;
