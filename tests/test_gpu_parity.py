@@ -286,7 +286,10 @@ def test_full_size_c2_uniform():
 
 @pytest.mark.parametrize("mp,po,n_bot", [("maps/16x16/basesWorkers16x16.xml", False, 0),
                                           ("maps/10x10/basesWorkers10x10.xml", True, 6),
-                                          ("maps/4x4/base4x4.xml", False, 4)])
+                                          ("maps/4x4/base4x4.xml", False, 4),
+                                          # combat units: attack slots of range > 1 in the delta rows
+                                          ("maps/16x16/melee16x16Mixed12.xml", False, 0),
+                                          ("maps/melee14x12Mixed18.xml", True, 4)])
 def test_delta_masks_and_source_policy_match_full(mp, po, n_bot):
     """Delta mask and observation writes (only dirty rows / 4-cell chunks rewritten) leave the buffers
     byte-identical to full writes after every step (auto-resets at 150 steps included), and the
@@ -610,6 +613,7 @@ def test_max_units_below_map_units_rejected():
     ("maps/8x8/basesWorkers8x8.xml", 8, 0, False, False),
     ("maps/10x10/basesWorkers10x10.xml", 4, 2, True, True),     # H*W*K % 16 != 0: full mask path
     ("maps/BWDistantResources32x32.xml", 4, 0, True, True),
+    ("maps/16x16/melee16x16Mixed12.xml", 8, 0, False, True),    # Ranged units: the far attack bits
 ])
 def test_fused_policy_matches_separate_kernels(mp, n_sp, n_bot, po, delta):
     """mrts_step_fused_dev = mrts_step_dev followed by mrts_policy_dev(next step), bit for bit, including

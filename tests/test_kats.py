@@ -1,5 +1,6 @@
 """Hand-derived known-answer tests for the Java semantics of SURVEY.md Appendix A (and the a12 mask
-layout), on 4x4 / 5x5 micro-maps written here.
+layout), on 4x4 / 5x5 micro-maps written here; the ranged-window KATs at the end use layouts of
+tests.combat_maps on 8x8 .. 32x32 maps.
 
 Every expected value below is worked out from the Java text (the file:line next to each KAT), not
 from either implementation.  Each KAT runs on the CPU oracle (unmarked: part of the CPU suite) and on
@@ -446,10 +447,144 @@ def kat_selfplay_reset_keeps_slots_from_two(tmp, backend):
     r.close()
 
 
+SIGHT = {BASE: 5, BARRACKS: 3, WORKER: 3, LIGHT: 2, HEAVY: 2, RANGED: 3}  # UnitTypeTable.java:137-279
+
+
+def window_positions(W, H):
+    """Where the ranged-window KATs put the Ranged unit: the centre, the four corners, one cell on each
+    edge and one cell at distance 2 from two edges (the first window column / row that is clipped)."""
+    return [(W // 2, H // 2), (0, 0), (W - 1, 0), (0, H - 1), (W - 1, H - 1), (W // 2 - 1, 0), (W // 2 + 1, H - 1),
+            (0, H // 2 + 1), (W - 1, H // 2 - 1), (W - 3, 2)]
+
+
+def _expected_view(layout, W, H, player, po):
+    """hp / owner / type planes (and, partially observable, the two visibility planes) of `player`'s
+    reset observation of a layout {(x, y): (type, owner)}, from GameState.getVectorObservation
+    (GameState.java:942-951): hp, ((owner + player) % 2) + 1 for owned units, type id + 1.  Partially
+    observable: a unit of another owner (Resources too) is in the view only if some unit of `player` has
+    it within its sightRadius, dx^2 + dy^2 <= r^2 (PartiallyObservableGameState.java:45-53, 61-71); plane 6
+    is the union of the sight disks of `player`'s units and plane 7 that of the opponent's units that
+    are in the view (PartiallyObservableGameState.java:145-150, 156-178)."""
+    own = [(x, y, SIGHT[t]) for (x, y), (t, p) in layout.items() if p == player]
+
+    def seen(x, y):
+        return any((ux - x) ** 2 + (uy - y) ** 2 <= r * r for ux, uy, r in own)
+
+    hp, owner, typ = (np.zeros((H, W), np.int32) for _ in range(3))
+    vis = np.zeros((2, H, W), np.int32)
+    for (x, y), (t, p) in layout.items():
+        if po and p != player and not seen(x, y):
+            continue
+        hp[y, x], typ[y, x] = HP[t], t + 1
+        if p >= 0:
+            owner[y, x] = ((p + player) % 2) + 1
+            r = SIGHT[t]
+            for dy in range(-r, r + 1):
+                for dx in range(-r, r + 1):
+                    if 0 <= x + dx < W and 0 <= y + dy < H and dx * dx + dy * dy <= r * r:
+                        vis[0 if p == player else 1, y + dy, x + dx] = 1
+    return hp, owner, typ, vis
+
+
+def _ranged_window_kat(tmp, backend, W, H, po=False, max_units=0):
+    """a12 — the attack slots of a unit with attackRange > 1.  Unit.getUnitActions (Unit.java:424-434):
+    one ATTACK_LOCATION for every unit u of the other player (u.player >= 0, so no Resource) with
+    (u.x - x)^2 + (u.y - y)^2 <= attackRange^2 — Ranged: 3 (UnitTypeTable.java:270), so the 28 offsets
+    with dx^2 + dy^2 <= 9 — over the whole unit list, no window and no map-border test of its own.
+    UnitAction.getValidActionArray (UnitAction.java:742-747) sets slot 30 + (3 + dy) * 7 + (3 + dx) and the
+    attack type bit 1 + 5; slot 0 marks an own unit without an action (JNIGridnetClientSelfPlay.java:196-209).
+    The masks always come from the full state, partially observable or not (:205).
+    One handle, one game per (position, flip) of tests.combat_maps.ranged_window: in every game the
+    Ranged cell's 49 attack slots, attack type bit and slot 0 equal the rule applied to the layout; over
+    the two flips every in-range offset is set once and clear once.  Every other mask row equals the
+    oracle's.  The reset observations of both players equal _expected_view of the layout."""
+    from tests.combat_maps import in_range, ranged_window
+
+    games = [(cx, cy, flip) for cx, cy in window_positions(W, H) for flip in (0, 1)]
+    maps, layouts = [], []
+    for g, (cx, cy, flip) in enumerate(games):
+        m, lay = ranged_window(tmp / f"rw{W}x{H}_{g}.xml", W, H, cx, cy, flip)
+        maps += [m, m]
+        layouts.append(lay)
+    S = len(maps)
+    ref = oracle_py.OracleVecClient(S, 0, 2000, maps, partial_obs=po)
+    ref_obs, _, _ = ref.reset()
+    ref_masks = ref.get_masks(0)
+    if backend == "oracle":
+        obs, masks = ref_obs, ref_masks
+    else:
+        import torch
+
+        assert torch.cuda.is_available(), "GPU KATs need an MI355X"
+        from microrts_amd import DeviceVecEnv
+
+        e = DeviceVecEnv(S, 0, 2000, maps, partial_obs=po, max_units=max_units)
+        e.reset()
+        e.synchronize()
+        obs, masks = e.obs.cpu().numpy(), e.masks.cpu().numpy()
+        assert not e.error_flags().any()
+        e.close()
+    ref.close()
+    assert masks.shape == (S, H, W, 79)
+    hit = np.zeros((7, 7), np.int32)
+    for g, (cx, cy, flip) in enumerate(games):
+        lay = layouts[g]
+        if (cx, cy) == (W // 2, H // 2) and min(W, H) >= 9:
+            assert len(lay) == 81  # more than one wave of units: the multi-block mask path
+        want = np.zeros(49, np.uint8)
+        for dy in range(-3, 4):
+            for dx in range(-3, 4):
+                t, p = lay.get((cx + dx, cy + dy), (None, -1))
+                if (dx, dy) != (0, 0) and in_range(dx, dy) and p == 1:
+                    want[atk(dx, dy)] = 1
+        hit += want.reshape(7, 7) if (cx, cy) == (W // 2, H // 2) else 0
+        k = masks[2 * g, cy, cx]
+        tag = f"{W}x{H} Ranged at ({cx},{cy}) flip {flip}"
+        assert k[30:79].tolist() == want.tolist(), \
+            f"{tag}: attack slots\n got {k[30:79].reshape(7, 7)}\nwant {want.reshape(7, 7)}"
+        assert k[0] == 1 and k[1 + ATTACK] == int(want.any()), tag
+        rest = np.ones((H, W), bool)
+        rest[cy, cx] = False
+        assert np.array_equal(masks[2 * g][rest], ref_masks[2 * g][rest]), f"{tag}: other rows of player 0"
+        assert np.array_equal(masks[2 * g + 1], ref_masks[2 * g + 1]), f"{tag}: rows of player 1"
+        for player in (0, 1):
+            o = obs[2 * g + player]
+            hp, owner, typ, vis = _expected_view(lay, W, H, player, po)
+            for name, plane, exp in (("hp", 0, hp), ("owner", 2, owner), ("type", 3, typ)) + \
+                    ((("own sight", 6, vis[0]), ("opponent sight", 7, vis[1])) if po else ()):
+                assert np.array_equal(o[plane], exp), f"{tag}: {name} plane of player {player}\n got {o[plane]}\nwant {exp}"
+    if min(W, H) >= 7:  # the centre window is whole: over the two flips every in-range offset was set once
+        disk = np.array([[int(in_range(dx, dy) and (dx, dy) != (0, 0)) for dx in range(-3, 4)] for dy in range(-3, 4)])
+        assert np.array_equal(hit, disk) and disk.sum() == 28
+
+
+def kat_ranged_window_16x16(tmp, backend):
+    """_ranged_window_kat on 16x16 (the specialised step kernel's shape): Unit.java:424-434."""
+    _ranged_window_kat(tmp, backend, 16, 16)
+
+
+def kat_ranged_window_8x8(tmp, backend):
+    """_ranged_window_kat on 8x8: the 9x9 block is clipped on every side (Unit.java:424-434)."""
+    _ranged_window_kat(tmp, backend, 8, 8)
+
+
+def kat_ranged_window_14x12(tmp, backend):
+    """_ranged_window_kat on a non-square map (the generic kernel): Unit.java:424-434."""
+    _ranged_window_kat(tmp, backend, 14, 12)
+
+
+def kat_ranged_window_32x32_po(tmp, backend):
+    """_ranged_window_kat on 32x32, partially observable, max_units 256 (the helper-wave kernel's shape):
+    the masks still come from the full state (JNIGridnetClientSelfPlay.java:205), the views hide what no
+    own sight disk covers (Light's radius 2, Ranged's 3: PartiallyObservableGameState.java:61-71)."""
+    _ranged_window_kat(tmp, backend, 32, 32, po=True, max_units=256)
+
+
 KATS = [kat_illegal_becomes_none_eta, kat_resource_quirk_row_order, kat_rows_that_do_not_count,
         kat_player1_sees_player0_reservations, kat_dead_unit_still_executes, kat_simultaneous_kill_is_a_draw,
         kat_harvest_deplete_return, kat_duplicate_row_keeps_map_position, kat_po_killed_unit_in_view, kat_mask_record,
-        kat_reward_functions, kat_env_steps_survive_reset, kat_selfplay_reset_keeps_slots_from_two]
+        kat_reward_functions, kat_env_steps_survive_reset, kat_selfplay_reset_keeps_slots_from_two,
+        kat_ranged_window_16x16, kat_ranged_window_8x8, kat_ranged_window_14x12, kat_ranged_window_32x32_po]
 
 
 @pytest.mark.parametrize("kat", KATS, ids=[k.__name__ for k in KATS])
