@@ -344,6 +344,41 @@ int mrts_obs_invalidate(mrts_env* env);
 /* the next mrts_policy_dev call writes every row, and the next fused step decodes the rows of
  * d_actions (not the copy the previous fused call kept): call it after writing d_actions yourself */
 int mrts_policy_invalidate(mrts_env* env);
+/* Masked policy head (no Java counterpart: MicroRTS-Py's GridNet head, its per-component masked categoricals),
+ * between a network's logits and the action rows.  d_logits: float32 [rows][H*W][K-1], logit j for mask slot
+ * j + 1, so the fields are action type [0,6), move / harvest / return / produce direction [6,10) [10,14) [14,18)
+ * [18,22), produce type [22,22+ntypes) and the attack window [22+ntypes,K-1); action rows [type, move, harvest,
+ * return, produce dir, produce type, attack index].  A cell is a candidate when its mask slot 0 is non-zero; any
+ * other cell gets a zero row and adds nothing.  For a candidate, every field with a set mask bit is an independent
+ * categorical over its set bits, p_i = exp(l_i - m) / sum_j exp(l_j - m) in fp32 (m: the maximum over the set
+ * bits); all non-empty fields are drawn and counted (the environment ignores the parameters that do not belong to
+ * the drawn type); an empty field gives component 0 and adds nothing — MicroRTS-Py adds log n / -log n constants
+ * there, which change neither PPO ratios nor gradients.  Logits at cleared bits and of other cells never enter the
+ * arithmetic (they may be NaN / inf).  logprob / entropy: per row the sum over candidate cells and non-empty
+ * fields, float32 [rows], reduced in a fixed order (the same inputs give the same bytes); either may be NULL.
+ * mrts_policy_head_sample_dev: rows = n_slots.  Candidates from d_source (the source bits of
+ * mrts_set_source_output: only candidate cells' mask records and logit rows are read) or, d_source NULL, from mask
+ * byte 0.  Philox4x32-10, key = seed, counters (slot_id_base + slot, step, cell, 0x48454144) and (.., 0x48454145):
+ * their eight words serve the seven fields in order, u = (word >> 8) * 2^-24, and the draw is the smallest set bit
+ * whose running sum of exp(l - m) exceeds u * S (the last set bit if rounding leaves none).  Writes every row of
+ * d_actions [n_slots][H*W][7] and leaves the handle as mrts_policy_invalidate() would.
+ * mrts_policy_head_score_dev: the log-probability of the given d_actions rows and the entropy, for any n_rows (an
+ * update minibatch is T x slots rows); candidates from mask byte 0.  A component outside its non-empty field's set
+ * bits makes that row's log-probability -inf.
+ * mrts_policy_head_grad_dev: d_grad_logits [n_rows][H*W][K-1] = the gradient of sum_r g_logprob[r] * logprob[r] +
+ * g_entropy[r] * entropy[r]: g_lp * (1[j = a] - p_j) + g_ent * (-p_j * (log p_j + H_field)) at the set bits of a
+ * candidate's non-empty fields (a field whose given component is not a set bit: the entropy term only), exact
+ * zero elsewhere; every element is written.  d_g_logprob / d_g_entropy: float32 [n_rows], NULL = zeros.
+ * -EINVAL: a NULL required pointer, n_rows < 0 or n_rows * H*W >= 2^31; -ENOTSUP: a bot-only or forward-model
+ * handle (neither has masks). */
+int mrts_policy_head_sample_dev(mrts_env* env, const float* d_logits, const uint8_t* d_masks, const uint32_t* d_source,
+                                uint64_t seed, uint32_t step, int32_t* d_actions, float* d_logprob, float* d_entropy,
+                                void* stream);
+int mrts_policy_head_score_dev(mrts_env* env, int32_t n_rows, const float* d_logits, const uint8_t* d_masks,
+                               const int32_t* d_actions, float* d_logprob, float* d_entropy, void* stream);
+int mrts_policy_head_grad_dev(mrts_env* env, int32_t n_rows, const float* d_logits, const uint8_t* d_masks,
+                              const int32_t* d_actions, const float* d_g_logprob, const float* d_g_entropy,
+                              float* d_grad_logits, void* stream);
 /* Optional compact output of every mask write: mask slot 0 ("own unit without an action here") as
  * bits, uint32 [n_slots][ceil(H*W/32)] (sticky; NULL disables).  mrts_policy_dev uses it, when
  * given, to read only the candidate cells' mask rows. */

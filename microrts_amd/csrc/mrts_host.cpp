@@ -42,6 +42,7 @@ hipError_t phaseTimes(unsigned long long* out, int reset);
 hipError_t phaseSpans(unsigned long long* out, int n);
 #endif
 hipError_t launchPolicy(const PolicyParams& Q, hipStream_t stream, bool* prevWritten);
+hipError_t launchHead(int mode, const HeadParams& Q, hipStream_t stream);
 hipError_t launchWiden(const uint8_t* in, int32_t* out, size_t n, hipStream_t stream);
 hipError_t launchOneHot(const int32_t* obs, uint8_t* out, int n_slots, int HW, int C, int ntypes, hipStream_t stream);
 hipError_t prepareLds(size_t bytes);
@@ -456,6 +457,7 @@ struct mrts_env {
     int H = 0, W = 0, HW = 0, CAP = 0, C = 6, K = 79;
     int nSlots = 0, nGames = 0, nSpGames = 0, maxSteps = 0, partialObs = 0;
     int forwardModel = 0;  // games advance through mrts_playout* only (GT_PLAYOUT)
+    int botOnly = 0;       // the bot-only client (ai1_kinds): reward / done only, no observation or masks
     int maxUnits = 0;      // live-unit bound (H*W unless mrts_config.max_units)
     // native LightRush: the handle has a LightRush game, so every state block carries the bot's memory
     // (mrts_internal.h botWords) after its stateWords; botTypes = the types named Base, Barracks, Worker, Light
@@ -713,6 +715,7 @@ int mrts_create(const mrts_config* cfg, mrts_env** out) {
         }
         if (cfg->ai1_kinds && cfg->n_selfplay_slots) throw Fail{-EINVAL, "the bot-only client has no self-play slots"};
         env->forwardModel = cfg->forward_model ? 1 : 0;
+        env->botOnly = cfg->ai1_kinds ? 1 : 0;
         if (env->forwardModel && !cfg->ai1_kinds) throw Fail{-EINVAL, "a forward model needs ai1_kinds (player 0's playout policy)"};
         if (env->forwardModel && cfg->partial_obs) throw Fail{-EINVAL, "a forward model plays on the full state (partial_obs must be 0)"};
         env->gameKindHost.assign((size_t)env->nGames, 0);  // self-play = 0
@@ -1815,6 +1818,88 @@ int mrts_policy_dev(mrts_env* env, const uint8_t* d_masks, const uint32_t* d_sou
         env->polValid = prevWritten;
         if (prevWritten) env->polParity ^= 1;
         env->lastPolicyActions = d_actions;
+        return 0;
+    } catch (const Fail& f) {
+        return fail(f);
+    }
+}
+
+namespace {
+// the policy head's shared argument checks; n_rows rows of the handle's H*W cells
+HeadParams headParams(mrts_env* env, int32_t n_rows, const float* d_logits, const uint8_t* d_masks, const int32_t* d_actions) {
+    if (!env) throw Fail{-EINVAL, "null handle"};
+    if (env->botOnly || env->forwardModel)
+        throw Fail{-ENOTSUP, "the policy head needs a handle that writes masks (not a bot-only or forward-model handle)"};
+    if (!d_logits || !d_masks || !d_actions) throw Fail{-EINVAL, "null argument"};
+    if (n_rows < 0 || (int64_t)n_rows * env->HW >= ((int64_t)1 << 31)) throw Fail{-EINVAL, "n_rows: 0 <= n_rows * H*W < 2^31"};
+    if (((uintptr_t)d_logits & 3) || ((uintptr_t)d_actions & 3)) throw Fail{-EINVAL, "misaligned buffer"};
+    const int nt = env->utt.ntypes, natt = env->K - 23 - nt;
+    if (env->K - 1 > HEAD_MAX_LOGITS || nt > 16 || natt < 0 || natt > 64)
+        throw Fail{-ENOTSUP, "the policy head: at most 16 unit types, 64 attack-window cells and 80 logits per cell"};
+    HeadParams Q;
+    std::memset(&Q, 0, sizeof(Q));
+    Q.HW = env->HW;
+    Q.K = env->K;
+    Q.ntypes = nt;
+    Q.n_rows = n_rows;
+    Q.slot_id_base = env->slotIdBase;
+    Q.logits = d_logits;
+    Q.masks = d_masks;
+    Q.actions = const_cast<int32_t*>(d_actions);
+    return Q;
+}
+}  // namespace
+
+int mrts_policy_head_sample_dev(mrts_env* env, const float* d_logits, const uint8_t* d_masks, const uint32_t* d_source,
+                                uint64_t seed, uint32_t step, int32_t* d_actions, float* d_logprob, float* d_entropy,
+                                void* stream) {
+    try {
+        HeadParams Q = headParams(env, env ? env->nSlots : 0, d_logits, d_masks, d_actions);
+        if (((uintptr_t)d_source & 3) || ((uintptr_t)d_logprob & 3) || ((uintptr_t)d_entropy & 3)) throw Fail{-EINVAL, "misaligned buffer"};
+        HIPCHK(hipSetDevice(env->device));
+        Q.source = d_source;
+        Q.seed = seed;
+        Q.step = step;
+        Q.logprob = d_logprob;
+        Q.entropy = d_entropy;
+        // the rows are no longer what the masked-uniform policy or a fused step wrote (mrts_policy_invalidate)
+        env->polValid = false;
+        env->fusedActions = nullptr;
+        HIPCHK(launchHead(HEAD_SAMPLE, Q, pickStream(env, stream)));
+        return 0;
+    } catch (const Fail& f) {
+        return fail(f);
+    }
+}
+
+int mrts_policy_head_score_dev(mrts_env* env, int32_t n_rows, const float* d_logits, const uint8_t* d_masks,
+                               const int32_t* d_actions, float* d_logprob, float* d_entropy, void* stream) {
+    try {
+        HeadParams Q = headParams(env, n_rows, d_logits, d_masks, d_actions);
+        if (((uintptr_t)d_logprob & 3) || ((uintptr_t)d_entropy & 3)) throw Fail{-EINVAL, "misaligned buffer"};
+        HIPCHK(hipSetDevice(env->device));
+        Q.logprob = d_logprob;
+        Q.entropy = d_entropy;
+        HIPCHK(launchHead(HEAD_SCORE, Q, pickStream(env, stream)));
+        return 0;
+    } catch (const Fail& f) {
+        return fail(f);
+    }
+}
+
+int mrts_policy_head_grad_dev(mrts_env* env, int32_t n_rows, const float* d_logits, const uint8_t* d_masks,
+                              const int32_t* d_actions, const float* d_g_logprob, const float* d_g_entropy,
+                              float* d_grad_logits, void* stream) {
+    try {
+        HeadParams Q = headParams(env, n_rows, d_logits, d_masks, d_actions);
+        if (!d_grad_logits) throw Fail{-EINVAL, "null argument"};
+        if (((uintptr_t)d_g_logprob & 3) || ((uintptr_t)d_g_entropy & 3) || ((uintptr_t)d_grad_logits & 3))
+            throw Fail{-EINVAL, "misaligned buffer"};
+        HIPCHK(hipSetDevice(env->device));
+        Q.g_logprob = d_g_logprob;
+        Q.g_entropy = d_g_entropy;
+        Q.grad = d_grad_logits;
+        HIPCHK(launchHead(HEAD_GRAD, Q, pickStream(env, stream)));
         return 0;
     } catch (const Fail& f) {
         return fail(f);

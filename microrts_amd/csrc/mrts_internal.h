@@ -254,4 +254,23 @@ struct PolicyParams {
     int32_t delta;                 // 1: actions holds the previous output; rewrite only prev|source rows
 };
 
+// Masked policy head (mrts_policy_head_*_dev): one wave per row of [n_rows][HW] cells.  mode SAMPLE draws
+// `actions` (source optional: the candidate bits), SCORE reads them, GRAD writes `grad` [n_rows][HW][K-1].
+enum : int32_t { HEAD_SAMPLE = 0, HEAD_SCORE = 1, HEAD_GRAD = 2 };
+constexpr int HEAD_MAX_LOGITS = 80;  // K - 1 of the largest table create accepts (8 types, attack range 3)
+struct HeadParams {
+    int32_t HW, K, ntypes, n_rows;
+    uint32_t slot_id_base, step;
+    uint64_t seed;
+    const float* logits;           // [n_rows][HW][K-1]
+    const uint8_t* masks;          // [n_rows][HW][K]
+    const uint32_t* source;        // SAMPLE, optional: [n_rows][maskWords(HW)] candidate bits
+    int32_t* actions;              // [n_rows][HW][7]: written by SAMPLE, read by SCORE / GRAD
+    float* logprob;                // SAMPLE / SCORE, optional: [n_rows]
+    float* entropy;                // SAMPLE / SCORE, optional: [n_rows]
+    const float* g_logprob;        // GRAD, optional (zeros): [n_rows]
+    const float* g_entropy;        // GRAD, optional (zeros): [n_rows]
+    float* grad;                   // GRAD: [n_rows][HW][K-1], every element written
+};
+
 }  // namespace mrts

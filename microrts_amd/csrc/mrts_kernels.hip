@@ -6412,6 +6412,321 @@ __global__ __launch_bounds__(64) void k_policy(PolicyParams Q) {
     for (int k = 0; k < 7; k++) out[k] = a[k];
 }
 
+// ---------------------------------------------------------------- masked policy head
+// Logits [rows][HW][K-1] (logit j <-> mask slot j + 1) -> per candidate cell (mask slot 0) one independent masked
+// categorical per non-empty field: type [0,6), the four directions [6,22), produce type [22,22+ntypes), attack
+// window [22+ntypes,K-1).  One wave per row; a candidate cell is worked by a 16-lane DPP row, four cells at a
+// time.  A lane owns one logit of the type field, one of the 16 direction logits (a field per quad), one produce
+// type and four consecutive attack-window logits, so every field is one quad or one row and its maximum, sums
+// and running sum are DPP operations inside it.
+constexpr uint32_t HEAD_TAG = 0x48454144u;  // "HEAD": Philox counter word 3 (and HEAD_TAG + 1), apart from 0 / UNIFORM_TAG
+
+template <int CTRL, int ROWS = 0xF>
+DEV float dppF(float old, float v) {
+    return __int_as_float(__builtin_amdgcn_update_dpp(__float_as_int(old), __float_as_int(v), CTRL, ROWS, 0xF, false));
+}
+// max / sum over each W-lane segment (a quad or a 16-lane row), the result on every lane of it: each step
+// combines two values that are already equal across the lanes they came from, so the lanes agree bit for bit
+template <int W>
+DEV float segMax(float v) {
+    LANE_AUDIT_WAVE(2);
+    v = fmaxf(v, dppF<0xB1>(v, v));  // quad_perm [1,0,3,2]
+    v = fmaxf(v, dppF<0x4E>(v, v));  // quad_perm [2,3,0,1]
+    if (W == 16) {
+        v = fmaxf(v, dppF<0x141>(v, v));  // row_half_mirror
+        v = fmaxf(v, dppF<0x140>(v, v));  // row_mirror
+    }
+    return v;
+}
+template <int W>
+DEV float segSum(float v) {
+    LANE_AUDIT_WAVE(2);
+    v += dppF<0xB1>(v, v);
+    v += dppF<0x4E>(v, v);
+    if (W == 16) {
+        v += dppF<0x141>(v, v);
+        v += dppF<0x140>(v, v);
+    }
+    return v;
+}
+// inclusive running sum over each segment, in lane order (ql: the lane's index in its segment)
+template <int W>
+DEV float segScan(float v, int ql) {
+    LANE_AUDIT_WAVE(2);
+    if (W == 16) {
+        v += dppF<0x111>(0.f, v);  // row_shr:1 (lanes shifted in from outside the row read 0)
+        v += dppF<0x112>(0.f, v);
+        v += dppF<0x114>(0.f, v);
+        v += dppF<0x118>(0.f, v);
+    } else {
+        const float t1 = dppF<0x90>(0.f, v);  // quad_perm [0,0,1,2]
+        v += ql >= 1 ? t1 : 0.f;
+        const float t2 = dppF<0x40>(0.f, v);  // quad_perm [0,0,0,1]
+        v += ql >= 2 ? t2 : 0.f;
+    }
+    return v;
+}
+// a double through DPP as its two halves (lanes without a source read 0.0)
+template <int CTRL, int ROWS = 0xF>
+DEV double dppD(double v) {
+    const uint64_t b = (uint64_t)__double_as_longlong(v);
+    const uint32_t lo = (uint32_t)__builtin_amdgcn_update_dpp(0, (int)(uint32_t)b, CTRL, ROWS, 0xF, false);
+    const uint32_t hi = (uint32_t)__builtin_amdgcn_update_dpp(0, (int)(uint32_t)(b >> 32), CTRL, ROWS, 0xF, false);
+    return __longlong_as_double((long long)(((uint64_t)hi << 32) | lo));
+}
+// sum over the wave in a fixed order (wave_reduce's DPP chain on doubles): a row's log-probability and entropy add
+// up to 64 x 7 fp32 terms per lane, and double partial sums keep their rounding below that of the terms
+DEV double waveSumD(double v) {
+    LANE_AUDIT_WAVE(2);
+    v += dppD<0xB1>(v);
+    v += dppD<0x4E>(v);
+    v += dppD<0x141>(v);
+    v += dppD<0x140>(v);
+    v += dppD<0x142, 0xA>(v);
+    v += dppD<0x143, 0xC>(v);
+    const uint64_t b = (uint64_t)__double_as_longlong(v);
+    const uint32_t lo = (uint32_t)rl((int)(uint32_t)b, 63), hi = (uint32_t)rl((int)(uint32_t)(b >> 32), 63);
+    return __longlong_as_double((long long)(((uint64_t)hi << 32) | lo));
+}
+
+// one candidate cell as its 16-lane row sees it
+struct HeadCell {
+    bool act;             // the row has a cell this round
+    const float* lrow;    // its K-1 logits
+    const uint8_t* mrec;  // its K mask bytes
+    const int32_t* arow;  // SCORE / GRAD: its given action row
+    int32_t* srow;        // SAMPLE: its action row in LDS (zeroed)
+    float* grow;          // GRAD: its gradient row in LDS (zeroed)
+    float glp, gent;      // GRAD: the row's upstream gradients
+    double lp, ent;       // per-lane partial sums of the row's log-probability and entropy (fp32 terms)
+    uint32_t w0, wd, w5, w6;  // SAMPLE: the Philox words of the lane's fields (type, its direction field, produce type, attack)
+};
+
+// One field, NE logits per lane (l / set: the lane's logits and mask bits, 0 / false outside the field), the field
+// spanning a W-lane segment.  idx0: the field-local index of l[0]; a: the given component (SCORE / GRAD).
+template <int MODE, int NE, int W>
+DEV void headField(HeadCell& X, int lane, const float* l, const bool* set, int j0, int idx0, int field, uint32_t word, int a) {
+#pragma clang fp contract(off)
+    const int ql = lane & (W - 1), segbase = lane - ql;
+    const uint32_t segmask = (1u << W) - 1u;
+    float mx = -INFINITY;
+    bool anyset = false;
+#pragma unroll
+    for (int k = 0; k < NE; k++) {
+        mx = set[k] ? fmaxf(mx, l[k]) : mx;
+        anyset |= set[k];
+    }
+    mx = segMax<W>(mx);
+    const uint32_t sb = (uint32_t)(ballot(anyset) >> segbase) & segmask;
+    const bool nonempty = sb != 0;
+    float e[NE], lt = 0.f, tt = 0.f;
+#pragma unroll
+    for (int k = 0; k < NE; k++) {
+        const float d = l[k] - mx;
+        e[k] = set[k] ? expf(d) : 0.f;
+        lt += e[k];
+        tt += set[k] ? e[k] * d : 0.f;
+    }
+    const float S = segSum<W>(lt), T = segSum<W>(tt);
+    const float logS = logf(S), H = logS - T / S;
+    X.ent += (nonempty && ql == 0) ? (double)H : 0.0;
+    if (MODE == HEAD_SAMPLE) {
+        // the smallest set bit whose running sum exceeds u * S, else (rounding) the last set bit
+        const float thr = (float)(word >> 8) * 0x1p-24f * S;
+        float run = segScan<W>(lt, ql);
+        if (NE > 1) run = dppF<0x111>(0.f, run);  // exclusive: the lanes before this one
+        bool hit[NE], anyhit = false;
+#pragma unroll
+        for (int k = 0; k < NE; k++) {
+            if (NE > 1) run += e[k];
+            hit[k] = set[k] && run > thr;
+            anyhit |= hit[k];
+        }
+        const uint32_t hb = (uint32_t)(ballot(anyhit) >> segbase) & segmask;
+        const int pick = hb ? __builtin_ctz(hb) : (sb ? 31 - __builtin_clz(sb) : 0);
+        int kk = -1;
+        float dsel = 0.f;
+#pragma unroll
+        for (int k = NE - 1; k >= 0; k--)
+            if (hit[k]) {
+                kk = k;
+                dsel = l[k] - mx;
+            }
+        if (kk < 0) {
+#pragma unroll
+            for (int k = 0; k < NE; k++)
+                if (set[k]) {
+                    kk = k;
+                    dsel = l[k] - mx;
+                }
+        }
+        if (nonempty && ql == pick) {
+            X.srow[field] = idx0 + kk;
+            X.lp += (double)(dsel - logS);
+        }
+    } else {
+        bool match[NE], anym = false;
+#pragma unroll
+        for (int k = 0; k < NE; k++) {
+            match[k] = set[k] && idx0 + k == a;
+            anym |= match[k];
+        }
+        const bool hasA = ((uint32_t)(ballot(anym) >> segbase) & segmask) != 0;
+        if (MODE == HEAD_SCORE) {
+#pragma unroll
+            for (int k = 0; k < NE; k++) X.lp += match[k] ? (double)((l[k] - mx) - logS) : 0.0;
+            // a component outside the field's set bits: the row's log-probability is -inf
+            X.lp += (nonempty && !hasA && ql == 0) ? (double)-INFINITY : 0.0;
+        } else {
+#pragma unroll
+            for (int k = 0; k < NE; k++)
+                if (set[k]) {
+                    const float p = e[k] / S, logp = (l[k] - mx) - logS;
+                    float gv = X.gent * (-p * (logp + H));
+                    if (hasA) gv += X.glp * ((match[k] ? 1.f : 0.f) - p);
+                    X.grow[j0 + k] = gv;
+                }
+        }
+    }
+}
+
+template <int MODE>
+DEV void headCell(HeadCell& X, const HeadParams& Q, int lane) {
+    const int q = lane & 15, nt = Q.ntypes, natt = Q.K - 23 - nt;
+    // the lane's seven logits: 0 type, 1 a direction (quad = field), 2 produce type, 3..6 attack window 4q..4q+3
+    int j[7];
+    bool in[7];
+    j[0] = q, in[0] = q < 6;
+    j[1] = 6 + q, in[1] = true;
+    j[2] = 22 + q, in[2] = q < nt;
+#pragma unroll
+    for (int k = 0; k < 4; k++) j[3 + k] = 22 + nt + 4 * q + k, in[3 + k] = 4 * q + k < natt;
+    // Unconditional loads (a lane without a logit of the field, or a row without a cell this round, reads logit 0
+    // of a cell of the chunk): all fourteen are in flight together, one memory round per cell.  The logit of a
+    // cleared bit comes with its row's cache lines and is dropped by the select: it never reaches the arithmetic.
+    float l[7];
+    bool set[7];
+#pragma unroll
+    for (int i = 0; i < 7; i++) {
+        const int jj = in[i] ? j[i] : 0;
+        const uint32_t mb = X.mrec[1 + jj];
+        const float lv = X.lrow[jj];
+        set[i] = X.act && in[i] && mb != 0;
+        l[i] = set[i] ? lv : 0.f;
+    }
+    const int dq = q >> 2;
+    int a0 = 0, a1 = 0, a5 = 0, a6 = 0;
+    if (MODE != HEAD_SAMPLE && X.act) a0 = X.arow[0], a1 = X.arow[1 + dq], a5 = X.arow[5], a6 = X.arow[6];
+    headField<MODE, 1, 16>(X, lane, l + 0, set + 0, j[0], q, 0, X.w0, a0);
+    headField<MODE, 1, 4>(X, lane, l + 1, set + 1, j[1], q & 3, 1 + dq, X.wd, a1);
+    headField<MODE, 1, 16>(X, lane, l + 2, set + 2, j[2], q, 5, X.w5, a5);
+    headField<MODE, 4, 16>(X, lane, l + 3, set + 3, j[3], 4 * q, 6, X.w6, a6);
+}
+
+// nw words of a chunk to global memory as dwordx4 where whole vectors lie inside it: LDS word t <-> gp[t], the
+// chunk at t in [a, a + nw) with gp 16-byte aligned (a = the chunk's word offset in its vector).  lds null: zeros.
+DEV void headFlush(const int32_t* lds, int32_t* gp, int a, int nw, int lane) {
+    const int nv = (a + nw + 3) >> 2;
+    for (int v = lane; v < nv; v += 64) {
+        const int t = 4 * v;
+        const int4 x = lds ? ((const int4*)lds)[v] : make_int4(0, 0, 0, 0);
+        if (t >= a && t + 4 <= a + nw) {
+            ((int4*)gp)[v] = x;
+        } else {
+            const int xs[4] = {x.x, x.y, x.z, x.w};
+#pragma unroll
+            for (int k = 0; k < 4; k++)
+                if (t + k >= a && t + k < a + nw) gp[t + k] = xs[k];
+        }
+    }
+}
+
+// One wave per row.  Per 64 cells: the candidate bits (source bits, or mask byte 0) as one ballot; SAMPLE / GRAD
+// compose the chunk's action / gradient rows in zeroed LDS and store them with dwordx4, a chunk without a
+// candidate as plain zero stores.  The row's log-probability and entropy are per-lane partial sums added up by one
+// DPP chain at the end: a fixed order, no atomics.
+template <int MODE>
+__global__ __launch_bounds__(64) void k_head(HeadParams Q) {
+    __shared__ __align__(16) int32_t sbuf[(MODE == HEAD_GRAD ? 64 * HEAD_MAX_LOGITS : MODE == HEAD_SAMPLE ? 64 * 7 : 0) + 8];
+    const int lane = (int)threadIdx.x, row = (int)blockIdx.x, KL = Q.K - 1;
+    const int RW = MODE == HEAD_GRAD ? KL : 7;  // words per cell of what this mode writes
+    const size_t cell0 = (size_t)row * Q.HW;
+    const uint32_t* src = (MODE == HEAD_SAMPLE && Q.source) ? Q.source + (size_t)row * ((Q.HW + 31) / 32) : nullptr;
+    int32_t* out = MODE == HEAD_GRAD ? (int32_t*)Q.grad : Q.actions;
+    HeadCell X;
+    X.lp = X.ent = 0.0;
+    X.glp = X.gent = 0.f;
+    if (MODE == HEAD_GRAD) {
+        if (Q.g_logprob) X.glp = Q.g_logprob[row];
+        if (Q.g_entropy) X.gent = Q.g_entropy[row];
+    }
+    for (int c0 = 0; c0 < Q.HW; c0 += 64) {
+        const int ncell = min(64, Q.HW - c0), c = c0 + lane;
+        bool cand = false;
+        if (c < Q.HW) cand = src ? ((src[c >> 5] >> (c & 31)) & 1u) != 0 : Q.masks[(cell0 + c) * Q.K] != 0;
+        uint64_t m = ballot(cand);
+        int32_t* gp = nullptr;
+        int a = 0, nw = 0;
+        if (MODE != HEAD_SCORE) {
+            int32_t* p = out + (cell0 + c0) * RW;
+            a = (int)(((uintptr_t)p >> 2) & 3);
+            gp = p - a;
+            nw = ncell * RW;
+            if (m == 0) {
+                headFlush(nullptr, gp, a, nw, lane);
+                continue;
+            }
+            for (int v = lane; v < ((a + nw + 3) >> 2); v += 64) ((int4*)sbuf)[v] = make_int4(0, 0, 0, 0);
+            __syncthreads();
+        } else if (m == 0) {
+            continue;
+        }
+        while (m) {  // four candidate cells per round, the g-th to row g
+            int cl = -1;
+#pragma unroll
+            for (int g = 0; g < 4; g++)
+                if (m) {
+                    const int b = __builtin_ctzll(m);
+                    m &= m - 1;
+                    cl = (lane >> 4) == g ? b : cl;
+                }
+            X.act = cl >= 0;
+            const size_t cell = cell0 + c0 + (cl >= 0 ? cl : 0);
+            X.lrow = Q.logits + cell * KL;
+            X.mrec = Q.masks + cell * Q.K;
+            X.arow = Q.actions + cell * 7;
+            X.srow = sbuf + a + (cl >= 0 ? cl : 0) * 7;
+            X.grow = (float*)sbuf + a + (cl >= 0 ? cl : 0) * KL;
+            if (MODE == HEAD_SAMPLE) {
+                const uint32_t sid = Q.slot_id_base + (uint32_t)row, cc = (uint32_t)(c0 + (cl >= 0 ? cl : 0));
+                uint32_t c1[4] = {sid, Q.step, cc, HEAD_TAG}, c2[4] = {sid, Q.step, cc, HEAD_TAG + 1u};
+                philox(c1, (uint32_t)Q.seed, (uint32_t)(Q.seed >> 32));
+                philox(c2, (uint32_t)Q.seed, (uint32_t)(Q.seed >> 32));
+                // eight words, field f's uniform from word f; the lane's direction field is 1 + its quad
+                const uint32_t p1 = c1[1], p2 = c1[2], p3 = c1[3], p4 = c2[0];
+                const int dq = (lane >> 2) & 3;
+                X.w0 = c1[0];
+                X.wd = dq == 0 ? p1 : dq == 1 ? p2 : dq == 2 ? p3 : p4;
+                X.w5 = c2[1];
+                X.w6 = c2[2];
+            }
+            headCell<MODE>(X, Q, lane);
+        }
+        if (MODE != HEAD_SCORE) {
+            __syncthreads();
+            headFlush(sbuf, gp, a, nw, lane);
+            __syncthreads();
+        }
+    }
+    if (MODE != HEAD_GRAD) {
+        const float lp = (float)waveSumD(X.lp), ent = (float)waveSumD(X.ent);
+        if (lane == 0) {
+            if (Q.logprob) Q.logprob[row] = lp;
+            if (Q.entropy) Q.entropy[row] = ent;
+        }
+    }
+}
+
 #ifdef MRTS_LANE_AUDIT
 // the audit's negative control: a readlane of lane 40 from a branch only lanes 0..31 take
 __global__ __launch_bounds__(64) void k_lane_audit_probe(int32_t* out) {
@@ -7089,6 +7404,16 @@ hipError_t launchPolicy(const PolicyParams& Q, hipStream_t stream, bool* prevWri
         hipLaunchKernelGGL(k_policy_tiled, grid, block, 0, stream, Q);
     else
         hipLaunchKernelGGL(k_policy, grid, block, 0, stream, Q);
+    return hipGetLastError();
+}
+
+// mode: HEAD_SAMPLE / HEAD_SCORE / HEAD_GRAD; one 64-lane block per row (the host checked K - 1 <= HEAD_MAX_LOGITS)
+hipError_t launchHead(int mode, const HeadParams& Q, hipStream_t stream) {
+    if (Q.n_rows <= 0) return hipSuccess;
+    const dim3 grid((unsigned)Q.n_rows), block(64);
+    if (mode == HEAD_SAMPLE) hipLaunchKernelGGL(k_head<HEAD_SAMPLE>, grid, block, 0, stream, Q);
+    else if (mode == HEAD_SCORE) hipLaunchKernelGGL(k_head<HEAD_SCORE>, grid, block, 0, stream, Q);
+    else hipLaunchKernelGGL(k_head<HEAD_GRAD>, grid, block, 0, stream, Q);
     return hipGetLastError();
 }
 }  // namespace mrts

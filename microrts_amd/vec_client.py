@@ -751,6 +751,27 @@ class DeviceVecEnv:
         self._policy_out, self._policy_version = out, out._version
         return out
 
+    def sample_actions(self, logits, seed, step, out=None, stream=None):
+        """The masked policy head (mrts_policy_head_sample_dev; policy_head.py): action rows drawn from `logits`
+        (float32 [slots][H*W][K-1]) under env.masks, the candidate cells taken from env.source when it exists.
+        Returns (actions, logprob, entropy): `out` (default env.actions, every row written) and float32 [slots]
+        sums over each slot's candidate cells.  Philox counters (slot id, step, cell): the same seed, step and
+        logits give the same rows."""
+        from . import policy_head
+
+        h, T = self._h, self.torch
+        if self.masks is None:
+            raise ValueError("sample_actions needs the masks (with_masks=True)")
+        out = self.actions if out is None else out
+        policy_head.check_head_args(self, logits, self.masks, out, n=h.S, actions_name="out")
+        logprob = T.empty(h.S, dtype=T.float32, device=self.device)
+        entropy = T.empty(h.S, dtype=T.float32, device=self.device)
+        _lib.check(h.L.mrts_policy_head_sample_dev(h.h, self._p(logits), self._p(self.masks), self._p(self.source), seed, step,
+                                                   self._p(out), self._p(logprob), self._p(entropy), self._s(stream)))
+        # the library dropped its delta bases (as mrts_policy_invalidate): no tensor holds a tracked policy output
+        self._policy_out, self._policy_version = None, -1
+        return out, logprob, entropy
+
     def synchronize(self):
         self.torch.cuda.current_stream(self.device).synchronize()
 

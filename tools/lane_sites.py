@@ -66,6 +66,19 @@ WHY = {
     "balancePerm": "the last wave of an XCD class sorts in uniform flow (`if (ballot(!ok)) return` is uniform); "
                    "sum is each lane's 4-bin total",
     "k_policy_delta": "kernel level, before any divergence: every lane's popc(dirty)",
+    "dppF": "policy head helper: one float DPP step — called only from segMax / segSum / segScan and "
+            "headField's exclusive shift, each of which checks the whole wave (LANE_AUDIT_WAVE)",
+    "segMax": "policy head: DPP maximum over a quad / 16-lane row; headField calls it in uniform flow (k_head's loops "
+              "test ballots and wave-uniform counts) with a select defined on every lane (-inf without a set bit)",
+    "segSum": "policy head: as segMax, the operand a sum of selects (0 on lanes without a set bit or without a cell)",
+    "segScan": "policy head: DPP running sum inside a quad / row, same call sites and operand as segSum",
+    "headField": "policy head: the row_shr:1 of the running sum and the ballots sit outside every lane test; the "
+                 "lane tests that follow (`ql == pick`, `set[k]`) only store or accumulate on their own lane",
+    "dppD": "policy head helper: a double's two halves through one DPP step each — called only from waveSumD",
+    "waveSumD": "policy head helper: wave_reduce's DPP chain and lane-63 read on doubles; its one caller is k_head",
+    "k_head": "policy head: the kernel's last statement, after its chunk loop (whose `continue`, `while (m)` and "
+              "bounds test ballots and kernel arguments: uniform); lp / ent are per-lane partial sums initialised to "
+              "0 on every lane",
     "k_lane_audit_probe": "the audit build's negative control (reads lane 40 from a branch only lanes 0-31 take)",
     "lrClosest": "LightRush: wave_min after the per-lane `for (o = lid() ...)` loop has reconverged; `best` starts at "
                  "INF on every lane; every caller passes wave-uniform arguments from uniform flow",
@@ -93,7 +106,8 @@ def sites():
         if "#define" in l or "DEV int rl(" in l or "DEV int rlAudit" in l:
             continue
         code = l.split("//")[0]
-        if re.search(r"\brl\(|\bwave_(sum|min|incl_sum)\s*\(|\bwave_reduce\s*<|update_dpp\(|\bquadOr\(", code):
+        if re.search(r"\brl\(|\bwave_(sum|min|incl_sum)\s*\(|\bwave_reduce\s*<|update_dpp\(|\bquadOr\(|\bdppF\s*<|\bseg(Max|Sum|Scan)\s*<|"
+                     r"\bdppD\s*<|\bwaveSumD\(", code):
             out.append((i, fn, l.strip()))
     return out
 
