@@ -379,6 +379,50 @@ int mrts_policy_head_score_dev(mrts_env* env, int32_t n_rows, const float* d_log
 int mrts_policy_head_grad_dev(mrts_env* env, int32_t n_rows, const float* d_logits, const uint8_t* d_masks,
                               const int32_t* d_actions, const float* d_g_logprob, const float* d_g_entropy,
                               float* d_grad_logits, void* stream);
+/* Packed policy rows: what a rollout keeps of a row's masks and action rows for the update — its candidate cells
+ * only (a dense row is H*W * (K + 28) bytes, almost all of them zero).  A packed row is 1 + cap * 5 uint32 words
+ * (mrts_policy_head_packed_words), 1 <= cap <= H*W (cap = H*W never overflows):
+ *   word 0: the row's candidate count n (the true count, also when n > cap);
+ *   then the first min(n, cap) candidates in ascending cell order, 5 words each:
+ *     word 0: the cell index;
+ *     word 1: the seven action components, component f in bits [s_f, s_f + b_f) with
+ *             (s_f, b_f) = (0,3) (3,3) (6,3) (9,3) (12,3) (15,5) (20,7) for f = 0..6, bits 27..31 zero; a component
+ *             c is stored as c when 0 <= c < 2^b_f - 1 and as 2^b_f - 1 ("off its field") otherwise (negative and
+ *             huge values included) — 2^b_f - 1 is beyond every field's width (6, 4, 4, 4, 4, <= 16, <= 64), so a
+ *             component outside its field's set bits stays outside them;
+ *     words 2..4: the K mask bits, bit j of the 96 (word 2 + j / 32, bit j % 32) set <=> mask byte j != 0; bits
+ *             K..95 zero;
+ *   every word after the last stored candidate is zero (the same inputs give the same bytes).
+ * mrts_policy_head_pack_dev: packs n_rows rows of d_masks [n_rows][H*W][K] and d_actions [n_rows][H*W][7] into
+ * d_packed [n_rows][1 + cap * 5], every word written, in one launch.  Candidates from d_source (as
+ * mrts_policy_head_sample_dev) or, d_source NULL, from mask byte 0; only the candidates' mask records and action
+ * rows are read.  A row of more than cap candidates keeps its count and its first cap candidates, and adds one to
+ * the handle's overflow counter.
+ * mrts_policy_head_pack_status: *overflow_rows = the rows the pack calls since the last status call cut at cap;
+ * clears the counter.  Synchronises (as mrts_render_status).
+ * mrts_policy_head_unpack_dev: the canonical dense form of n_rows packed rows, every byte of d_masks_out
+ * [n_rows][H*W][K] and d_actions_out [n_rows][H*W][7] written: mask bytes 0 / 1, components that were off their
+ * field -1, non-candidate cells zero.
+ * mrts_policy_head_score_packed_dev / _grad_packed_dev: mrts_policy_head_score_dev / _grad_dev with the masks and
+ * action rows read from packed rows — the same bytes out as the dense calls on the rows that were packed (the same
+ * terms added in the same order).  d_logits and d_grad_logits stay dense, [n_rows][H*W][K-1].
+ * d_packed holds n_packed rows.  Row r of the call works packed row d_index[r] (int32 [n_rows], repeats allowed),
+ * or packed row r when d_index is NULL (then n_packed >= n_rows).  An index outside [0, n_packed) faults nothing:
+ * score and gradient give NaN for that row, unpack gives zeros.  A packed row whose count exceeds cap gives NaN
+ * log-probability, entropy and gradient row (unpack: its first cap candidates); other rows are not affected.
+ * -EINVAL: as the dense calls, or cap < 1, cap > H*W, n_packed < 1; -ENOTSUP: a bot-only or forward-model handle. */
+int32_t mrts_policy_head_packed_words(const mrts_env* env, int32_t cap);
+int mrts_policy_head_pack_dev(mrts_env* env, int32_t n_rows, const uint8_t* d_masks, const uint32_t* d_source,
+                              const int32_t* d_actions, int32_t cap, uint32_t* d_packed, void* stream);
+int mrts_policy_head_pack_status(mrts_env* env, int64_t* overflow_rows);
+int mrts_policy_head_unpack_dev(mrts_env* env, int32_t n_rows, const uint32_t* d_packed, int32_t n_packed, int32_t cap,
+                                const int32_t* d_index, uint8_t* d_masks_out, int32_t* d_actions_out, void* stream);
+int mrts_policy_head_score_packed_dev(mrts_env* env, int32_t n_rows, const float* d_logits, const uint32_t* d_packed,
+                                      int32_t n_packed, int32_t cap, const int32_t* d_index, float* d_logprob,
+                                      float* d_entropy, void* stream);
+int mrts_policy_head_grad_packed_dev(mrts_env* env, int32_t n_rows, const float* d_logits, const uint32_t* d_packed,
+                                     int32_t n_packed, int32_t cap, const int32_t* d_index, const float* d_g_logprob,
+                                     const float* d_g_entropy, float* d_grad_logits, void* stream);
 /* Optional compact output of every mask write: mask slot 0 ("own unit without an action here") as
  * bits, uint32 [n_slots][ceil(H*W/32)] (sticky; NULL disables).  mrts_policy_dev uses it, when
  * given, to read only the candidate cells' mask rows. */

@@ -43,6 +43,7 @@ hipError_t phaseSpans(unsigned long long* out, int n);
 #endif
 hipError_t launchPolicy(const PolicyParams& Q, hipStream_t stream, bool* prevWritten);
 hipError_t launchHead(int mode, const HeadParams& Q, hipStream_t stream);
+hipError_t launchHeadPacked(int mode, const HeadPackedParams& P, hipStream_t stream);
 hipError_t launchWiden(const uint8_t* in, int32_t* out, size_t n, hipStream_t stream);
 hipError_t launchOneHot(const int32_t* obs, uint8_t* out, int n_slots, int HW, int C, int ntypes, hipStream_t stream);
 hipError_t prepareLds(size_t bytes);
@@ -506,6 +507,7 @@ struct mrts_env {
     int32_t* d_poPrev = nullptr;
     uint32_t* d_prioTab = nullptr;  // multi-step launches: per-SIMD issue-rank table (KDyn.prio_tab)
     int32_t* d_renderErr = nullptr; // the record renders' overflow flag (mrts_render_status)
+    unsigned long long* d_packOverflow = nullptr;  // rows mrts_policy_head_pack_dev cut at cap (mrts_policy_head_pack_status)
     int32_t* d_bal = nullptr;       // multi-step launches: balanced game placement (KDyn.bal)
     int obsImg = 0;                 // KDyn.obs_img: every observation value fits a byte
     bool exPending[2] = {false, false};  // exDone[b] was recorded by an earlier (eager) exchange call
@@ -1906,6 +1908,143 @@ int mrts_policy_head_grad_dev(mrts_env* env, int32_t n_rows, const float* d_logi
     }
 }
 
+namespace {
+// the packed rows' shared argument checks: the handle as headParams wants it, n_rows rows of H*W cells, 1 <= cap <= H*W
+HeadPackedParams headPackedParams(mrts_env* env, int32_t n_rows, int32_t cap) {
+    if (!env) throw Fail{-EINVAL, "null handle"};
+    if (env->botOnly || env->forwardModel)
+        throw Fail{-ENOTSUP, "the policy head needs a handle that writes masks (not a bot-only or forward-model handle)"};
+    if (n_rows < 0 || (int64_t)n_rows * env->HW >= ((int64_t)1 << 31)) throw Fail{-EINVAL, "n_rows: 0 <= n_rows * H*W < 2^31"};
+    if (cap < 1 || cap > env->HW) throw Fail{-EINVAL, "cap: 1 <= cap <= H*W"};
+    const int nt = env->utt.ntypes, natt = env->K - 23 - nt;
+    if (env->K - 1 > HEAD_MAX_LOGITS || nt > 16 || natt < 0 || natt > 64)
+        throw Fail{-ENOTSUP, "the policy head: at most 16 unit types, 64 attack-window cells and 80 logits per cell"};
+    HeadPackedParams P;
+    std::memset(&P, 0, sizeof(P));
+    P.H.HW = env->HW;
+    P.H.K = env->K;
+    P.H.ntypes = nt;
+    P.H.n_rows = n_rows;
+    P.H.slot_id_base = env->slotIdBase;
+    P.cap = cap;
+    P.words = headPackedWords(cap);
+    return P;
+}
+// packed rows as a score / gradient / unpack call reads them: without an index row r reads packed row r
+void headPackedSource(HeadPackedParams& P, const uint32_t* d_packed, int32_t n_packed, const int32_t* d_index) {
+    if (!d_packed) throw Fail{-EINVAL, "null argument"};
+    if (n_packed < 1 || (!d_index && n_packed < P.H.n_rows)) throw Fail{-EINVAL, "n_packed: at least 1, and n_rows without an index"};
+    if (((uintptr_t)d_packed & 3) || ((uintptr_t)d_index & 3)) throw Fail{-EINVAL, "misaligned buffer"};
+    P.packed = d_packed;
+    P.n_packed = n_packed;
+    P.index = d_index;
+}
+}  // namespace
+
+int32_t mrts_policy_head_packed_words(const mrts_env* env, int32_t cap) {
+    if (!env) return fail(Fail{-EINVAL, "null handle"});
+    if (env->botOnly || env->forwardModel) return fail(Fail{-ENOTSUP, "the policy head needs a handle that writes masks"});
+    if (cap < 1 || cap > env->HW) return fail(Fail{-EINVAL, "cap: 1 <= cap <= H*W"});
+    return headPackedWords(cap);
+}
+
+int mrts_policy_head_pack_dev(mrts_env* env, int32_t n_rows, const uint8_t* d_masks, const uint32_t* d_source,
+                              const int32_t* d_actions, int32_t cap, uint32_t* d_packed, void* stream) {
+    try {
+        HeadPackedParams P = headPackedParams(env, n_rows, cap);
+        if (!d_masks || !d_actions || !d_packed) throw Fail{-EINVAL, "null argument"};
+        if (((uintptr_t)d_source & 3) || ((uintptr_t)d_actions & 3) || ((uintptr_t)d_packed & 3)) throw Fail{-EINVAL, "misaligned buffer"};
+        HIPCHK(hipSetDevice(env->device));
+        if (!env->d_packOverflow) {
+            HIPCHK(hipMalloc(&env->d_packOverflow, 8));
+            HIPCHK(hipMemset(env->d_packOverflow, 0, 8));
+        }
+        P.H.masks = d_masks;
+        P.H.source = d_source;
+        P.H.actions = const_cast<int32_t*>(d_actions);
+        P.packed_out = d_packed;
+        P.overflow = env->d_packOverflow;
+        HIPCHK(launchHeadPacked(HEAD_PACK, P, pickStream(env, stream)));
+        return 0;
+    } catch (const Fail& f) {
+        return fail(f);
+    }
+}
+
+int mrts_policy_head_pack_status(mrts_env* env, int64_t* overflow_rows) {
+    try {
+        if (!env || !overflow_rows) throw Fail{-EINVAL, "null argument"};
+        *overflow_rows = 0;
+        if (!env->d_packOverflow) return 0;
+        HIPCHK(hipSetDevice(env->device));
+        HIPCHK(hipDeviceSynchronize());
+        unsigned long long v = 0;
+        HIPCHK(hipMemcpy(&v, env->d_packOverflow, 8, hipMemcpyDeviceToHost));
+        if (v) HIPCHK(hipMemset(env->d_packOverflow, 0, 8));
+        *overflow_rows = (int64_t)v;
+        return 0;
+    } catch (const Fail& f) {
+        return fail(f);
+    }
+}
+
+int mrts_policy_head_unpack_dev(mrts_env* env, int32_t n_rows, const uint32_t* d_packed, int32_t n_packed, int32_t cap,
+                                const int32_t* d_index, uint8_t* d_masks_out, int32_t* d_actions_out, void* stream) {
+    try {
+        HeadPackedParams P = headPackedParams(env, n_rows, cap);
+        headPackedSource(P, d_packed, n_packed, d_index);
+        if (!d_masks_out || !d_actions_out) throw Fail{-EINVAL, "null argument"};
+        if ((uintptr_t)d_actions_out & 3) throw Fail{-EINVAL, "misaligned buffer"};
+        HIPCHK(hipSetDevice(env->device));
+        P.masks_out = d_masks_out;
+        P.actions_out = d_actions_out;
+        HIPCHK(launchHeadPacked(HEAD_UNPACK, P, pickStream(env, stream)));
+        return 0;
+    } catch (const Fail& f) {
+        return fail(f);
+    }
+}
+
+int mrts_policy_head_score_packed_dev(mrts_env* env, int32_t n_rows, const float* d_logits, const uint32_t* d_packed,
+                                      int32_t n_packed, int32_t cap, const int32_t* d_index, float* d_logprob,
+                                      float* d_entropy, void* stream) {
+    try {
+        HeadPackedParams P = headPackedParams(env, n_rows, cap);
+        headPackedSource(P, d_packed, n_packed, d_index);
+        if (!d_logits) throw Fail{-EINVAL, "null argument"};
+        if (((uintptr_t)d_logits & 3) || ((uintptr_t)d_logprob & 3) || ((uintptr_t)d_entropy & 3)) throw Fail{-EINVAL, "misaligned buffer"};
+        HIPCHK(hipSetDevice(env->device));
+        P.H.logits = d_logits;
+        P.H.logprob = d_logprob;
+        P.H.entropy = d_entropy;
+        HIPCHK(launchHeadPacked(HEAD_SCORE, P, pickStream(env, stream)));
+        return 0;
+    } catch (const Fail& f) {
+        return fail(f);
+    }
+}
+
+int mrts_policy_head_grad_packed_dev(mrts_env* env, int32_t n_rows, const float* d_logits, const uint32_t* d_packed,
+                                     int32_t n_packed, int32_t cap, const int32_t* d_index, const float* d_g_logprob,
+                                     const float* d_g_entropy, float* d_grad_logits, void* stream) {
+    try {
+        HeadPackedParams P = headPackedParams(env, n_rows, cap);
+        headPackedSource(P, d_packed, n_packed, d_index);
+        if (!d_logits || !d_grad_logits) throw Fail{-EINVAL, "null argument"};
+        if (((uintptr_t)d_logits & 3) || ((uintptr_t)d_g_logprob & 3) || ((uintptr_t)d_g_entropy & 3) || ((uintptr_t)d_grad_logits & 3))
+            throw Fail{-EINVAL, "misaligned buffer"};
+        HIPCHK(hipSetDevice(env->device));
+        P.H.logits = d_logits;
+        P.H.g_logprob = d_g_logprob;
+        P.H.g_entropy = d_g_entropy;
+        P.H.grad = d_grad_logits;
+        HIPCHK(launchHeadPacked(HEAD_GRAD, P, pickStream(env, stream)));
+        return 0;
+    } catch (const Fail& f) {
+        return fail(f);
+    }
+}
+
 static void fillResponses(mrts_env* env, mrts_responses* out) {
     const size_t S = (size_t)env->nSlots;
     HIPCHK(hipMemcpyAsync(env->h_obs, env->d_obs, S * env->C * env->HW * 4, hipMemcpyDeviceToHost, env->stream));
@@ -2137,6 +2276,7 @@ void mrts_destroy(mrts_env* env) {
     (void)hipFree(env->d_poPrev);
     (void)hipFree(env->d_prioTab);
     (void)hipFree(env->d_renderErr);
+    (void)hipFree(env->d_packOverflow);
     (void)hipFree(env->d_bal);
     (void)hipFree(env->d_state);
     (void)hipFree(env->d_polPrev);

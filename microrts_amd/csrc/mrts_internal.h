@@ -256,7 +256,7 @@ struct PolicyParams {
 
 // Masked policy head (mrts_policy_head_*_dev): one wave per row of [n_rows][HW] cells.  mode SAMPLE draws
 // `actions` (source optional: the candidate bits), SCORE reads them, GRAD writes `grad` [n_rows][HW][K-1].
-enum : int32_t { HEAD_SAMPLE = 0, HEAD_SCORE = 1, HEAD_GRAD = 2 };
+enum : int32_t { HEAD_SAMPLE = 0, HEAD_SCORE = 1, HEAD_GRAD = 2, HEAD_PACK = 3, HEAD_UNPACK = 4 };
 constexpr int HEAD_MAX_LOGITS = 80;  // K - 1 of the largest table create accepts (8 types, attack range 3)
 struct HeadParams {
     int32_t HW, K, ntypes, n_rows;
@@ -271,6 +271,24 @@ struct HeadParams {
     const float* g_logprob;        // GRAD, optional (zeros): [n_rows]
     const float* g_entropy;        // GRAD, optional (zeros): [n_rows]
     float* grad;                   // GRAD: [n_rows][HW][K-1], every element written
+};
+
+// The packed rollout row (include/mrts.h, "Packed policy rows"): word 0 the candidate count, then per candidate
+// HEAD_CW words: cell, action word, mask bits 0..31, 32..63, 64..95.  Action word: component f at bit
+// HEAD_ACT_SHIFT[f], HEAD_ACT_BITS[f] wide, all ones = off its field.
+constexpr int HEAD_CW = 5;
+constexpr int HEAD_ACT_SHIFT[7] = {0, 3, 6, 9, 12, 15, 20};
+constexpr int HEAD_ACT_BITS[7] = {3, 3, 3, 3, 3, 5, 7};
+constexpr int headPackedWords(int cap) { return 1 + cap * HEAD_CW; }
+struct HeadPackedParams {
+    HeadParams H;                  // the dense modes' fields; pack reads masks / source / actions, the others logits
+    int32_t cap, words, n_packed;  // words = headPackedWords(cap); n_packed: rows of `packed` (an index is clamped)
+    const uint32_t* packed;        // score / grad / unpack: [n_packed][words]
+    uint32_t* packed_out;          // pack: [n_rows][words], every word written
+    const int32_t* index;          // score / grad / unpack, optional: row r works packed row index[r]
+    uint8_t* masks_out;            // unpack: [n_rows][HW][K]
+    int32_t* actions_out;          // unpack: [n_rows][HW][7]
+    unsigned long long* overflow;  // pack: rows with more than cap candidates (mrts_policy_head_pack_status)
 };
 
 }  // namespace mrts

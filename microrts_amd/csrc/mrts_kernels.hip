@@ -6727,6 +6727,258 @@ __global__ __launch_bounds__(64) void k_head(HeadParams Q) {
     }
 }
 
+// ---- Packed policy rows (include/mrts.h): the candidates of a row as HEAD_CW words each, for rollout storage ----
+// an action component's code: itself inside [0, off), else off (off = all ones of the component's bits, beyond
+// every field's width: a component the dense score finds outside its field's set bits stays outside them)
+DEV uint32_t headActWord(const int32_t* a) {
+    uint32_t w = 0;
+#pragma unroll
+    for (int f = 0; f < 7; f++) {
+        const uint32_t off = (1u << HEAD_ACT_BITS[f]) - 1u, v = (uint32_t)a[f];
+        w |= (v < off ? v : off) << HEAD_ACT_SHIFT[f];
+    }
+    return w;
+}
+DEV int32_t headActComp(uint32_t w, int f) {
+    int sh = 0, bits = 0;
+#pragma unroll
+    for (int k = 0; k < 7; k++)
+        if (k == f) sh = HEAD_ACT_SHIFT[k], bits = HEAD_ACT_BITS[k];
+    const uint32_t off = (1u << bits) - 1u, v = (w >> sh) & off;
+    return v == off ? -1 : (int32_t)v;
+}
+// four mask bits as four 0 / 1 bytes
+DEV uint32_t headSpread4(uint32_t b) { return (b & 1u) | ((b & 2u) << 7) | ((b & 4u) << 14) | ((b & 8u) << 21); }
+DEV uint32_t headBits4(uint32_t b0, uint32_t b1, uint32_t b2, int w) {  // bits 4w..4w+3 of the 96
+    const uint32_t x = w < 8 ? b0 : w < 16 ? b1 : b2;
+    return (x >> (4 * (w & 7))) & 15u;
+}
+// the packed row a block works: packed row index[row] (row without an index); ok false when that is out of range
+DEV const uint32_t* headPackedRow(const HeadPackedParams& P, int row, bool& ok) {
+    const int64_t pr = P.index ? (int64_t)P.index[row] : (int64_t)row;
+    ok = pr >= 0 && pr < (int64_t)P.n_packed;
+    return P.packed + (size_t)(ok ? pr : 0) * (size_t)P.words;
+}
+constexpr int HEAD_STG = 128;  // candidates k_head_pack stages in LDS between flushes (a chunk adds at most 64)
+
+// One wave per row.  Per 64 cells the candidate bits (source bits, or mask byte 0) as one ballot, as k_head finds
+// them; a candidate's slot in the row is the count before its chunk plus the candidates below its lane.  The
+// candidate's own lane adds its cell and action word, the wave reads its mask record (two bytes per lane) and two
+// ballots give the bits.  The row is composed in LDS and stored with dwordx4 (headFlush), count word and zero tail
+// included; a row of more than HEAD_STG candidates flushes in between.
+__global__ __launch_bounds__(64) void k_head_pack(HeadPackedParams P) {
+    __shared__ __align__(16) int32_t stg[4 + 1 + HEAD_STG * HEAD_CW + 3];
+    const HeadParams& Q = P.H;
+    const int lane = (int)threadIdx.x, row = (int)blockIdx.x;
+    const size_t cell0 = (size_t)row * Q.HW;
+    const uint32_t* src = Q.source ? Q.source + (size_t)row * ((Q.HW + 31) / 32) : nullptr;
+    int32_t* orow = (int32_t*)P.packed_out + (size_t)row * (size_t)P.words;
+    // staged: the row's words [r0, r0 + rn) at stg[a + (word - r0)], orow + r0 - a 16-byte aligned
+    int total = 0, r0 = 0, rn = 1, a = (int)(((uintptr_t)orow >> 2) & 3);
+    for (int c0 = 0; c0 < Q.HW; c0 += 64) {
+        const int c = c0 + lane;
+        bool cand = false;
+        if (c < Q.HW) cand = src ? ((src[c >> 5] >> (c & 31)) & 1u) != 0 : Q.masks[(cell0 + c) * Q.K] != 0;
+        const uint64_t m = ballot(cand);
+        if (m == 0) continue;
+        const int nc = __builtin_popcountll(m), keep = max(0, min(nc, P.cap - total));
+        total += nc;
+        if (keep == 0) continue;
+        if (rn + keep * HEAD_CW > 1 + HEAD_STG * HEAD_CW) {  // word 0 waits for the count
+            __syncthreads();
+            if (r0 == 0) headFlush(stg, orow - a, a + 1, rn - 1, lane);
+            else headFlush(stg, orow + r0 - a, a, rn, lane);
+            __syncthreads();
+            r0 += rn;
+            rn = 0;
+            a = (int)(((uintptr_t)(orow + r0) >> 2) & 3);
+        }
+        int32_t* s = stg + a + rn;
+        const int pos = lanes_below(m);
+        if (cand && pos < keep) {
+            s[pos * HEAD_CW] = c;
+            s[pos * HEAD_CW + 1] = (int32_t)headActWord(Q.actions + (cell0 + c) * 7);
+        }
+        uint64_t mm = m;
+        for (int k = 0; k < keep; k++) {
+            const uint8_t* rec = Q.masks + (cell0 + c0 + __builtin_ctzll(mm)) * Q.K;
+            mm &= mm - 1;
+            const bool v0 = lane < Q.K && rec[lane < Q.K ? lane : 0] != 0;
+            const bool v1 = lane + 64 < Q.K && rec[lane + 64 < Q.K ? lane + 64 : 0] != 0;
+            const uint64_t b0 = ballot(v0), b1 = ballot(v1);
+            if (lane == 0) {
+                s[k * HEAD_CW + 2] = (int32_t)(uint32_t)b0;
+                s[k * HEAD_CW + 3] = (int32_t)(uint32_t)(b0 >> 32);
+                s[k * HEAD_CW + 4] = (int32_t)(uint32_t)b1;
+            }
+        }
+        rn += keep * HEAD_CW;
+    }
+    if (lane == 0) {
+        if (r0 == 0) stg[a] = total;
+        else orow[0] = total;
+        if (total > P.cap) atomicAdd(P.overflow, 1ull);
+    }
+    __syncthreads();
+    headFlush(stg, orow + r0 - a, a, rn, lane);
+    const int t0 = r0 + rn, a2 = (int)(((uintptr_t)(orow + t0) >> 2) & 3);
+    headFlush(nullptr, orow + t0 - a2, a2, P.words - t0, lane);
+}
+
+// nb bytes of a chunk to global memory as dwordx4 where whole vectors lie inside it: LDS byte t <-> gp[t], the chunk
+// at t in [a, a + nb) with gp 16-byte aligned.  lds null: zeros.
+DEV void headFlushBytes(const uint8_t* lds, uint8_t* gp, int a, int nb, int lane) {
+    const int nv = (a + nb + 15) >> 4;
+    for (int v = lane; v < nv; v += 64) {
+        const int t = 16 * v;
+        if (t >= a && t + 16 <= a + nb) {
+            ((int4*)gp)[v] = lds ? ((const int4*)lds)[v] : make_int4(0, 0, 0, 0);
+        } else {
+            for (int k = 0; k < 16; k++)
+                if (t + k >= a && t + k < a + nb) gp[t + k] = lds ? lds[t + k] : (uint8_t)0;
+        }
+    }
+}
+
+// The canonical dense form of packed rows, one wave per row: per 64 cells the chunk's mask records (0 / 1 bytes)
+// and action rows composed in zeroed LDS from the row's candidates of that chunk, then stored whole — every byte of
+// both outputs is written.  A count above cap gives its first cap candidates; a cell outside the map or out of
+// order and an index outside the packed rows give nothing.
+__global__ __launch_bounds__(64) void k_head_unpack(HeadPackedParams P) {
+    __shared__ __align__(16) uint8_t smask[16 + 64 * (HEAD_MAX_LOGITS + 1) + 16];
+    __shared__ __align__(16) int32_t sact[4 + 64 * 7 + 4];
+    const HeadParams& Q = P.H;
+    const int lane = (int)threadIdx.x, row = (int)blockIdx.x;
+    const size_t cell0 = (size_t)row * Q.HW;
+    bool ok;
+    const uint32_t* prow = headPackedRow(P, row, ok);
+    const uint32_t n = ok ? min(prow[0], (uint32_t)P.cap) : 0u;
+    uint32_t i0 = 0;
+    for (int c0 = 0; c0 < Q.HW; c0 += 64) {
+        const int ncell = min(64, Q.HW - c0);
+        uint8_t* mp = P.masks_out + (cell0 + c0) * Q.K;
+        int32_t* ap = P.actions_out + (cell0 + c0) * 7;
+        const int am = (int)((uintptr_t)mp & 15), aa = (int)(((uintptr_t)ap >> 2) & 3);
+        const int nb = ncell * Q.K, nw = ncell * 7;
+        for (int v = lane; v < ((am + nb + 15) >> 4); v += 64) ((int4*)smask)[v] = make_int4(0, 0, 0, 0);
+        for (int v = lane; v < ((aa + nw + 3) >> 2); v += 64) ((int4*)sact)[v] = make_int4(0, 0, 0, 0);
+        __syncthreads();
+        while (i0 < n) {
+            const uint32_t* cw = prow + 1 + (size_t)i0 * HEAD_CW;
+            const uint32_t cell = cw[0];
+            if ((cell >> 6) != (uint32_t)(c0 >> 6)) break;
+            i0++;
+            if (cell >= (uint32_t)Q.HW) continue;
+            const int cl = (int)(cell & 63u);
+            const uint32_t aw = cw[1], b0 = cw[2], b1 = cw[3], b2 = cw[4];
+            if (lane < Q.K) smask[am + cl * Q.K + lane] = (uint8_t)((lane < 32 ? b0 >> lane : b1 >> (lane - 32)) & 1u);
+            if (lane + 64 < Q.K) smask[am + cl * Q.K + lane + 64] = (uint8_t)((b2 >> lane) & 1u);
+            if (lane < 7) sact[aa + cl * 7 + lane] = headActComp(aw, lane);
+        }
+        __syncthreads();
+        headFlushBytes(smask, mp - am, am, nb, lane);
+        headFlush(sact, ap - aa, aa, nw, lane);
+        __syncthreads();
+    }
+}
+
+// k_head's SCORE / GRAD on packed rows: logits row r against packed row index[r].  The rounds are k_head's — up to
+// four consecutive candidates of one 64-cell chunk (cell >> 6; the row is sorted by cell), the g-th to DPP row g —
+// so every lane's partial sums take the same terms in the same order and the results equal the dense kernels' bit
+// for bit.  Each round expands its candidates' mask bits to 0 / 1 bytes and their action words to components in
+// LDS, where headCell reads them as it reads the dense tensors.  The count and the candidate words are read at
+// wave-uniform addresses inside the row (clamped to cap), so the first round's words load with the count.  A row
+// whose count exceeds cap, or whose index is outside the packed rows, is NaN: logprob, entropy, gradient row.
+template <int MODE>
+__global__ __launch_bounds__(64) void k_head_packed(HeadPackedParams P) {
+    constexpr int XW = (HEAD_MAX_LOGITS + 1 + 3) / 4 + 7;  // per DPP row: the mask bytes, then the action row
+    __shared__ __align__(16) int32_t sbuf[(MODE == HEAD_GRAD ? 64 * HEAD_MAX_LOGITS : 0) + 8];
+    __shared__ __align__(16) uint32_t sexp[4 * XW];
+    const HeadParams& Q = P.H;
+    const int lane = (int)threadIdx.x, row = (int)blockIdx.x, KL = Q.K - 1, g = lane >> 4, q = lane & 15;
+    const size_t cell0 = (size_t)row * Q.HW;
+    bool ok;
+    const uint32_t* prow = headPackedRow(P, row, ok);
+    const uint32_t n = prow[0], last = (uint32_t)P.cap - 1u;
+    uint32_t i0 = 0, cc = prow[1];  // cc: the cell of candidate i0
+    if (!ok || n > (uint32_t)P.cap) {
+        const float nan = __int_as_float(0x7FC00000);
+        if (MODE == HEAD_GRAD) {
+            for (size_t t = lane; t < (size_t)Q.HW * KL; t += 64) Q.grad[cell0 * KL + t] = nan;
+        } else if (lane == 0) {
+            if (Q.logprob) Q.logprob[row] = nan;
+            if (Q.entropy) Q.entropy[row] = nan;
+        }
+        return;
+    }
+    HeadCell X;
+    X.lp = X.ent = 0.0;
+    X.glp = X.gent = 0.f;
+    X.srow = nullptr;
+    X.w0 = X.wd = X.w5 = X.w6 = 0;
+    if (MODE == HEAD_GRAD) {
+        if (Q.g_logprob) X.glp = Q.g_logprob[row];
+        if (Q.g_entropy) X.gent = Q.g_entropy[row];
+    }
+    uint32_t* xr = sexp + g * XW;
+    for (int c0 = 0; c0 < Q.HW; c0 += 64) {
+        const uint32_t chunk = (uint32_t)(c0 >> 6);
+        const bool has = i0 < n && (cc >> 6) == chunk;
+        int32_t* gp = nullptr;
+        int a = 0, nw = 0;
+        if (MODE == HEAD_GRAD) {
+            int32_t* p = (int32_t*)Q.grad + (cell0 + c0) * KL;
+            a = (int)(((uintptr_t)p >> 2) & 3);
+            gp = p - a;
+            nw = min(64, Q.HW - c0) * KL;
+            if (!has) {
+                headFlush(nullptr, gp, a, nw, lane);
+                continue;
+            }
+            for (int v = lane; v < ((a + nw + 3) >> 2); v += 64) ((int4*)sbuf)[v] = make_int4(0, 0, 0, 0);
+        } else if (!has) {
+            if (i0 >= n) break;
+            continue;
+        }
+        while (i0 < n && (cc >> 6) == chunk) {  // four candidate cells per round, the g-th to row g
+            uint32_t cl[5];
+#pragma unroll
+            for (int k = 0; k < 5; k++) cl[k] = prow[1 + (size_t)min(i0 + k, last) * HEAD_CW];
+            int take = 1;
+#pragma unroll
+            for (int k = 1; k < 4; k++)
+                if (take == k && i0 + k < n && (cl[k] >> 6) == chunk) take = k + 1;
+            const uint32_t* cw = prow + 1 + (size_t)min(i0 + g, last) * HEAD_CW;
+            const uint32_t cell = cw[0], aw = cw[1], b0 = cw[2], b1 = cw[3], b2 = cw[4];
+            X.act = g < take && cell < (uint32_t)Q.HW;
+            const uint32_t cs = X.act ? cell : 0u;
+            __syncthreads();  // the previous round has read its expansion
+            for (int w = q; w < (Q.K + 3) / 4; w += 16) xr[w] = headSpread4(headBits4(b0, b1, b2, w));
+            if (q < 7) xr[XW - 7 + q] = (uint32_t)headActComp(aw, q);
+            __syncthreads();
+            X.lrow = Q.logits + (cell0 + cs) * KL;
+            X.mrec = (const uint8_t*)xr;
+            X.arow = (const int32_t*)(xr + XW - 7);
+            X.grow = (float*)sbuf + a + (cs & 63u) * KL;
+            headCell<MODE>(X, Q, lane);
+            i0 += take;
+            cc = take == 1 ? cl[1] : take == 2 ? cl[2] : take == 3 ? cl[3] : cl[4];
+        }
+        if (MODE == HEAD_GRAD) {
+            __syncthreads();
+            headFlush(sbuf, gp, a, nw, lane);
+            __syncthreads();
+        }
+    }
+    if (MODE != HEAD_GRAD) {
+        const float lp = (float)waveSumD(X.lp), ent = (float)waveSumD(X.ent);
+        if (lane == 0) {
+            if (Q.logprob) Q.logprob[row] = lp;
+            if (Q.entropy) Q.entropy[row] = ent;
+        }
+    }
+}
+
 #ifdef MRTS_LANE_AUDIT
 // the audit's negative control: a readlane of lane 40 from a branch only lanes 0..31 take
 __global__ __launch_bounds__(64) void k_lane_audit_probe(int32_t* out) {
@@ -7414,6 +7666,17 @@ hipError_t launchHead(int mode, const HeadParams& Q, hipStream_t stream) {
     if (mode == HEAD_SAMPLE) hipLaunchKernelGGL(k_head<HEAD_SAMPLE>, grid, block, 0, stream, Q);
     else if (mode == HEAD_SCORE) hipLaunchKernelGGL(k_head<HEAD_SCORE>, grid, block, 0, stream, Q);
     else hipLaunchKernelGGL(k_head<HEAD_GRAD>, grid, block, 0, stream, Q);
+    return hipGetLastError();
+}
+
+// the packed rows' kernels, one 64-lane block per row: HEAD_PACK / HEAD_UNPACK, or HEAD_SCORE / HEAD_GRAD on packed rows
+hipError_t launchHeadPacked(int mode, const HeadPackedParams& P, hipStream_t stream) {
+    if (P.H.n_rows <= 0) return hipSuccess;
+    const dim3 grid((unsigned)P.H.n_rows), block(64);
+    if (mode == HEAD_PACK) hipLaunchKernelGGL(k_head_pack, grid, block, 0, stream, P);
+    else if (mode == HEAD_UNPACK) hipLaunchKernelGGL(k_head_unpack, grid, block, 0, stream, P);
+    else if (mode == HEAD_SCORE) hipLaunchKernelGGL(k_head_packed<HEAD_SCORE>, grid, block, 0, stream, P);
+    else hipLaunchKernelGGL(k_head_packed<HEAD_GRAD>, grid, block, 0, stream, P);
     return hipGetLastError();
 }
 }  // namespace mrts

@@ -1,6 +1,9 @@
 """The masked policy head (include/mrts.h, mrts_policy_head_*_dev): between a network's logits
 [rows][H*W][K-1] and the action rows [rows][H*W][7].  DeviceVecEnv.sample_actions draws the rows of a rollout
-step; evaluate_actions scores given rows for the update, differentiable in the logits.
+step; evaluate_actions scores given rows for the update, differentiable in the logits.  A rollout keeps its masks
+and action rows packed (DeviceVecEnv.packed_buffer / pack_step: the candidate cells only), and
+evaluate_actions_packed scores them as they are, through an optional gather index — the same bytes out as
+evaluate_actions on the dense rows.
 
 Per candidate cell (mask slot 0 set) every field with a set mask bit is an independent masked categorical — the
 GridNet factorisation of MicroRTS-Py.  An empty field adds nothing here, where MicroRTS-Py's all-masked
@@ -93,3 +96,138 @@ def evaluate_actions(env, logits, masks, actions):
     if _EVALUATE is None:
         _EVALUATE = _evaluate_fn()
     return _EVALUATE.apply(logits, masks, actions, env)
+
+
+CW = 5  # words per candidate of a packed row (include/mrts.h, "Packed policy rows")
+
+
+def default_cap(env):
+    """The packed rows' default candidate capacity: min(H*W, 64)."""
+    _, H, W, _, _ = env.dims
+    return min(H * W, 64)
+
+
+def packed_words(env, cap=None):
+    """uint32 words of a packed row of at most `cap` candidates (default min(H*W, 64)): 1 + cap * 5."""
+    _, H, W, _, _ = env.dims
+    cap = default_cap(env) if cap is None else cap
+    if not isinstance(cap, int) or isinstance(cap, bool) or cap < 1 or cap > H * W:
+        raise ValueError(f"cap: {cap!r}, expected an int in [1, H*W = {H * W}]")
+    return 1 + cap * CW
+
+
+def _cap_of(env, name, t, cap):
+    """The cap a packed tensor's last dimension stands for; ValueError naming it unless that is 1 + cap * 5."""
+    import torch
+
+    _, H, W, _, _ = env.dims
+    if not isinstance(t, torch.Tensor) or t.dim() < 2:
+        raise ValueError(f"{name}: expected a uint32 tensor [rows][words]")
+    words = t.shape[-1]
+    if cap is None:
+        if words < 1 + CW or (words - 1) % CW or (words - 1) // CW > H * W:
+            raise ValueError(f"{name}: {words} words is not 1 + cap * {CW} for a cap in [1, H*W = {H * W}]")
+        return (words - 1) // CW
+    if words != packed_words(env, cap):
+        raise ValueError(f"{name}: {words} words, expected {packed_words(env, cap)} for cap {cap}")
+    return cap
+
+
+def check_pack_args(env, out, masks, actions, source=None, cap=None):
+    """The argument checks of pack_step (no GPU call): out uint32 [n][words], masks uint8 [n][H][W][K] (or
+    [n][H*W][K]), actions int32 [n][H*W][7], source (optional) int32 [n][ceil(H*W/32)], all contiguous on the env's
+    device, words = 1 + cap * 5.  Returns (n, cap)."""
+    import torch
+
+    _, H, W, _, K = env.dims
+    cap = _cap_of(env, "out", out, cap)
+    if out.dim() != 2:
+        raise ValueError(f"out: shape {tuple(out.shape)}, expected [rows][words]")
+    n = out.shape[0]
+    check_tensor("out", out, torch.uint32, [(n, 1 + cap * CW)], env.device)
+    check_tensor("masks", masks, torch.uint8, [(n, H, W, K), (n, H * W, K)], env.device)
+    check_tensor("actions", actions, torch.int32, [(n, H * W, 7)], env.device)
+    if source is not None:
+        check_tensor("source", source, torch.int32, [(n, (H * W + 31) // 32)], env.device)
+    if n * H * W >= 1 << 31:
+        raise ValueError("out: rows * H*W must be below 2^31")
+    return n, cap
+
+
+def check_packed_args(env, packed, index, rows, cap=None):
+    """The argument checks of the calls that read packed rows (no GPU call): packed uint32 [...][words], contiguous
+    on the env's device; index (optional) int32 [rows]; without an index packed holds `rows` rows.  Returns
+    (packed rows, cap)."""
+    import torch
+
+    _, H, W, _, _ = env.dims
+    cap = _cap_of(env, "packed", packed, cap)
+    check_tensor("packed", packed, torch.uint32, [tuple(packed.shape)], env.device)
+    n_packed = packed.numel() // packed.shape[-1]
+    if n_packed < 1:
+        raise ValueError("packed: no rows")
+    if index is None:
+        if n_packed != rows:
+            raise ValueError(f"packed: {n_packed} rows for {rows} rows of logits (pass an index to gather)")
+    else:
+        check_tensor("index", index, torch.int32, [(rows,)], env.device)
+    if rows * H * W >= 1 << 31:
+        raise ValueError("logits: rows * H*W must be below 2^31")
+    return n_packed, cap
+
+
+def _evaluate_packed_fn():
+    import torch
+
+    class EvaluateActionsPacked(torch.autograd.Function):
+        @staticmethod
+        def forward(ctx, logits, packed, index, env, n_packed, cap):
+            n = logits.shape[0]
+            logprob = torch.empty(n, dtype=torch.float32, device=logits.device)
+            entropy = torch.empty(n, dtype=torch.float32, device=logits.device)
+            h = env._h
+            _lib.check(h.L.mrts_policy_head_score_packed_dev(h.h, n, _p(logits), _p(packed), n_packed, cap, _p(index),
+                                                             _p(logprob), _p(entropy), env._s(None)))
+            ctx.save_for_backward(logits, packed, index)
+            ctx.env, ctx.n_packed, ctx.cap = env, n_packed, cap
+            ctx.set_materialize_grads(False)
+            return logprob, entropy
+
+        @staticmethod
+        def backward(ctx, g_logprob, g_entropy):
+            logits, packed, index = ctx.saved_tensors
+            if not ctx.needs_input_grad[0]:
+                return None, None, None, None, None, None
+            g = [None if t is None else t.to(torch.float32).contiguous() for t in (g_logprob, g_entropy)]
+            grad = torch.empty_like(logits)
+            h = ctx.env._h
+            _lib.check(h.L.mrts_policy_head_grad_packed_dev(h.h, logits.shape[0], _p(logits), _p(packed), ctx.n_packed, ctx.cap,
+                                                            _p(index), _p(g[0]), _p(g[1]), _p(grad), ctx.env._s(None)))
+            return grad, None, None, None, None, None
+
+    return EvaluateActionsPacked
+
+
+_EVALUATE_PACKED = None
+
+
+def evaluate_actions_packed(env, logits, packed, index=None):
+    """evaluate_actions on packed rows (DeviceVecEnv.pack_step): (logprob, entropy), float32 [rows], byte for byte
+    what evaluate_actions gives on the dense masks and action rows that were packed, differentiable in `logits`
+    (float32 [rows][H*W][K-1]; the backward is one launch and writes the dense gradient).  packed: uint32
+    [N][words], or any leading shape (a [T][slots][words] rollout buffer), flattened.  Row r is scored against
+    packed row index[r] (int32 [rows] on the device, repeats allowed: a minibatch needs no copy), or against packed
+    row r without an index (then N = rows).  A packed row that overflowed its cap (DeviceVecEnv.pack_overflow) and
+    an index outside [0, N) give NaN for that row only."""
+    global _EVALUATE_PACKED
+    import torch
+
+    _, H, W, _, K = env.dims
+    if not isinstance(logits, torch.Tensor) or logits.dim() != 3:
+        raise ValueError("logits: expected a float32 tensor [rows][H*W][K-1]")
+    rows = logits.shape[0]
+    check_tensor("logits", logits, torch.float32, [(rows, H * W, K - 1)], env.device)
+    n_packed, cap = check_packed_args(env, packed, index, rows)
+    if _EVALUATE_PACKED is None:
+        _EVALUATE_PACKED = _evaluate_packed_fn()
+    return _EVALUATE_PACKED.apply(logits, packed, index, env, n_packed, cap)

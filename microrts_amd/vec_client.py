@@ -772,6 +772,64 @@ class DeviceVecEnv:
         self._policy_out, self._policy_version = None, -1
         return out, logprob, entropy
 
+    def packed_words(self, cap=None):
+        """uint32 words of a packed row (policy_head.py; include/mrts.h "Packed policy rows") of at most `cap`
+        candidate cells: 1 + cap * 5.  cap: 1 .. H*W, default min(H*W, 64); H*W can never overflow."""
+        from . import policy_head
+
+        return policy_head.packed_words(self, cap)
+
+    def packed_buffer(self, n_steps, cap=None):
+        """A rollout's masks and action rows, packed: uint32 zeros [n_steps][slots][packed_words(cap)] —
+        pack_step(buf[t]) fills step t, evaluate_actions_packed(env, logits, buf, index=mb) scores a minibatch."""
+        T = self.torch
+        return T.zeros((n_steps, self._h.S, self.packed_words(cap)), dtype=T.int32, device=self.device).view(T.uint32)
+
+    def pack_step(self, out, masks=None, actions=None, cap=None, stream=None):
+        """Packs the step's masks and action rows into `out` (uint32 [slots][words], such as buf[t]; every word
+        written): one launch (mrts_policy_head_pack_dev).  Default env.masks / env.actions, the candidate cells from
+        env.source; with `masks` given, [n][H][W][K] and `actions` [n][H*W][7] for any n = out's rows, the
+        candidates come from mask slot 0.  cap defaults to what out's words stand for.  A row of more than cap
+        candidates keeps its first cap and is counted (pack_overflow); its score is NaN."""
+        from . import policy_head
+
+        h = self._h
+        if masks is None and self.masks is None:
+            raise ValueError("masks: pack_step needs the masks (with_masks=True)")
+        m = self.masks if masks is None else masks
+        a = self.actions if actions is None else actions
+        src = self.source if masks is None else None
+        n, cap = policy_head.check_pack_args(self, out, m, a, src, cap)
+        _lib.check(h.L.mrts_policy_head_pack_dev(h.h, n, self._p(m), self._p(src), self._p(a), cap, self._p(out), self._s(stream)))
+        return out
+
+    def pack_overflow(self):
+        """The rows that pack_step cut at their cap since the last call of this (mrts_policy_head_pack_status);
+        clears the count.  Synchronises."""
+        v = ctypes.c_int64(0)
+        _lib.check(self._h.L.mrts_policy_head_pack_status(self._h.h, ctypes.byref(v)))
+        return v.value
+
+    def unpack(self, packed, index=None, masks_out=None, actions_out=None, stream=None):
+        """The canonical dense form of packed rows (mrts_policy_head_unpack_dev): (masks uint8 [rows][H][W][K] of
+        0 / 1, actions int32 [rows][H*W][7]) with components that were off their field -1 and zeros at
+        non-candidate cells.  rows: index's length (int32, gathers packed rows), else every packed row."""
+        from . import policy_head
+
+        h, T = self._h, self.torch
+        rows = index.shape[0] if isinstance(index, T.Tensor) and index.dim() == 1 else (
+            packed.numel() // packed.shape[-1] if isinstance(packed, T.Tensor) and packed.dim() >= 2 else 0)
+        n_packed, cap = policy_head.check_packed_args(self, packed, index, rows)
+        if masks_out is None:
+            masks_out = T.empty((rows, h.H, h.W, h.K), dtype=T.uint8, device=self.device)
+        if actions_out is None:
+            actions_out = T.empty((rows, h.H * h.W, 7), dtype=T.int32, device=self.device)
+        policy_head.check_tensor("masks_out", masks_out, T.uint8, [(rows, h.H, h.W, h.K), (rows, h.H * h.W, h.K)], self.device)
+        policy_head.check_tensor("actions_out", actions_out, T.int32, [(rows, h.H * h.W, 7)], self.device)
+        _lib.check(h.L.mrts_policy_head_unpack_dev(h.h, rows, self._p(packed), n_packed, cap, self._p(index),
+                                                   self._p(masks_out), self._p(actions_out), self._s(stream)))
+        return masks_out, actions_out
+
     def synchronize(self):
         self.torch.cuda.current_stream(self.device).synchronize()
 

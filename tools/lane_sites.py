@@ -75,10 +75,16 @@ WHY = {
     "headField": "policy head: the row_shr:1 of the running sum and the ballots sit outside every lane test; the "
                  "lane tests that follow (`ql == pick`, `set[k]`) only store or accumulate on their own lane",
     "dppD": "policy head helper: a double's two halves through one DPP step each — called only from waveSumD",
-    "waveSumD": "policy head helper: wave_reduce's DPP chain and lane-63 read on doubles; its one caller is k_head",
+    "waveSumD": "policy head helper: wave_reduce's DPP chain and lane-63 read on doubles; its callers are k_head and "
+                "k_head_packed",
     "k_head": "policy head: the kernel's last statement, after its chunk loop (whose `continue`, `while (m)` and "
               "bounds test ballots and kernel arguments: uniform); lp / ent are per-lane partial sums initialised to "
               "0 on every lane",
+    "k_head_packed": "packed policy rows: as k_head, the kernel's last statement; the early return of a NaN row and the "
+                     "chunk and round loops test the packed row's count and cells, read at wave-uniform addresses; the "
+                     "rounds' headCell calls (segMax / segSum / ballots inside) sit in those uniform loops, a DPP row "
+                     "without a candidate running them with every bit cleared.  k_head_pack's ballots (candidates, mask "
+                     "bits) are in uniform flow too: its loops test ballots, the cap and kernel arguments",
     "k_lane_audit_probe": "the audit build's negative control (reads lane 40 from a branch only lanes 0-31 take)",
     "lrClosest": "LightRush: wave_min after the per-lane `for (o = lid() ...)` loop has reconverged; `best` starts at "
                  "INF on every lane; every caller passes wave-uniform arguments from uniform flow",

@@ -16,7 +16,15 @@ and the bytes the sampling kernel reads (the 32-byte sectors its loads touch) ag
 kernel's log-probability is checked against the PyTorch head's on the kernel's own actions (they differ by the
 empty fields' and non-candidate cells' constants, sum of -log n, which the check adds back).
 
-Usage (GPU box): python tools/policy_head_bench.py [--slots 4096] [--rollout 1000] [--repeats 20]
+--packed adds the packed rollout rows on the same masks and actions: pack_step (one launch, with the
+source bits and from mask byte 0), and evaluate_actions_packed + backward against evaluate_actions + backward.  The
+dense update is timed twice, before and after the packed one in every repeat (window order dense, packed, dense): the
+difference of the two dense medians is the noise floor the packed figure is read against.  The same three windows are
+timed once more with the two launches alone (score, gradient; the C entry points), where the host's PyTorch ops
+of the loss do not bound the figure.  The packed results are
+checked to equal the dense ones byte for byte.  Also the bytes per step a rollout keeps in either form.
+
+Usage (GPU box): python tools/policy_head_bench.py [--slots 4096] [--rollout 1000] [--repeats 20] [--packed]
 Prints one JSON line.
 """
 import argparse
@@ -76,6 +84,27 @@ def timed(torch, fn, warmup, repeats, inner):
     return {"median_ms": statistics.median(ts), "min_ms": min(ts), "max_ms": max(ts), "calls_per_window": inner, "windows": repeats}
 
 
+def timed_interleaved(torch, fns, warmup, repeats, inner):
+    """timed() for several legs at once: every repeat times one window of each leg, in the given order"""
+    for _ in range(warmup):
+        for fn in fns.values():
+            for _ in range(inner):
+                fn()
+    torch.cuda.synchronize()
+    ts = {k: [] for k in fns}
+    for _ in range(repeats):
+        for k, fn in fns.items():
+            e0, e1 = torch.cuda.Event(enable_timing=True), torch.cuda.Event(enable_timing=True)
+            e0.record()
+            for _ in range(inner):
+                fn()
+            e1.record()
+            e1.synchronize()
+            ts[k].append(e0.elapsed_time(e1) / inner)
+    return {k: {"median_ms": statistics.median(v), "min_ms": min(v), "max_ms": max(v), "calls_per_window": inner, "windows": repeats}
+            for k, v in ts.items()}
+
+
 def sectors(np, starts, length):
     """distinct 32-byte sectors touched by byte ranges [start, start + length)"""
     first, last = starts // 32, (starts + length - 1) // 32
@@ -84,17 +113,79 @@ def sectors(np, starts, length):
     return int(np.unique(s).size)
 
 
+def packed_leg(torch, env, evaluate_actions, evaluate_actions_packed, a, logits, masks, acts, g_lp, g_ent, k_update, lk):
+    """the --packed figures; env.actions holds `acts` (sample_actions wrote them) and env.source the masks' bits"""
+    S, HW, K = masks.shape
+    assert torch.equal(env.actions, acts)
+    buf = env.packed_buffer(1)
+    cap = (buf.shape[-1] - 1) // 5
+    env.pack_step(buf[0])
+    other = torch.empty_like(buf[0])
+    env.pack_step(other, masks=masks, actions=acts)  # candidates from mask byte 0
+    assert torch.equal(buf[0].view(torch.int32), other.view(torch.int32))
+    overflow = env.pack_overflow()
+    lp_ = logits.clone().requires_grad_(True)
+    rows = buf[0]  # (a view: made once, as the dense leg's tensors are)
+
+    def p_update():
+        lp_.grad = None
+        lp, ent = evaluate_actions_packed(env, lp_, rows)
+        ((lp * g_lp).sum() + (ent * g_ent).sum()).backward()
+        return lp, ent
+
+    with torch.no_grad():
+        d = evaluate_actions(env, logits, masks, acts)
+    p = p_update()
+    k_update()
+    i32 = torch.int32
+    equal = all(torch.equal(x.detach().view(i32), y.view(i32)) for x, y in zip(p, d)) and torch.equal(lp_.grad.view(i32), lk.grad.view(i32))
+    assert equal or overflow, "packed score / gradient differ from the dense ones"
+    t = timed_interleaved(torch, {"update_dense_a": k_update, "update_packed": p_update, "update_dense_b": k_update}, a.warmup, a.repeats, 5)
+    # the two launches alone (score, gradient), without autograd and the loss's PyTorch ops around them
+    from microrts_amd import _lib
+
+    h, P = env._h, env._p
+    lp, ent, grad = torch.empty(S, device=env.device), torch.empty(S, device=env.device), torch.empty_like(logits)
+
+    def d_launches():
+        _lib.check(h.L.mrts_policy_head_score_dev(h.h, S, P(logits), P(masks), P(acts), P(lp), P(ent), env._s(None)))
+        _lib.check(h.L.mrts_policy_head_grad_dev(h.h, S, P(logits), P(masks), P(acts), P(g_lp), P(g_ent), P(grad), env._s(None)))
+
+    def p_launches():
+        _lib.check(h.L.mrts_policy_head_score_packed_dev(h.h, S, P(logits), P(buf), S, cap, None, P(lp), P(ent), env._s(None)))
+        _lib.check(h.L.mrts_policy_head_grad_packed_dev(h.h, S, P(logits), P(buf), S, cap, None, P(g_lp), P(g_ent), P(grad), env._s(None)))
+
+    t.update(timed_interleaved(torch, {"launches_dense_a": d_launches, "launches_packed": p_launches, "launches_dense_b": d_launches},
+                               a.warmup, a.repeats, 20))
+    t.update(timed_interleaved(torch, {"pack_step": lambda: env.pack_step(buf[0]),
+                                       "pack_step_mask_byte_0": lambda: env.pack_step(other, masks=masks, actions=acts)},
+                               a.warmup, a.repeats, 50))
+    env.pack_overflow()
+    da, db, pk = (t[k]["median_ms"] for k in ("update_dense_a", "update_dense_b", "update_packed"))
+    t.update({
+        "cap": cap, "overflow_rows": overflow, "bit_identical_to_dense": bool(equal),
+        "dense_bytes_per_step": S * HW * (K + 28), "packed_bytes_per_step": S * buf.shape[-1] * 4,
+        "bytes_ratio": HW * (K + 28) / (buf.shape[-1] * 4),
+        "noise_floor_ms": abs(da - db), "packed_minus_dense_ms": pk - (da + db) / 2,
+        "launches_noise_floor_ms": abs(t["launches_dense_a"]["median_ms"] - t["launches_dense_b"]["median_ms"]),
+        "launches_packed_minus_dense_ms": t["launches_packed"]["median_ms"]
+        - (t["launches_dense_a"]["median_ms"] + t["launches_dense_b"]["median_ms"]) / 2,
+    })
+    return t
+
+
 def main():
     import numpy as np
     import torch
 
-    from microrts_amd import DeviceVecEnv, evaluate_actions
+    from microrts_amd import DeviceVecEnv, evaluate_actions, evaluate_actions_packed
 
     ap = argparse.ArgumentParser()
     ap.add_argument("--slots", type=int, default=4096)
     ap.add_argument("--rollout", type=int, default=1000)
     ap.add_argument("--warmup", type=int, default=3)
     ap.add_argument("--repeats", type=int, default=20)
+    ap.add_argument("--packed", action="store_true", help="also the packed rollout rows against the dense update")
     a = ap.parse_args()
     if not torch.cuda.is_available():
         raise SystemExit("policy_head_bench needs an MI355X")
@@ -180,6 +271,8 @@ def main():
         "sample_read_share_of_dense": (read["source_bits"] + read["mask_sector_bytes"] + read["logit_sector_bytes"]) / dense,
         "check": {"logprob_max_abs_diff": d_lp, "entropy_max_abs_diff": d_ent, "grad_max_abs_diff": d_grad, "logprob_scale": scale},
     })
+    if a.packed:
+        res["packed"] = packed_leg(torch, env, evaluate_actions, evaluate_actions_packed, a, logits, masks, acts, g_lp, g_ent, k_update, lk)
     print(json.dumps(res))
     env.close()
 
