@@ -17,54 +17,68 @@ ERR_BITS = {
     1 << 4: "NEG_RESOURCES", 1 << 5: "MOVE_COLLISION", 1 << 6: "RECORD",
 }
 
-def _code_sections(obj):
-    """The .text and .rodata sections (the kernels' machine code and kernel descriptors) of an amdgcn code
-    object, concatenated: what the kernels run, without the symbol tables (hipcc's per-compile __hip_cuid_*
-    symbol differs between builds of the same source under different -D flags)."""
+def _elf_sections(obj):
+    """[(name, type, address, offset, size, link, entry size)] of a 64-bit little-endian ELF image, by section index"""
     import struct
 
     shoff = struct.unpack_from("<Q", obj, 0x28)[0]
     shentsize, shnum, shstrndx = struct.unpack_from("<HHH", obj, 0x3A)
-    secs = [struct.unpack_from("<IIQQQQ", obj, shoff + i * shentsize) for i in range(shnum)]
+    secs = [struct.unpack_from("<IIQQQQIIQQ", obj, shoff + i * shentsize) for i in range(shnum)]
     stroff = secs[shstrndx][4]
-    out = b""
-    for want in (b".text", b".rodata"):
-        for name, _, _, _, off, size in secs:
-            if obj[stroff + name:obj.index(b"\0", stroff + name)] == want:
-                out += obj[off:off + size]
-    if not out:
+    return [(obj[stroff + s[0]:obj.index(b"\0", stroff + s[0])].decode(), s[1], s[3], s[4], s[5], s[6], s[9]) for s in secs]
+
+
+def _code_sections(obj):
+    """The .text and .rodata sections (the kernels' machine code and kernel descriptors) of an amdgcn code
+    object, concatenated: what the kernels run, without the symbol tables (hipcc's per-compile __hip_cuid_*
+    symbol differs between builds of the same source under different -D flags)."""
+    secs = {s[0]: s for s in _elf_sections(obj)}
+    if ".text" not in secs:
         raise RuntimeError("amdgcn code object without .text")
-    return out
+    return b"".join(obj[secs[n][3]:secs[n][3] + secs[n][4]] for n in (".text", ".rodata") if n in secs)
 
 
-def device_code_sha256(path=None):
-    """SHA-256 of the gfx950 code inside libmrts.so (the .hip_fatbin offload bundle's amdgcn entry): its
-    .text and .rodata, the kernels' machine code and descriptors.  Counter files (profiles/pmc_*.json) name
-    the code they describe with it, so a host-only change to the library keeps them valid and any kernel
-    change voids them."""
-    import hashlib
+def device_code_objects(path=None):
+    """The gfx950 code objects of libmrts.so, in file order: the library is linked from several HIP objects
+    (csrc/*.hip), each of which brings an offload bundle of its own into .hip_fatbin (bundles are 4 KiB-aligned;
+    an object without device code brings an entry with no bytes).  Also takes a bare code object (a device-only
+    compile)."""
     import struct
 
     data = open(path or LIB_PATH, "rb").read()
-    shoff = struct.unpack_from("<Q", data, 0x28)[0]
-    shentsize, shnum, shstrndx = struct.unpack_from("<HHH", data, 0x3A)
-    secs = [struct.unpack_from("<IIQQQQ", data, shoff + i * shentsize) for i in range(shnum)]
-    stroff = secs[shstrndx][4]
-    for name, _, _, _, off, size in secs:
-        if data[stroff + name:data.index(b"\0", stroff + name)] != b".hip_fatbin":
-            continue
-        b = data[off:off + size]
-        if not b.startswith(b"__CLANG_OFFLOAD_BUNDLE__"):
-            break
-        n, p = struct.unpack_from("<Q", b, 24)[0], 32
+    secs = {s[0]: s for s in _elf_sections(data)}
+    if ".hip_fatbin" not in secs:
+        if struct.unpack_from("<H", data, 0x12)[0] == 224:  # EM_AMDGPU
+            return [data]
+        raise RuntimeError(f"{path or LIB_PATH}: no .hip_fatbin")
+    magic = b"__CLANG_OFFLOAD_BUNDLE__"
+    b = data[secs[".hip_fatbin"][3]:secs[".hip_fatbin"][3] + secs[".hip_fatbin"][4]]
+    out, at = [], b.find(magic)
+    while at >= 0:
+        n, p = struct.unpack_from("<Q", b, at + 24)[0], at + 32
+        end = p
         for _ in range(n):
             eoff, esize, tl = struct.unpack_from("<QQQ", b, p)
             p += 24
             triple = b[p:p + tl].decode()
             p += tl
-            if "amdgcn" in triple:
-                return hashlib.sha256(_code_sections(b[eoff:eoff + esize])).hexdigest()
-    raise RuntimeError(f"{path or LIB_PATH}: no amdgcn code object in .hip_fatbin")
+            end = max(end, at + eoff + esize)
+            if "amdgcn" in triple and esize:
+                out.append(b[at + eoff:at + eoff + esize])
+        at = b.find(magic, max(p, end))  # the next bundle, past this one's entries
+    if not out:
+        raise RuntimeError(f"{path or LIB_PATH}: no amdgcn code object in .hip_fatbin")
+    return out
+
+
+def device_code_sha256(path=None):
+    """SHA-256 of the gfx950 code inside libmrts.so: the .text and .rodata — the kernels' machine code and
+    descriptors — of every code object (device_code_objects), in file order.  Counter files (profiles/pmc_*.json)
+    name the code they describe with it, so a host-only change to the library keeps them valid and any change to
+    any kernel voids them."""
+    import hashlib
+
+    return hashlib.sha256(b"".join(_code_sections(o) for o in device_code_objects(path))).hexdigest()
 
 
 # every symbol include/mrts.h declares

@@ -18,44 +18,9 @@
 #include "../../include/mrts.h"
 #include "mrts_internal.h"
 #include "mrts_json.hpp"
+#include "mrts_launch.h"
 
 using namespace mrts;
-
-namespace mrts {
-size_t ldsBytes(int HW, int W, int CAP, int po);
-size_t lrLdsBytes(int HW, int W, int CAP);
-hipError_t launchEnv(int mode, const KStatic& hs, const KStatic* ds, const KDyn& D, hipStream_t stream, hipEvent_t e0 = nullptr,
-                     hipEvent_t e1 = nullptr);
-bool envIterable(const KStatic& hs);
-hipError_t launchPolicyUniform(int32_t* actions, int n_slots, int HW, int ntypes, int natt, uint64_t seed, uint32_t step,
-                               uint32_t slot_base, hipStream_t stream);
-#ifdef MRTS_LANE_AUDIT
-hipError_t laneAudit(int32_t* out, int reset);
-hipError_t laneAuditProbe(int32_t* scratch);
-#endif
-#ifdef MRTS_ABLATE
-hipError_t setAblate(uint32_t v);
-hipError_t getDbg(unsigned long long* out, int reset);
-#endif
-#ifdef MRTS_PHASE_TIMING
-hipError_t phaseTimes(unsigned long long* out, int reset);
-hipError_t phaseSpans(unsigned long long* out, int n);
-#endif
-hipError_t launchPolicy(const PolicyParams& Q, hipStream_t stream, bool* prevWritten);
-hipError_t launchHead(int mode, const HeadParams& Q, hipStream_t stream);
-hipError_t launchHeadPacked(int mode, const HeadPackedParams& P, hipStream_t stream);
-hipError_t launchWiden(const uint8_t* in, int32_t* out, size_t n, hipStream_t stream);
-hipError_t launchOneHot(const int32_t* obs, uint8_t* out, int n_slots, int HW, int C, int ntypes, hipStream_t stream);
-hipError_t prepareLds(size_t bytes);
-hipError_t launchCopyGames(int32_t* dst, const int32_t* src, const int32_t* pairs, int n, int n_dst, int n_src,
-                           int CAP, int HW, int src_words, hipStream_t stream);
-hipError_t launchEvaluate(const KStatic& hs, const KStatic* ds, int maxplayer, float* out, hipStream_t stream);
-hipError_t launchRenderRecords(const KStatic& hs, const KStatic* ds, const uint32_t* rec, int units, int n_ranks,
-                               int64_t rank_stride, void* out, int out_bytes, int32_t* err, hipStream_t stream);
-hipError_t launchRenderRecordsOneHot(const KStatic& hs, const KStatic* ds, const uint32_t* rec, int64_t rec_words, int n_ranks,
-                                     int units, int64_t rank_stride, const int32_t* sel, const int64_t* step_off, int n_sel,
-                                     uint8_t* out, int32_t* err, hipStream_t stream);
-}  // namespace mrts
 
 static thread_local std::string g_err;
 
@@ -465,10 +430,7 @@ struct mrts_env {
     int hasLightRush = 0;
     uint32_t botTypes = 0;
     size_t blockWords() const { return (size_t)stateWords(CAP, HW) + (hasLightRush ? (size_t)botWords(CAP) : 0); }
-    size_t ldsNeed() const {
-        const size_t base = (ldsBytes(HW, W, CAP, partialObs) + 15) & ~(size_t)15;
-        return hasLightRush ? base + lrLdsBytes(HW, W, CAP) : ldsBytes(HW, W, CAP, partialObs);
-    }
+    size_t ldsNeed() const { return handleLdsBytes(HW, W, CAP, partialObs, hasLightRush != 0); }
     uint32_t slotIdBase = 0;
     DevUtt utt;
     UttInfo uttInfo;
@@ -608,7 +570,7 @@ struct mrts_env {
         hstatic.tmpl_off = d_tmplOff;
         hstatic.game_kind = d_gameKind;
         hstatic.bot_off = hasLightRush ? stateWords(CAP, HW) : 0;
-        hstatic.bot_lds = hasLightRush ? (int32_t)((ldsBytes(HW, W, CAP, partialObs) + 15) & ~(size_t)15) : 0;
+        hstatic.bot_lds = hasLightRush ? (int32_t)ldsLightRushOff(HW, W, CAP, partialObs) : 0;
         hstatic.bot_types = botTypes;
     }
     hipError_t launch(int mode, const KDyn& Din, hipStream_t s, hipEvent_t e0 = nullptr, hipEvent_t e1 = nullptr) const {

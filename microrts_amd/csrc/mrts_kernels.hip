@@ -10,6 +10,8 @@
 // (row fetch + decode, legality, conflict flags, ready ranking, death compaction, visibility,
 // observation planes, legal-action masks) runs lane-parallel with ballots and DPP reductions.
 // No MFMA: integer/indexing work.
+// This unit is the step kernel: Game, k_env and its instances, the launch selection, the LDS sizes and the
+// diagnostic builds' read-backs.  The policies are in mrts_policy.hip, the renderers in mrts_aux.hip.
 #include <hip/hip_runtime.h>
 #include <hip/hip_ext.h>
 #include <stdint.h>
@@ -17,16 +19,12 @@
 #include <algorithm>
 #include <vector>
 
-#include "mrts_internal.h"
-
-using namespace mrts;
-
-#define DEV __device__ __forceinline__
+#define MRTS_UNIT 0
+#include "mrts_device.h"
 
 namespace {
 
 constexpr uint16_t EMPTY = 0xFFFF, WALL = 0xFFFE;
-constexpr int INF = 0x7FFFFFFF;
 enum { T_NONE = 0, T_MOVE = 1, T_HARVEST = 2, T_RETURN = 3, T_PRODUCE = 4, T_ATTACK = 5 };
 enum { MODE_STEP = 0, MODE_RESET = 1, MODE_MASKS = 2, MODE_PLAYOUT = 3, MODE_TRACE = 4 };
 
@@ -122,13 +120,12 @@ enum : uint32_t {
 // MODE_TRACE per-game result word (KDyn.trace_out)
 enum : uint32_t { TR_ISSUED = 1u, TR_GAMEOVER = 2u, TR_NO_UNIT = 4u };
 
-DEV int lane_id() { return (int)threadIdx.x; }
 // branch-probability hints: cold paths (more than 64 units, auto-reset, conflict resolution, the
 // general mask writer, reward bookkeeping the benchmark does not request) are laid out away from the
 // hot straight-line code, which then packs into fewer instruction-cache lines
 #define MRTS_LIKELY(x) __builtin_expect(!!(x), 1)
 #define MRTS_UNLIKELY(x) __builtin_expect(!!(x), 0)
-// The build switches that remain: the diagnostic builds above and below (MRTS_LANE_AUDIT), and the two that a
+// The build switches that remain: the diagnostic builds above and MRTS_LANE_AUDIT (mrts_device.h), and the two that a
 // committed test or tool builds at the other value.  An experiment's switch lives for the pull request that
 // measures it (`make x1 XFLAGS1=-D...`); the code then keeps the measured choice.
 #ifndef MRTS_ISSUE_BOTH  // selfPlayFast issues both players' rows in one pass when no row of either interacts (round 7);
@@ -149,308 +146,6 @@ DEV int lane_id() { return (int)threadIdx.x; }
 #ifndef MRTS_PO_VRES
 #define MRTS_PO_VRES 0
 #endif
-// Output stores.  WT = streaming (`nt`) stores, so output lines do not sit dirty in the XCD's L2
-// until the end-of-kernel write-back.  Builtins, not inline asm: the wait-count and store-data
-// hazard passes must see the stores.
-typedef int32_t i32x4v __attribute__((ext_vector_type(4)));
-typedef int32_t i32x4u __attribute__((ext_vector_type(4), aligned(4)));
-typedef int32_t i32x3u __attribute__((ext_vector_type(3), aligned(4)));
-template <bool WT>
-DEV void st4(void* p, int a, int b, int c, int d) {  // 16-byte aligned
-    const i32x4v v = {a, b, c, d};
-    if (WT) __builtin_nontemporal_store(v, (i32x4v*)p);
-    else *(i32x4v*)p = v;
-}
-template <bool WT>
-DEV void st4u(void* p, int a, int b, int c, int d) {  // 4-byte aligned
-    const i32x4u v = {a, b, c, d};
-    if (WT) __builtin_nontemporal_store(v, (i32x4u*)p);
-    else *(i32x4u*)p = v;
-}
-template <bool WT>
-DEV void st3u(void* p, int a, int b, int c) {  // 4-byte aligned
-    const i32x3u v = {a, b, c};
-    if (WT) __builtin_nontemporal_store(v, (i32x3u*)p);
-    else *(i32x3u*)p = v;
-}
-template <bool WT>
-DEV void st1(int32_t* p, int a) {
-    if (WT) __builtin_nontemporal_store(a, p);
-    else *p = a;
-}
-// The store policy, measured on c3 / c5 / --mask-mode full (profiles/r12_summary.md).  Streaming stores for:
-constexpr bool WT_OBS = true,        // full-observability planes (c3 +4.5 %, full masks +3 %)
-               WT_MASK = false,      // delta mask records + policy rows (c3 -1.3 %)
-               WT_FULLMASK = false,  // full-rewrite mask chunks (-15 %)
-               WT_STATE = false,     // the state block (neutral)
-               WT_POOBS = false;     // partially observable planes (c5 -18 %)
-// Round 2 (profiles/round2_store_policy.md): write-through (`sc1`) buffer stores leave no line in the XCD's L2,
-// so the next step's state and action-row reads (the same game runs on the same XCD every launch:
-// tools/xcd_placement.py) keep theirs; `rsrc` = a raw buffer over the stored region (gfx9 descriptor word 3).
-constexpr bool SC1_OBS = true,     // full-observability planes (c3 +3.2 %)
-               SC1_POOBS = true,   // partially observable planes (c5 +3.4 %)
-               SC1_MASK = false;   // delta mask records (byte-granular partial lines: c3 -5 %)
-// The plane stores are written for this policy: where a writer has the sc1 form it calls st4sc1 (or the b32
-// builtin) directly, which takes precedence over WT_OBS / WT_POOBS.
-static_assert(WT_OBS && SC1_OBS && SC1_POOBS, "plane stores: sc1 buffer stores");
-DEV __amdgpu_buffer_rsrc_t bufRsrc(void* base, uint32_t bytes) {
-    return __builtin_amdgcn_make_buffer_rsrc(base, (short)0, (int)bytes, 0x00020000);
-}
-DEV void st4sc1(__amdgpu_buffer_rsrc_t r, uint32_t byteOff, int a, int b, int c, int d) {
-    const i32x4v v = {a, b, c, d};
-    __builtin_amdgcn_raw_buffer_store_b128(v, r, (int)byteOff, 0, 16);
-}
-DEV int ux(uint32_t c) { return (int)(c & 0xFF); }
-DEV int uy(uint32_t c) { return (int)((c >> 8) & 0xFF); }
-DEV int utyp(uint32_t c) { return (int)((c >> 16) & 0xF); }
-DEV int uplay(uint32_t c) { return (int)((c >> 20) & 3) - 1; }
-DEV uint32_t pack_uc(int x, int y, int t, int p) {
-    return (uint32_t)x | ((uint32_t)y << 8) | ((uint32_t)t << 16) | ((uint32_t)(p + 1) << 20);
-}
-DEV int ua_type(uint32_t a) { return (int)(a & 0xF); }
-DEV int ua_ut(uint32_t a) { return (int)((a >> 4) & 0xF); }
-DEV int ua_tx(uint32_t a) { return (int)((a >> 8) & 0xFF); }
-DEV int ua_ty(uint32_t a) { return (int)((a >> 16) & 0xFF); }
-DEV uint32_t pack_ua(int t, int ut, int tx, int ty) {
-    return (uint32_t)t | ((uint32_t)ut << 4) | ((uint32_t)tx << 8) | ((uint32_t)ty << 16);
-}
-// UnitAction.DIRECTION_OFFSET_X/Y (rts/UnitAction.java:94-100); invalid directions move nowhere
-DEV int dxo(int d) { return d == 1 ? 1 : (d == 3 ? -1 : 0); }
-DEV int dyo(int d) { return d == 0 ? -1 : (d == 2 ? 1 : 0); }
-DEV int clampdir(int d) { return (d >= 0 && d <= 3) ? d : ACT_INVALID; }
-
-// Diagnostic build only (-DMRTS_LANE_AUDIT, `make audit`; tests/test_zz_lane_audit.py): every cross-lane read
-// checks at run time that the lanes it reads are active where it executes — a readlane's source lane, every lane
-// for the DPP reductions and ballots (which the code treats as whole-wave) — and records the source line of a
-// violation in g_laneAudit (one vector store per lane, its own slot).  A readlane of an inactive lane returns
-// whatever its register last held (the round-4 soak's stale PO value).  Not in libmrts.so.
-#ifdef MRTS_LANE_AUDIT
-__device__ int32_t g_laneAudit[256];
-DEV void laneAuditHit(int line, int kind) { g_laneAudit[threadIdx.x & 255] = line | (kind << 24); }
-DEV bool laneOn(int k) { return (__builtin_amdgcn_read_exec() >> k) & 1ull; }
-DEV bool waveOn() { return __builtin_amdgcn_read_exec() == ~0ull; }
-DEV int rlAudit(int v, int k, int line) {
-    if (!laneOn(k)) laneAuditHit(line, 1);
-    return __builtin_amdgcn_readlane(v, k);
-}
-#define rl(v, k) rlAudit((v), (k), __LINE__)
-#define LANE_AUDIT_WAVE(kind)                              \
-    do {                                                   \
-        if (!waveOn()) laneAuditHit(__LINE__, (kind));     \
-    } while (0)
-#else
-DEV int rl(int v, int k) { return __builtin_amdgcn_readlane(v, k); }
-#define LANE_AUDIT_WAVE(kind) ((void)0)
-#endif
-// four int32 values (each within int16) as four packed int16
-DEV uint2 pk16(int4 w) {
-    return make_uint2(((uint32_t)w.x & 0xFFFFu) | ((uint32_t)w.y << 16), ((uint32_t)w.z & 0xFFFFu) | ((uint32_t)w.w << 16));
-}
-DEV int uni(int v) { return __builtin_amdgcn_readfirstlane(v); }
-DEV uint32_t uniu(uint32_t v) { return (uint32_t)__builtin_amdgcn_readfirstlane((int)v); }
-#ifdef MRTS_LANE_AUDIT
-#define ballot(p) ballotAudit((p), __LINE__)
-DEV uint64_t ballotAudit(bool p, int line) {
-    if (!waveOn()) laneAuditHit(line, 3);
-    return __ballot(p);
-}
-#else
-DEV uint64_t ballot(bool p) { return __ballot(p); }
-#endif
-DEV int lanes_below(uint64_t m) {
-    return (int)__builtin_amdgcn_mbcnt_hi((uint32_t)(m >> 32), __builtin_amdgcn_mbcnt_lo((uint32_t)m, 0));
-}
-// A game is one wave and its LDS is private to that wave: LDS operations of one wave execute in
-// order, so a wave-scope fence (a compiler barrier, no instruction) orders them across lanes.
-DEV void wsync() {
-    __builtin_amdgcn_fence(__ATOMIC_RELEASE, "wavefront");
-    __builtin_amdgcn_wave_barrier();
-    __builtin_amdgcn_fence(__ATOMIC_ACQUIRE, "wavefront");
-}
-
-// Whole-wave reductions with DPP (GFX9 row_bcast forms): quad swaps, half-row and row mirrors
-// reduce each 16-lane row; row_bcast:15/31 chain the rows; lane 63 holds the result.
-template <bool MIN>
-DEV int wave_reduce(int v) {
-    LANE_AUDIT_WAVE(2);
-    const int id = MIN ? INF : 0;
-    auto op = [](int a, int b) { return MIN ? min(a, b) : a + b; };
-    v = op(v, __builtin_amdgcn_update_dpp(id, v, 0xB1, 0xF, 0xF, false));   // quad_perm [1,0,3,2]
-    v = op(v, __builtin_amdgcn_update_dpp(id, v, 0x4E, 0xF, 0xF, false));   // quad_perm [2,3,0,1]
-    v = op(v, __builtin_amdgcn_update_dpp(id, v, 0x141, 0xF, 0xF, false));  // row_half_mirror
-    v = op(v, __builtin_amdgcn_update_dpp(id, v, 0x140, 0xF, 0xF, false));  // row_mirror
-    v = op(v, __builtin_amdgcn_update_dpp(id, v, 0x142, 0xA, 0xF, false));  // row_bcast:15
-    v = op(v, __builtin_amdgcn_update_dpp(id, v, 0x143, 0xC, 0xF, false));  // row_bcast:31
-    return rl(v, 63);
-}
-// Inclusive prefix sum over the wave's lanes with DPP: row_shr 1/2/4/8 scan each 16-lane row
-// (lanes shifted in from outside the row read 0), row_bcast:15 / :31 carry the row totals.
-DEV int wave_incl_sum(int v) {
-    LANE_AUDIT_WAVE(2);
-    v += __builtin_amdgcn_update_dpp(0, v, 0x111, 0xF, 0xF, false);  // row_shr:1
-    v += __builtin_amdgcn_update_dpp(0, v, 0x112, 0xF, 0xF, false);  // row_shr:2
-    v += __builtin_amdgcn_update_dpp(0, v, 0x114, 0xF, 0xF, false);  // row_shr:4
-    v += __builtin_amdgcn_update_dpp(0, v, 0x118, 0xF, 0xF, false);  // row_shr:8
-    v += __builtin_amdgcn_update_dpp(0, v, 0x142, 0xA, 0xF, false);  // row_bcast:15 -> rows 1, 3
-    v += __builtin_amdgcn_update_dpp(0, v, 0x143, 0xC, 0xF, false);  // row_bcast:31 -> rows 2, 3
-    return v;
-}
-DEV int wave_min(int v) { return wave_reduce<true>(v); }
-DEV int wave_sum(int v) { return wave_reduce<false>(v); }
-
-// java.util.Random (48-bit LCG, JDK 8) — GameState.r / UnitAction.r / Sampler.generator, per game
-struct JRand {
-    uint64_t s;
-    DEV int next(int bits) {
-        s = (s * 0x5DEECE66DULL + 0xBULL) & ((1ULL << 48) - 1);
-        return (int)(uint32_t)(s >> (48 - bits));
-    }
-    DEV int nextInt(int bound) {
-        if ((bound & -bound) == bound) return (int)(((int64_t)bound * (int64_t)next(31)) >> 31);
-        int bits, val;
-        do {
-            bits = next(31);
-            val = bits % bound;
-        } while ((int)((uint32_t)bits - (uint32_t)val + (uint32_t)(bound - 1)) < 0);
-        return val;
-    }
-    DEV double nextDouble() { return (double)(((int64_t)next(26) << 27) + next(27)) * (1.0 / 9007199254740992.0); }
-};
-DEV uint64_t rng_of(int lo, int hi) { return (uint64_t)(uint32_t)lo | ((uint64_t)(uint32_t)hi << 32); }
-
-// Snapshot byte per unit for PartiallyObservableGameState views (rts/PartiallyObservableGameState.java:35-54):
-// bit p = unit is in player p's snapshot list; bits 2-4 / 5-7 = (snapshot UAA action type + 1), 0 = none.
-DEV int snap_in(uint32_t b, int p) { return (b >> p) & 1; }
-DEV int snap_act(uint32_t b, int p) { return (int)((b >> (2 + 3 * p)) & 7); }
-
-// The unit-type table is read with lane-varying indices all over the step; an LDS copy turns those
-// global loads into LDS reads.
-constexpr int UTT_WORDS = (int)(sizeof(DevUtt) / 4);
-constexpr int UTT_LDS = (int)((sizeof(DevUtt) + 15) & ~(size_t)15);
-static_assert(sizeof(DevUtt) % 4 == 0 && UTT_WORDS <= 192, "DevUtt copy: 3 words per lane");
-
-// a ^ b ^ k in one VALU instruction (gfx950's three-input bit op, truth table 0x96; the compiler emits
-// two v_xor_b32 for it).  k MUST be wave-uniform (a Philox key word, in an SGPR): the "s" constraint would
-// silently readfirstlane a per-lane value.  Other targets (ARCH overridden) take the plain C form.
-DEV uint32_t xor3s(uint32_t a, uint32_t b, uint32_t k) {
-#if defined(__gfx950__)
-    uint32_t d;
-    asm("v_bitop3_b32 %0, %1, %2, %3 bitop3:0x96" : "=v"(d) : "v"(a), "v"(b), "s"(k));
-    return d;
-#else
-    return a ^ b ^ k;
-#endif
-}
-// Philox4x32-10, the ten rounds unrolled (rolled, the loop carried two v_mov per round and the xors
-// were not fused: 8 VALU per round against 4)
-DEV void philox(uint32_t c[4], uint32_t k0, uint32_t k1) {
-#pragma unroll
-    for (int r = 0; r < 10; r++) {
-        const uint64_t p0 = (uint64_t)0xD2511F53u * c[0];
-        const uint64_t p1 = (uint64_t)0xCD9E8D57u * c[2];
-        const uint32_t n0 = xor3s((uint32_t)(p1 >> 32), c[1], k0), n1 = (uint32_t)p1;
-        const uint32_t n2 = xor3s((uint32_t)(p0 >> 32), c[3], k1), n3 = (uint32_t)p0;
-        c[0] = n0;
-        c[1] = n1;
-        c[2] = n2;
-        c[3] = n3;
-        k0 += 0x9E3779B9u;
-        k1 += 0xBB67AE85u;
-    }
-}
-DEV int pickBit(uint32_t r, uint64_t bitsv, int n) {
-    const uint64_t m = n >= 64 ? ~0ull : ((1ull << n) - 1);
-    bitsv &= m;
-    const int cnt = __popcll(bitsv);
-    if (cnt == 0) return -1;
-    int k = (int)(((uint64_t)r * (uint32_t)cnt) >> 32);
-    while (k--) bitsv &= bitsv - 1;
-    return __builtin_ctzll(bitsv);
-}
-// one cell's action from its mask bits (lo/hi: mask slots 1..K-1 -> bit i-1), Philox counter
-// (slot id, step, cell, 0)
-// Masked-uniform random policy of one cell (the bench / rollout agent): mask slots 1..K-1 as bits
-// (lo: slots 1..64, hi: 65..), Philox4x32-10 with key = seed, counter = (slot id, step, cell, 0)
-// pickBit of a field of at most 32 bits (already masked): the same pick in 32-bit operations
-DEV int pickBit32(uint32_t r, uint32_t bitsv) {
-    const int cnt = __popc(bitsv);
-    if (cnt == 0) return -1;
-    int k = (int)__umulhi(r, (uint32_t)cnt);
-    while (k--) bitsv &= bitsv - 1;
-    return __builtin_ctz(bitsv);
-}
-// packFwd of a row with every value 0 (each parameter field holds value + 1)
-constexpr uint32_t FWD_ZERO = (1u << 3) | (1u << 6) | (1u << 9) | (1u << 12) | (1u << 15) | (1u << 19);
-// packed (optional): packFwd(a) of the drawn row, built from the picks (no field repacking)
-// The parameter comes from ONE pick over the chosen type's field, not one pick per case of a switch over the type:
-// the lanes of a wave hold several types, and a switch runs its cases one after the other.
-DEV void sampleBitsRaw(uint64_t seed, uint32_t step, uint32_t slotId, int ntypes, int K, uint64_t lo, uint64_t hi, int c,
-                       int32_t a[7], uint32_t* packed = nullptr) {
-    uint32_t ctr[4] = {slotId, step, (uint32_t)c, 0u};
-    philox(ctr, (uint32_t)seed, (uint32_t)(seed >> 32));
-    // mask slots 1..K-1 as bits of lo:hi (slot k -> bit k - 1): the type field is bits 0..5, the produce
-    // types bits 22.., the direction fields bits 6 + 4 (t - 1).., the attack window bits 22 + ntypes..
-    const int t = pickBit32(ctr[0], (uint32_t)lo & 63u);
-    int pv = 0, ut = 0;
-    if (t > 0 && t < 5) {
-        // a direction: 4 bits at 2 + 4 t (below 32) — one 32-bit pick
-        pv = pickBit32(ctr[1], ((uint32_t)lo >> (2 + 4 * t)) & 15u);
-    } else if (t > 0) {
-        // the attack window: K - 23 - ntypes bits from 22 + ntypes (across lo / hi), a 64-bit pick
-        const int b = t == 5 ? 22 + ntypes : 2 + 4 * t, n = t == 5 ? K - 23 - ntypes : 4;
-        uint64_t v = b >= 64 ? hi >> (b - 64) : ((lo >> b) | (hi << (64 - b)));
-        v &= n >= 64 ? ~0ull : ((1ull << n) - 1);
-        pv = pickBit(ctr[1], v, 64);
-    }
-    if (t == 4) ut = pickBit32(ctr[2], (uint32_t)(lo >> 22) & ((1u << ntypes) - 1u));
-    a[0] = t > 0 ? t : 0;
-    a[1] = t == 1 ? pv : 0;
-    a[2] = t == 2 ? pv : 0;
-    a[3] = t == 3 ? pv : 0;
-    a[4] = t == 4 ? pv : 0;
-    a[5] = ut;
-    a[6] = t == 5 ? pv : 0;
-    if (packed)
-        *packed = FWD_ZERO + (uint32_t)(t > 0 ? t : 0) + (t > 0 ? (uint32_t)pv << (t == 5 ? 19 : 3 * t) : 0u) +
-                  ((uint32_t)ut << 15);
-}
-
-// Unmasked uniform random row (BASELINE config c2) of cell c of slot id slotId:
-// type in [0, 6), the four directions in [0, 4), produce type in [0, ntypes), attack window index
-// in [0, natt) — rows that reach every illegal -> NONE path of issueSafe.  Philox4x32-10, key =
-// seed, counter = (slot id, step, cell, UNIFORM_TAG); ranges by multiply-shift of the 32-bit words.
-constexpr uint32_t UNIFORM_TAG = 0x554E4946u;  // "UNIF": a stream apart from the masked policy's (word 3 = 0)
-DEV void uniformRow(uint64_t seed, uint32_t step, uint32_t slotId, int c, int ntypes, int natt, int32_t a[7]) {
-    uint32_t ctr[4] = {slotId, step, (uint32_t)c, UNIFORM_TAG};
-    philox(ctr, (uint32_t)seed, (uint32_t)(seed >> 32));
-    auto below = [](uint32_t r, int n) { return (int)(((uint64_t)r * (uint32_t)n) >> 32); };
-    a[0] = below(ctr[0], 6);
-    a[1] = (int)(ctr[1] & 3u);
-    a[2] = (int)((ctr[1] >> 2) & 3u);
-    a[3] = (int)((ctr[1] >> 4) & 3u);
-    a[4] = (int)((ctr[1] >> 6) & 3u);
-    a[5] = below(ctr[2], ntypes);
-    a[6] = below(ctr[3], natt);
-}
-
-// Forwarded action word (H_FWD / stateFwdOff): the 7 values of a fused-policy row, which the sampler
-// draws as type 0..5 and parameters -1..(field size - 1): type 3 bits, the four directions 3 bits
-// each, produce type 4 bits, attack index 7 bits, each parameter stored + 1.
-DEV uint32_t packFwd(const int32_t a[7]) {
-    return ((uint32_t)a[0] & 7u) | (((uint32_t)(a[1] + 1) & 7u) << 3) | (((uint32_t)(a[2] + 1) & 7u) << 6) |
-           (((uint32_t)(a[3] + 1) & 7u) << 9) | (((uint32_t)(a[4] + 1) & 7u) << 12) | (((uint32_t)(a[5] + 1) & 15u) << 15) |
-           (((uint32_t)(a[6] + 1) & 127u) << 19);
-}
-DEV void unpackFwd(uint32_t w, int32_t a[7]) {
-    a[0] = (int32_t)(w & 7u);
-    a[1] = (int32_t)((w >> 3) & 7u) - 1;
-    a[2] = (int32_t)((w >> 6) & 7u) - 1;
-    a[3] = (int32_t)((w >> 9) & 7u) - 1;
-    a[4] = (int32_t)((w >> 12) & 7u) - 1;
-    a[5] = (int32_t)((w >> 15) & 15u) - 1;
-    a[6] = (int32_t)((w >> 19) & 127u) - 1;
-}
-
 // The kernel's KDyn argument as a pointer into the constant (kernarg) address space.  The multi-step
 // loop makes it opaque once per iteration (freshLane), so the compiler re-reads a field with a scalar
 // load (SMEM) where the step uses it, instead of loading every field at kernel entry and keeping it
@@ -465,32 +160,6 @@ DEV KDynPtr kdynArg(bool launder) {
     int z = 0;
     if (launder) asm volatile("" : "+s"(z));
     return (KDynPtr)((const __attribute__((address_space(4))) char*)__builtin_amdgcn_kernarg_segment_ptr() + 16 + z);
-}
-// One sight disk (dx^2 + dy^2 <= sr^2) ORed into per-row bitmaps of a W-wide map ((W + 31) / 32 words a
-// row): one atomicOr per covered row word.  dlo / dhi: the unit-type table's half-widths for sr <= 15
-// (host-computed, DevUtt::diskLo/Hi); a larger sight takes the integer square root per row.
-DEV void paintDiskRows(uint32_t* rows, int H, int W, int x, int y, int sr, uint32_t dlo, uint32_t dhi) {
-    const int WPR = (W + 31) >> 5;
-    for (int dy = -sr; dy <= sr; dy++) {
-        const int yy = y + dy;
-        if (yy < 0 || yy >= H) continue;
-        const int ady = dy < 0 ? -dy : dy;
-        int w;
-        if (sr <= 15) {
-            w = (int)(((ady < 8 ? dlo : dhi) >> (4 * (ady & 7))) & 0xFu);
-        } else {
-            const int lim = sr * sr - dy * dy;
-            w = (int)__builtin_sqrtf((float)lim);
-            while (w * w > lim) w--;
-            while ((w + 1) * (w + 1) <= lim) w++;
-        }
-        const int x0 = max(0, x - w), x1 = min(W - 1, x + w);
-        for (int k = x0 >> 5; k <= (x1 >> 5); k++) {
-            const int lo = max(x0, 32 * k) - 32 * k, hi = min(x1, 32 * k + 31) - 32 * k;
-            const uint32_t b = (hi - lo == 31) ? 0xFFFFFFFFu : (((1u << (hi - lo + 1)) - 1u) << lo);
-            atomicOr(&rows[yy * WPR + k], b);
-        }
-    }
 }
 
 // KDyn option tests that the steady instance (`steady`: Game's and k_env's template parameter) knows the answer to:
@@ -6227,758 +5896,6 @@ __global__ __launch_bounds__(HELP ? 128 : 64, (HELP || FIX == 16) ? 4 : 1) void 
 #endif
 }
 
-// ---------------------------------------------------------------- random policy (bench / rollouts)
-DEV void sampleBits(const PolicyParams& Q, uint64_t lo, uint64_t hi, int slot, int c, int32_t a[7]) {
-    sampleBitsRaw(Q.seed, Q.step, Q.slot_id_base + (uint32_t)slot, Q.ntypes, Q.K, lo, hi, c, a);
-}
-DEV void sampleCell(const PolicyParams& Q, const uint8_t* m, int slot, int c, int32_t a[7]) {
-    for (int k = 0; k < 7; k++) a[k] = 0;
-    if (!m[0]) return;
-    uint64_t lo = 0, hi = 0;
-    for (int i = 1; i < Q.K; i++) {
-        const uint64_t b = m[i] ? 1ull : 0ull;
-        if (i - 1 < 64) lo |= b << (i - 1);
-        else hi |= b << (i - 1 - 64);
-    }
-    sampleBits(Q, lo, hi, slot, c, a);
-}
-// 16 mask bytes (0 / non-zero) -> 16 bits, byte k -> bit k
-DEV uint32_t nz4(uint32_t w) {
-    uint32_t t = w | (w >> 4);
-    t |= t >> 2;
-    t |= t >> 1;
-    return ((t & 0x01010101u) * 0x01020408u) >> 24;
-}
-DEV uint32_t pack16(uint4 v) { return nz4(v.x) | (nz4(v.y) << 4) | (nz4(v.z) << 8) | (nz4(v.w) << 12); }
-
-// Tiled form: one wave = 64 cells of one slot.  The 64 mask records (64*K bytes, 16-B aligned when
-// HW*K and 64*K are multiples of 16) stream in with dwordx4 loads and are packed to bits in
-// registers on arrival (LDS holds 1 bit per mask byte); the 64 action rows (1792 B) stream out of
-// LDS with dwordx4 stores.
-__global__ __launch_bounds__(64) void k_policy_tiled(PolicyParams Q) {
-    __shared__ uint16_t tb[64 * 96 / 16 + 8];
-    __shared__ __align__(16) int32_t sa[64 * 7];
-    const int lane = (int)threadIdx.x, slot = (int)blockIdx.y;
-    const int c0 = (int)blockIdx.x * 64;
-    const int ncell = min(64, Q.HW - c0);
-    const uint8_t* src = Q.masks + ((size_t)slot * Q.HW + c0) * Q.K;
-    const int nbytes = ncell * Q.K, n16 = nbytes >> 4;
-    for (int i = lane; i < n16; i += 64) tb[i] = (uint16_t)pack16(((const uint4*)src)[i]);
-    if (lane == 0 && (nbytes & 15)) {
-        uint32_t b = 0;
-        for (int i = 16 * n16; i < nbytes; i++) b |= (src[i] ? 1u : 0u) << (i - 16 * n16);
-        tb[n16] = (uint16_t)b;
-    }
-    __syncthreads();
-    int32_t a[7] = {0, 0, 0, 0, 0, 0, 0};
-    if (lane < ncell) {
-        const int b0 = lane * Q.K;
-        if ((tb[b0 >> 4] >> (b0 & 15)) & 1) {
-            // bits b0+1 .. b0+K-1 -> lo/hi
-            const int s = b0 + 1, w0 = s >> 4, sh = s & 15;
-            uint64_t x0 = 0, x1 = 0;
-#pragma unroll
-            for (int j = 0; j < 4; j++) x0 |= (uint64_t)tb[w0 + j] << (16 * j);
-#pragma unroll
-            for (int j = 0; j < 3; j++) x1 |= (uint64_t)tb[w0 + 4 + j] << (16 * j);
-            uint64_t lo = sh ? ((x0 >> sh) | (x1 << (64 - sh))) : x0;
-            uint64_t hi = x1 >> sh;
-            const int nb = Q.K - 1;  // valid bits
-            if (nb < 64) {
-                lo &= (1ull << nb) - 1;
-                hi = 0;
-            } else if (nb < 128) {
-                hi &= (1ull << (nb - 64)) - 1;
-            }
-            sampleBits(Q, lo, hi, slot, c0 + lane, a);
-        }
-    }
-#pragma unroll
-    for (int k = 0; k < 7; k++) sa[lane * 7 + k] = a[k];
-    __syncthreads();
-    int32_t* dst = Q.actions + ((size_t)slot * Q.HW + c0) * 7;
-    const int nw = ncell * 7, nw4 = nw >> 2;
-    for (int i = lane; i < nw4; i += 64) ((int4*)dst)[i] = ((const int4*)sa)[i];
-    for (int i = 4 * nw4 + lane; i < nw; i += 64) dst[i] = sa[i];
-}
-
-// one candidate cell's action from its K-byte mask record: record bits 0..K-1 gathered from the
-// covering aligned 16-B chunks (chunk q's byte 0 sits at record bit pos = 16q - b0)
-DEV void sampleRecord(const PolicyParams& Q, const uint8_t* mrec, int slot, int c, int32_t row[7]) {
-    const int b0 = c * Q.K, j0 = b0 >> 4, j1 = (b0 + Q.K - 1) >> 4;
-    uint64_t r0 = 0, r1 = 0;
-    for (int q = j0; q <= j1; q++) {
-        const uint64_t b16 = pack16(((const uint4*)mrec)[q]);
-        const int pos = 16 * q - b0;
-        if (pos < 0) {
-            r0 |= b16 >> (-pos);
-        } else if (pos < 64) {
-            r0 |= b16 << pos;
-            if (pos > 48) r1 |= b16 >> (64 - pos);
-        } else {
-            r1 |= b16 << (pos - 64);
-        }
-    }
-    // record bits 1..K-1 -> lo/hi (bit i -> bit i-1)
-    uint64_t lo = (r0 >> 1) | (r1 << 63), hi = r1 >> 1;
-    const int nb = Q.K - 1;
-    if (nb < 64) {
-        lo &= (1ull << nb) - 1;
-        hi = 0;
-    } else {
-        hi &= (1ull << (nb - 64)) - 1;
-    }
-    sampleBits(Q, lo, hi, slot, c, row);
-}
-
-// Source-bit form: one wave = one slot.  Candidate cells come from the env's source bits; only their
-// mask records are read (the <= 6 aligned 16-B chunks covering each).  Rows are composed in LDS,
-// 256 cells (7 KB) at a time, and leave with coalesced dwordx4 stores.
-__global__ __launch_bounds__(64) void k_policy_src(PolicyParams Q) {
-    __shared__ __align__(16) int32_t sa[256 * 7];
-    const int lane = (int)threadIdx.x, slot = (int)blockIdx.x;
-    const int MW = (Q.HW + 31) / 32;
-    const uint32_t* src = Q.source + (size_t)slot * MW;
-    const uint8_t* mrec = Q.masks + (size_t)slot * Q.HW * Q.K;
-    int32_t* dst = Q.actions + (size_t)slot * Q.HW * 7;
-    for (int c0 = 0; c0 < Q.HW; c0 += 256) {
-        const int ncell = min(256, Q.HW - c0);
-#pragma unroll
-        for (int j = 0; j < 4; j++) {
-            const int c = c0 + 64 * j + lane;
-            int32_t row[7] = {0, 0, 0, 0, 0, 0, 0};
-            if (c < Q.HW && ((src[c >> 5] >> (c & 31)) & 1u)) sampleRecord(Q, mrec, slot, c, row);
-            const int r = 64 * j + lane;  // stride-7 words: conflict-free LDS writes
-#pragma unroll
-            for (int k = 0; k < 7; k++) sa[r * 7 + k] = row[k];
-        }
-        __syncthreads();
-        int32_t* d = dst + (size_t)c0 * 7;
-        const int nw = ncell * 7, nw4 = nw >> 2;
-        for (int i = lane; i < nw4; i += 64) ((int4*)d)[i] = ((const int4*)sa)[i];
-        for (int i = 4 * nw4 + lane; i < nw; i += 64) d[i] = sa[i];
-        __syncthreads();
-    }
-    if (Q.prev_out)
-        for (int w = lane; w < MW; w += 64) Q.prev_out[(size_t)slot * MW + w] = src[w];
-}
-
-// Delta form (actions holds this policy's previous output, whose candidate set is prev): only rows
-// in prev | source change — candidates get a fresh action, former candidates a zero row.  A wave
-// takes 64 (slot, 32-cell bit word) items in one load round, compacts their dirty cells into an LDS
-// list (wave prefix sum), and spreads the list over its lanes, so each dirty row costs one record
-// round trip in parallel with the others.  The candidate set is double-buffered (prev -> prev_out).
-__global__ __launch_bounds__(64) void k_policy_delta(PolicyParams Q) {
-    __shared__ uint32_t list[64 * 32];
-    const int lane = (int)threadIdx.x;
-    const uint32_t MW = (uint32_t)(Q.HW + 31) / 32;
-    const uint32_t nitems = (uint32_t)Q.n_slots * MW;
-    const uint32_t item = blockIdx.x * 64u + (uint32_t)lane;
-    const bool valid = item < nitems;
-    const uint32_t cur = valid ? Q.source[item] : 0u, old = valid ? Q.prev[item] : 0u;
-    if (valid) Q.prev_out[item] = cur;
-    const uint32_t dirty = cur | old;
-    const int n = __popc(dirty);
-    const int incl = wave_incl_sum(n);  // inclusive prefix sum over lanes
-    const int total = rl(incl, 63);
-    if (total == 0) return;
-    const uint32_t slot = item / MW, w = item - slot * MW;
-    int k = incl - n;
-    for (uint32_t d = dirty; d; d &= d - 1) {
-        const int b = __builtin_ctz(d);
-        // row index slot*HW + cell (< 2^31 by the host's size checks), bit 31 = candidate
-        list[k++] = (slot * (uint32_t)Q.HW + 32u * w + (uint32_t)b) | (((cur >> b) & 1u) << 31);
-    }
-    __syncthreads();
-    for (int i = lane; i < total; i += 64) {
-        const uint32_t e = list[i], r = e & 0x7FFFFFFFu;
-        const int sl = (int)(r / (uint32_t)Q.HW), c = (int)(r - (uint32_t)sl * Q.HW);
-        int32_t row[7] = {0, 0, 0, 0, 0, 0, 0};
-        if (e >> 31) sampleRecord(Q, Q.masks + (size_t)sl * Q.HW * Q.K, sl, c, row);
-        int32_t* dst = Q.actions + (size_t)r * 7;
-#pragma unroll
-        for (int q = 0; q < 7; q++) dst[q] = row[q];
-    }
-}
-
-__global__ __launch_bounds__(64) void k_policy(PolicyParams Q) {
-    const int c = (int)(blockIdx.x * 64 + threadIdx.x);
-    const int slot = (int)blockIdx.y;
-    if (c >= Q.HW) return;
-    int32_t a[7];
-    sampleCell(Q, Q.masks + ((size_t)slot * Q.HW + c) * Q.K, slot, c, a);
-    int32_t* out = Q.actions + ((size_t)slot * Q.HW + c) * 7;
-#pragma unroll
-    for (int k = 0; k < 7; k++) out[k] = a[k];
-}
-
-// ---------------------------------------------------------------- masked policy head
-// Logits [rows][HW][K-1] (logit j <-> mask slot j + 1) -> per candidate cell (mask slot 0) one independent masked
-// categorical per non-empty field: type [0,6), the four directions [6,22), produce type [22,22+ntypes), attack
-// window [22+ntypes,K-1).  One wave per row; a candidate cell is worked by a 16-lane DPP row, four cells at a
-// time.  A lane owns one logit of the type field, one of the 16 direction logits (a field per quad), one produce
-// type and four consecutive attack-window logits, so every field is one quad or one row and its maximum, sums
-// and running sum are DPP operations inside it.
-constexpr uint32_t HEAD_TAG = 0x48454144u;  // "HEAD": Philox counter word 3 (and HEAD_TAG + 1), apart from 0 / UNIFORM_TAG
-
-template <int CTRL, int ROWS = 0xF>
-DEV float dppF(float old, float v) {
-    return __int_as_float(__builtin_amdgcn_update_dpp(__float_as_int(old), __float_as_int(v), CTRL, ROWS, 0xF, false));
-}
-// max / sum over each W-lane segment (a quad or a 16-lane row), the result on every lane of it: each step
-// combines two values that are already equal across the lanes they came from, so the lanes agree bit for bit
-template <int W>
-DEV float segMax(float v) {
-    LANE_AUDIT_WAVE(2);
-    v = fmaxf(v, dppF<0xB1>(v, v));  // quad_perm [1,0,3,2]
-    v = fmaxf(v, dppF<0x4E>(v, v));  // quad_perm [2,3,0,1]
-    if (W == 16) {
-        v = fmaxf(v, dppF<0x141>(v, v));  // row_half_mirror
-        v = fmaxf(v, dppF<0x140>(v, v));  // row_mirror
-    }
-    return v;
-}
-template <int W>
-DEV float segSum(float v) {
-    LANE_AUDIT_WAVE(2);
-    v += dppF<0xB1>(v, v);
-    v += dppF<0x4E>(v, v);
-    if (W == 16) {
-        v += dppF<0x141>(v, v);
-        v += dppF<0x140>(v, v);
-    }
-    return v;
-}
-// inclusive running sum over each segment, in lane order (ql: the lane's index in its segment)
-template <int W>
-DEV float segScan(float v, int ql) {
-    LANE_AUDIT_WAVE(2);
-    if (W == 16) {
-        v += dppF<0x111>(0.f, v);  // row_shr:1 (lanes shifted in from outside the row read 0)
-        v += dppF<0x112>(0.f, v);
-        v += dppF<0x114>(0.f, v);
-        v += dppF<0x118>(0.f, v);
-    } else {
-        const float t1 = dppF<0x90>(0.f, v);  // quad_perm [0,0,1,2]
-        v += ql >= 1 ? t1 : 0.f;
-        const float t2 = dppF<0x40>(0.f, v);  // quad_perm [0,0,0,1]
-        v += ql >= 2 ? t2 : 0.f;
-    }
-    return v;
-}
-// a double through DPP as its two halves (lanes without a source read 0.0)
-template <int CTRL, int ROWS = 0xF>
-DEV double dppD(double v) {
-    const uint64_t b = (uint64_t)__double_as_longlong(v);
-    const uint32_t lo = (uint32_t)__builtin_amdgcn_update_dpp(0, (int)(uint32_t)b, CTRL, ROWS, 0xF, false);
-    const uint32_t hi = (uint32_t)__builtin_amdgcn_update_dpp(0, (int)(uint32_t)(b >> 32), CTRL, ROWS, 0xF, false);
-    return __longlong_as_double((long long)(((uint64_t)hi << 32) | lo));
-}
-// sum over the wave in a fixed order (wave_reduce's DPP chain on doubles): a row's log-probability and entropy add
-// up to 64 x 7 fp32 terms per lane, and double partial sums keep their rounding below that of the terms
-DEV double waveSumD(double v) {
-    LANE_AUDIT_WAVE(2);
-    v += dppD<0xB1>(v);
-    v += dppD<0x4E>(v);
-    v += dppD<0x141>(v);
-    v += dppD<0x140>(v);
-    v += dppD<0x142, 0xA>(v);
-    v += dppD<0x143, 0xC>(v);
-    const uint64_t b = (uint64_t)__double_as_longlong(v);
-    const uint32_t lo = (uint32_t)rl((int)(uint32_t)b, 63), hi = (uint32_t)rl((int)(uint32_t)(b >> 32), 63);
-    return __longlong_as_double((long long)(((uint64_t)hi << 32) | lo));
-}
-
-// one candidate cell as its 16-lane row sees it
-struct HeadCell {
-    bool act;             // the row has a cell this round
-    const float* lrow;    // its K-1 logits
-    const uint8_t* mrec;  // its K mask bytes
-    const int32_t* arow;  // SCORE / GRAD: its given action row
-    int32_t* srow;        // SAMPLE: its action row in LDS (zeroed)
-    float* grow;          // GRAD: its gradient row in LDS (zeroed)
-    float glp, gent;      // GRAD: the row's upstream gradients
-    double lp, ent;       // per-lane partial sums of the row's log-probability and entropy (fp32 terms)
-    uint32_t w0, wd, w5, w6;  // SAMPLE: the Philox words of the lane's fields (type, its direction field, produce type, attack)
-};
-
-// One field, NE logits per lane (l / set: the lane's logits and mask bits, 0 / false outside the field), the field
-// spanning a W-lane segment.  idx0: the field-local index of l[0]; a: the given component (SCORE / GRAD).
-template <int MODE, int NE, int W>
-DEV void headField(HeadCell& X, int lane, const float* l, const bool* set, int j0, int idx0, int field, uint32_t word, int a) {
-#pragma clang fp contract(off)
-    const int ql = lane & (W - 1), segbase = lane - ql;
-    const uint32_t segmask = (1u << W) - 1u;
-    float mx = -INFINITY;
-    bool anyset = false;
-#pragma unroll
-    for (int k = 0; k < NE; k++) {
-        mx = set[k] ? fmaxf(mx, l[k]) : mx;
-        anyset |= set[k];
-    }
-    mx = segMax<W>(mx);
-    const uint32_t sb = (uint32_t)(ballot(anyset) >> segbase) & segmask;
-    const bool nonempty = sb != 0;
-    float e[NE], lt = 0.f, tt = 0.f;
-#pragma unroll
-    for (int k = 0; k < NE; k++) {
-        const float d = l[k] - mx;
-        e[k] = set[k] ? expf(d) : 0.f;
-        lt += e[k];
-        tt += set[k] ? e[k] * d : 0.f;
-    }
-    const float S = segSum<W>(lt), T = segSum<W>(tt);
-    const float logS = logf(S), H = logS - T / S;
-    X.ent += (nonempty && ql == 0) ? (double)H : 0.0;
-    if (MODE == HEAD_SAMPLE) {
-        // the smallest set bit whose running sum exceeds u * S, else (rounding) the last set bit
-        const float thr = (float)(word >> 8) * 0x1p-24f * S;
-        float run = segScan<W>(lt, ql);
-        if (NE > 1) run = dppF<0x111>(0.f, run);  // exclusive: the lanes before this one
-        bool hit[NE], anyhit = false;
-#pragma unroll
-        for (int k = 0; k < NE; k++) {
-            if (NE > 1) run += e[k];
-            hit[k] = set[k] && run > thr;
-            anyhit |= hit[k];
-        }
-        const uint32_t hb = (uint32_t)(ballot(anyhit) >> segbase) & segmask;
-        const int pick = hb ? __builtin_ctz(hb) : (sb ? 31 - __builtin_clz(sb) : 0);
-        int kk = -1;
-        float dsel = 0.f;
-#pragma unroll
-        for (int k = NE - 1; k >= 0; k--)
-            if (hit[k]) {
-                kk = k;
-                dsel = l[k] - mx;
-            }
-        if (kk < 0) {
-#pragma unroll
-            for (int k = 0; k < NE; k++)
-                if (set[k]) {
-                    kk = k;
-                    dsel = l[k] - mx;
-                }
-        }
-        if (nonempty && ql == pick) {
-            X.srow[field] = idx0 + kk;
-            X.lp += (double)(dsel - logS);
-        }
-    } else {
-        bool match[NE], anym = false;
-#pragma unroll
-        for (int k = 0; k < NE; k++) {
-            match[k] = set[k] && idx0 + k == a;
-            anym |= match[k];
-        }
-        const bool hasA = ((uint32_t)(ballot(anym) >> segbase) & segmask) != 0;
-        if (MODE == HEAD_SCORE) {
-#pragma unroll
-            for (int k = 0; k < NE; k++) X.lp += match[k] ? (double)((l[k] - mx) - logS) : 0.0;
-            // a component outside the field's set bits: the row's log-probability is -inf
-            X.lp += (nonempty && !hasA && ql == 0) ? (double)-INFINITY : 0.0;
-        } else {
-#pragma unroll
-            for (int k = 0; k < NE; k++)
-                if (set[k]) {
-                    const float p = e[k] / S, logp = (l[k] - mx) - logS;
-                    float gv = X.gent * (-p * (logp + H));
-                    if (hasA) gv += X.glp * ((match[k] ? 1.f : 0.f) - p);
-                    X.grow[j0 + k] = gv;
-                }
-        }
-    }
-}
-
-template <int MODE>
-DEV void headCell(HeadCell& X, const HeadParams& Q, int lane) {
-    const int q = lane & 15, nt = Q.ntypes, natt = Q.K - 23 - nt;
-    // the lane's seven logits: 0 type, 1 a direction (quad = field), 2 produce type, 3..6 attack window 4q..4q+3
-    int j[7];
-    bool in[7];
-    j[0] = q, in[0] = q < 6;
-    j[1] = 6 + q, in[1] = true;
-    j[2] = 22 + q, in[2] = q < nt;
-#pragma unroll
-    for (int k = 0; k < 4; k++) j[3 + k] = 22 + nt + 4 * q + k, in[3 + k] = 4 * q + k < natt;
-    // Unconditional loads (a lane without a logit of the field, or a row without a cell this round, reads logit 0
-    // of a cell of the chunk): all fourteen are in flight together, one memory round per cell.  The logit of a
-    // cleared bit comes with its row's cache lines and is dropped by the select: it never reaches the arithmetic.
-    float l[7];
-    bool set[7];
-#pragma unroll
-    for (int i = 0; i < 7; i++) {
-        const int jj = in[i] ? j[i] : 0;
-        const uint32_t mb = X.mrec[1 + jj];
-        const float lv = X.lrow[jj];
-        set[i] = X.act && in[i] && mb != 0;
-        l[i] = set[i] ? lv : 0.f;
-    }
-    const int dq = q >> 2;
-    int a0 = 0, a1 = 0, a5 = 0, a6 = 0;
-    if (MODE != HEAD_SAMPLE && X.act) a0 = X.arow[0], a1 = X.arow[1 + dq], a5 = X.arow[5], a6 = X.arow[6];
-    headField<MODE, 1, 16>(X, lane, l + 0, set + 0, j[0], q, 0, X.w0, a0);
-    headField<MODE, 1, 4>(X, lane, l + 1, set + 1, j[1], q & 3, 1 + dq, X.wd, a1);
-    headField<MODE, 1, 16>(X, lane, l + 2, set + 2, j[2], q, 5, X.w5, a5);
-    headField<MODE, 4, 16>(X, lane, l + 3, set + 3, j[3], 4 * q, 6, X.w6, a6);
-}
-
-// nw words of a chunk to global memory as dwordx4 where whole vectors lie inside it: LDS word t <-> gp[t], the
-// chunk at t in [a, a + nw) with gp 16-byte aligned (a = the chunk's word offset in its vector).  lds null: zeros.
-DEV void headFlush(const int32_t* lds, int32_t* gp, int a, int nw, int lane) {
-    const int nv = (a + nw + 3) >> 2;
-    for (int v = lane; v < nv; v += 64) {
-        const int t = 4 * v;
-        const int4 x = lds ? ((const int4*)lds)[v] : make_int4(0, 0, 0, 0);
-        if (t >= a && t + 4 <= a + nw) {
-            ((int4*)gp)[v] = x;
-        } else {
-            const int xs[4] = {x.x, x.y, x.z, x.w};
-#pragma unroll
-            for (int k = 0; k < 4; k++)
-                if (t + k >= a && t + k < a + nw) gp[t + k] = xs[k];
-        }
-    }
-}
-
-// One wave per row.  Per 64 cells: the candidate bits (source bits, or mask byte 0) as one ballot; SAMPLE / GRAD
-// compose the chunk's action / gradient rows in zeroed LDS and store them with dwordx4, a chunk without a
-// candidate as plain zero stores.  The row's log-probability and entropy are per-lane partial sums added up by one
-// DPP chain at the end: a fixed order, no atomics.
-template <int MODE>
-__global__ __launch_bounds__(64) void k_head(HeadParams Q) {
-    __shared__ __align__(16) int32_t sbuf[(MODE == HEAD_GRAD ? 64 * HEAD_MAX_LOGITS : MODE == HEAD_SAMPLE ? 64 * 7 : 0) + 8];
-    const int lane = (int)threadIdx.x, row = (int)blockIdx.x, KL = Q.K - 1;
-    const int RW = MODE == HEAD_GRAD ? KL : 7;  // words per cell of what this mode writes
-    const size_t cell0 = (size_t)row * Q.HW;
-    const uint32_t* src = (MODE == HEAD_SAMPLE && Q.source) ? Q.source + (size_t)row * ((Q.HW + 31) / 32) : nullptr;
-    int32_t* out = MODE == HEAD_GRAD ? (int32_t*)Q.grad : Q.actions;
-    HeadCell X;
-    X.lp = X.ent = 0.0;
-    X.glp = X.gent = 0.f;
-    if (MODE == HEAD_GRAD) {
-        if (Q.g_logprob) X.glp = Q.g_logprob[row];
-        if (Q.g_entropy) X.gent = Q.g_entropy[row];
-    }
-    for (int c0 = 0; c0 < Q.HW; c0 += 64) {
-        const int ncell = min(64, Q.HW - c0), c = c0 + lane;
-        bool cand = false;
-        if (c < Q.HW) cand = src ? ((src[c >> 5] >> (c & 31)) & 1u) != 0 : Q.masks[(cell0 + c) * Q.K] != 0;
-        uint64_t m = ballot(cand);
-        int32_t* gp = nullptr;
-        int a = 0, nw = 0;
-        if (MODE != HEAD_SCORE) {
-            int32_t* p = out + (cell0 + c0) * RW;
-            a = (int)(((uintptr_t)p >> 2) & 3);
-            gp = p - a;
-            nw = ncell * RW;
-            if (m == 0) {
-                headFlush(nullptr, gp, a, nw, lane);
-                continue;
-            }
-            for (int v = lane; v < ((a + nw + 3) >> 2); v += 64) ((int4*)sbuf)[v] = make_int4(0, 0, 0, 0);
-            __syncthreads();
-        } else if (m == 0) {
-            continue;
-        }
-        while (m) {  // four candidate cells per round, the g-th to row g
-            int cl = -1;
-#pragma unroll
-            for (int g = 0; g < 4; g++)
-                if (m) {
-                    const int b = __builtin_ctzll(m);
-                    m &= m - 1;
-                    cl = (lane >> 4) == g ? b : cl;
-                }
-            X.act = cl >= 0;
-            const size_t cell = cell0 + c0 + (cl >= 0 ? cl : 0);
-            X.lrow = Q.logits + cell * KL;
-            X.mrec = Q.masks + cell * Q.K;
-            X.arow = Q.actions + cell * 7;
-            X.srow = sbuf + a + (cl >= 0 ? cl : 0) * 7;
-            X.grow = (float*)sbuf + a + (cl >= 0 ? cl : 0) * KL;
-            if (MODE == HEAD_SAMPLE) {
-                const uint32_t sid = Q.slot_id_base + (uint32_t)row, cc = (uint32_t)(c0 + (cl >= 0 ? cl : 0));
-                uint32_t c1[4] = {sid, Q.step, cc, HEAD_TAG}, c2[4] = {sid, Q.step, cc, HEAD_TAG + 1u};
-                philox(c1, (uint32_t)Q.seed, (uint32_t)(Q.seed >> 32));
-                philox(c2, (uint32_t)Q.seed, (uint32_t)(Q.seed >> 32));
-                // eight words, field f's uniform from word f; the lane's direction field is 1 + its quad
-                const uint32_t p1 = c1[1], p2 = c1[2], p3 = c1[3], p4 = c2[0];
-                const int dq = (lane >> 2) & 3;
-                X.w0 = c1[0];
-                X.wd = dq == 0 ? p1 : dq == 1 ? p2 : dq == 2 ? p3 : p4;
-                X.w5 = c2[1];
-                X.w6 = c2[2];
-            }
-            headCell<MODE>(X, Q, lane);
-        }
-        if (MODE != HEAD_SCORE) {
-            __syncthreads();
-            headFlush(sbuf, gp, a, nw, lane);
-            __syncthreads();
-        }
-    }
-    if (MODE != HEAD_GRAD) {
-        const float lp = (float)waveSumD(X.lp), ent = (float)waveSumD(X.ent);
-        if (lane == 0) {
-            if (Q.logprob) Q.logprob[row] = lp;
-            if (Q.entropy) Q.entropy[row] = ent;
-        }
-    }
-}
-
-// ---- Packed policy rows (include/mrts.h): the candidates of a row as HEAD_CW words each, for rollout storage ----
-// an action component's code: itself inside [0, off), else off (off = all ones of the component's bits, beyond
-// every field's width: a component the dense score finds outside its field's set bits stays outside them)
-DEV uint32_t headActWord(const int32_t* a) {
-    uint32_t w = 0;
-#pragma unroll
-    for (int f = 0; f < 7; f++) {
-        const uint32_t off = (1u << HEAD_ACT_BITS[f]) - 1u, v = (uint32_t)a[f];
-        w |= (v < off ? v : off) << HEAD_ACT_SHIFT[f];
-    }
-    return w;
-}
-DEV int32_t headActComp(uint32_t w, int f) {
-    int sh = 0, bits = 0;
-#pragma unroll
-    for (int k = 0; k < 7; k++)
-        if (k == f) sh = HEAD_ACT_SHIFT[k], bits = HEAD_ACT_BITS[k];
-    const uint32_t off = (1u << bits) - 1u, v = (w >> sh) & off;
-    return v == off ? -1 : (int32_t)v;
-}
-// four mask bits as four 0 / 1 bytes
-DEV uint32_t headSpread4(uint32_t b) { return (b & 1u) | ((b & 2u) << 7) | ((b & 4u) << 14) | ((b & 8u) << 21); }
-DEV uint32_t headBits4(uint32_t b0, uint32_t b1, uint32_t b2, int w) {  // bits 4w..4w+3 of the 96
-    const uint32_t x = w < 8 ? b0 : w < 16 ? b1 : b2;
-    return (x >> (4 * (w & 7))) & 15u;
-}
-// the packed row a block works: packed row index[row] (row without an index); ok false when that is out of range
-DEV const uint32_t* headPackedRow(const HeadPackedParams& P, int row, bool& ok) {
-    const int64_t pr = P.index ? (int64_t)P.index[row] : (int64_t)row;
-    ok = pr >= 0 && pr < (int64_t)P.n_packed;
-    return P.packed + (size_t)(ok ? pr : 0) * (size_t)P.words;
-}
-constexpr int HEAD_STG = 128;  // candidates k_head_pack stages in LDS between flushes (a chunk adds at most 64)
-
-// One wave per row.  Per 64 cells the candidate bits (source bits, or mask byte 0) as one ballot, as k_head finds
-// them; a candidate's slot in the row is the count before its chunk plus the candidates below its lane.  The
-// candidate's own lane adds its cell and action word, the wave reads its mask record (two bytes per lane) and two
-// ballots give the bits.  The row is composed in LDS and stored with dwordx4 (headFlush), count word and zero tail
-// included; a row of more than HEAD_STG candidates flushes in between.
-__global__ __launch_bounds__(64) void k_head_pack(HeadPackedParams P) {
-    __shared__ __align__(16) int32_t stg[4 + 1 + HEAD_STG * HEAD_CW + 3];
-    const HeadParams& Q = P.H;
-    const int lane = (int)threadIdx.x, row = (int)blockIdx.x;
-    const size_t cell0 = (size_t)row * Q.HW;
-    const uint32_t* src = Q.source ? Q.source + (size_t)row * ((Q.HW + 31) / 32) : nullptr;
-    int32_t* orow = (int32_t*)P.packed_out + (size_t)row * (size_t)P.words;
-    // staged: the row's words [r0, r0 + rn) at stg[a + (word - r0)], orow + r0 - a 16-byte aligned
-    int total = 0, r0 = 0, rn = 1, a = (int)(((uintptr_t)orow >> 2) & 3);
-    for (int c0 = 0; c0 < Q.HW; c0 += 64) {
-        const int c = c0 + lane;
-        bool cand = false;
-        if (c < Q.HW) cand = src ? ((src[c >> 5] >> (c & 31)) & 1u) != 0 : Q.masks[(cell0 + c) * Q.K] != 0;
-        const uint64_t m = ballot(cand);
-        if (m == 0) continue;
-        const int nc = __builtin_popcountll(m), keep = max(0, min(nc, P.cap - total));
-        total += nc;
-        if (keep == 0) continue;
-        if (rn + keep * HEAD_CW > 1 + HEAD_STG * HEAD_CW) {  // word 0 waits for the count
-            __syncthreads();
-            if (r0 == 0) headFlush(stg, orow - a, a + 1, rn - 1, lane);
-            else headFlush(stg, orow + r0 - a, a, rn, lane);
-            __syncthreads();
-            r0 += rn;
-            rn = 0;
-            a = (int)(((uintptr_t)(orow + r0) >> 2) & 3);
-        }
-        int32_t* s = stg + a + rn;
-        const int pos = lanes_below(m);
-        if (cand && pos < keep) {
-            s[pos * HEAD_CW] = c;
-            s[pos * HEAD_CW + 1] = (int32_t)headActWord(Q.actions + (cell0 + c) * 7);
-        }
-        uint64_t mm = m;
-        for (int k = 0; k < keep; k++) {
-            const uint8_t* rec = Q.masks + (cell0 + c0 + __builtin_ctzll(mm)) * Q.K;
-            mm &= mm - 1;
-            const bool v0 = lane < Q.K && rec[lane < Q.K ? lane : 0] != 0;
-            const bool v1 = lane + 64 < Q.K && rec[lane + 64 < Q.K ? lane + 64 : 0] != 0;
-            const uint64_t b0 = ballot(v0), b1 = ballot(v1);
-            if (lane == 0) {
-                s[k * HEAD_CW + 2] = (int32_t)(uint32_t)b0;
-                s[k * HEAD_CW + 3] = (int32_t)(uint32_t)(b0 >> 32);
-                s[k * HEAD_CW + 4] = (int32_t)(uint32_t)b1;
-            }
-        }
-        rn += keep * HEAD_CW;
-    }
-    if (lane == 0) {
-        if (r0 == 0) stg[a] = total;
-        else orow[0] = total;
-        if (total > P.cap) atomicAdd(P.overflow, 1ull);
-    }
-    __syncthreads();
-    headFlush(stg, orow + r0 - a, a, rn, lane);
-    const int t0 = r0 + rn, a2 = (int)(((uintptr_t)(orow + t0) >> 2) & 3);
-    headFlush(nullptr, orow + t0 - a2, a2, P.words - t0, lane);
-}
-
-// nb bytes of a chunk to global memory as dwordx4 where whole vectors lie inside it: LDS byte t <-> gp[t], the chunk
-// at t in [a, a + nb) with gp 16-byte aligned.  lds null: zeros.
-DEV void headFlushBytes(const uint8_t* lds, uint8_t* gp, int a, int nb, int lane) {
-    const int nv = (a + nb + 15) >> 4;
-    for (int v = lane; v < nv; v += 64) {
-        const int t = 16 * v;
-        if (t >= a && t + 16 <= a + nb) {
-            ((int4*)gp)[v] = lds ? ((const int4*)lds)[v] : make_int4(0, 0, 0, 0);
-        } else {
-            for (int k = 0; k < 16; k++)
-                if (t + k >= a && t + k < a + nb) gp[t + k] = lds ? lds[t + k] : (uint8_t)0;
-        }
-    }
-}
-
-// The canonical dense form of packed rows, one wave per row: per 64 cells the chunk's mask records (0 / 1 bytes)
-// and action rows composed in zeroed LDS from the row's candidates of that chunk, then stored whole — every byte of
-// both outputs is written.  A count above cap gives its first cap candidates; a cell outside the map or out of
-// order and an index outside the packed rows give nothing.
-__global__ __launch_bounds__(64) void k_head_unpack(HeadPackedParams P) {
-    __shared__ __align__(16) uint8_t smask[16 + 64 * (HEAD_MAX_LOGITS + 1) + 16];
-    __shared__ __align__(16) int32_t sact[4 + 64 * 7 + 4];
-    const HeadParams& Q = P.H;
-    const int lane = (int)threadIdx.x, row = (int)blockIdx.x;
-    const size_t cell0 = (size_t)row * Q.HW;
-    bool ok;
-    const uint32_t* prow = headPackedRow(P, row, ok);
-    const uint32_t n = ok ? min(prow[0], (uint32_t)P.cap) : 0u;
-    uint32_t i0 = 0;
-    for (int c0 = 0; c0 < Q.HW; c0 += 64) {
-        const int ncell = min(64, Q.HW - c0);
-        uint8_t* mp = P.masks_out + (cell0 + c0) * Q.K;
-        int32_t* ap = P.actions_out + (cell0 + c0) * 7;
-        const int am = (int)((uintptr_t)mp & 15), aa = (int)(((uintptr_t)ap >> 2) & 3);
-        const int nb = ncell * Q.K, nw = ncell * 7;
-        for (int v = lane; v < ((am + nb + 15) >> 4); v += 64) ((int4*)smask)[v] = make_int4(0, 0, 0, 0);
-        for (int v = lane; v < ((aa + nw + 3) >> 2); v += 64) ((int4*)sact)[v] = make_int4(0, 0, 0, 0);
-        __syncthreads();
-        while (i0 < n) {
-            const uint32_t* cw = prow + 1 + (size_t)i0 * HEAD_CW;
-            const uint32_t cell = cw[0];
-            if ((cell >> 6) != (uint32_t)(c0 >> 6)) break;
-            i0++;
-            if (cell >= (uint32_t)Q.HW) continue;
-            const int cl = (int)(cell & 63u);
-            const uint32_t aw = cw[1], b0 = cw[2], b1 = cw[3], b2 = cw[4];
-            if (lane < Q.K) smask[am + cl * Q.K + lane] = (uint8_t)((lane < 32 ? b0 >> lane : b1 >> (lane - 32)) & 1u);
-            if (lane + 64 < Q.K) smask[am + cl * Q.K + lane + 64] = (uint8_t)((b2 >> lane) & 1u);
-            if (lane < 7) sact[aa + cl * 7 + lane] = headActComp(aw, lane);
-        }
-        __syncthreads();
-        headFlushBytes(smask, mp - am, am, nb, lane);
-        headFlush(sact, ap - aa, aa, nw, lane);
-        __syncthreads();
-    }
-}
-
-// k_head's SCORE / GRAD on packed rows: logits row r against packed row index[r].  The rounds are k_head's — up to
-// four consecutive candidates of one 64-cell chunk (cell >> 6; the row is sorted by cell), the g-th to DPP row g —
-// so every lane's partial sums take the same terms in the same order and the results equal the dense kernels' bit
-// for bit.  Each round expands its candidates' mask bits to 0 / 1 bytes and their action words to components in
-// LDS, where headCell reads them as it reads the dense tensors.  The count and the candidate words are read at
-// wave-uniform addresses inside the row (clamped to cap), so the first round's words load with the count.  A row
-// whose count exceeds cap, or whose index is outside the packed rows, is NaN: logprob, entropy, gradient row.
-template <int MODE>
-__global__ __launch_bounds__(64) void k_head_packed(HeadPackedParams P) {
-    constexpr int XW = (HEAD_MAX_LOGITS + 1 + 3) / 4 + 7;  // per DPP row: the mask bytes, then the action row
-    __shared__ __align__(16) int32_t sbuf[(MODE == HEAD_GRAD ? 64 * HEAD_MAX_LOGITS : 0) + 8];
-    __shared__ __align__(16) uint32_t sexp[4 * XW];
-    const HeadParams& Q = P.H;
-    const int lane = (int)threadIdx.x, row = (int)blockIdx.x, KL = Q.K - 1, g = lane >> 4, q = lane & 15;
-    const size_t cell0 = (size_t)row * Q.HW;
-    bool ok;
-    const uint32_t* prow = headPackedRow(P, row, ok);
-    const uint32_t n = prow[0], last = (uint32_t)P.cap - 1u;
-    uint32_t i0 = 0, cc = prow[1];  // cc: the cell of candidate i0
-    if (!ok || n > (uint32_t)P.cap) {
-        const float nan = __int_as_float(0x7FC00000);
-        if (MODE == HEAD_GRAD) {
-            for (size_t t = lane; t < (size_t)Q.HW * KL; t += 64) Q.grad[cell0 * KL + t] = nan;
-        } else if (lane == 0) {
-            if (Q.logprob) Q.logprob[row] = nan;
-            if (Q.entropy) Q.entropy[row] = nan;
-        }
-        return;
-    }
-    HeadCell X;
-    X.lp = X.ent = 0.0;
-    X.glp = X.gent = 0.f;
-    X.srow = nullptr;
-    X.w0 = X.wd = X.w5 = X.w6 = 0;
-    if (MODE == HEAD_GRAD) {
-        if (Q.g_logprob) X.glp = Q.g_logprob[row];
-        if (Q.g_entropy) X.gent = Q.g_entropy[row];
-    }
-    uint32_t* xr = sexp + g * XW;
-    for (int c0 = 0; c0 < Q.HW; c0 += 64) {
-        const uint32_t chunk = (uint32_t)(c0 >> 6);
-        const bool has = i0 < n && (cc >> 6) == chunk;
-        int32_t* gp = nullptr;
-        int a = 0, nw = 0;
-        if (MODE == HEAD_GRAD) {
-            int32_t* p = (int32_t*)Q.grad + (cell0 + c0) * KL;
-            a = (int)(((uintptr_t)p >> 2) & 3);
-            gp = p - a;
-            nw = min(64, Q.HW - c0) * KL;
-            if (!has) {
-                headFlush(nullptr, gp, a, nw, lane);
-                continue;
-            }
-            for (int v = lane; v < ((a + nw + 3) >> 2); v += 64) ((int4*)sbuf)[v] = make_int4(0, 0, 0, 0);
-        } else if (!has) {
-            if (i0 >= n) break;
-            continue;
-        }
-        while (i0 < n && (cc >> 6) == chunk) {  // four candidate cells per round, the g-th to row g
-            uint32_t cl[5];
-#pragma unroll
-            for (int k = 0; k < 5; k++) cl[k] = prow[1 + (size_t)min(i0 + k, last) * HEAD_CW];
-            int take = 1;
-#pragma unroll
-            for (int k = 1; k < 4; k++)
-                if (take == k && i0 + k < n && (cl[k] >> 6) == chunk) take = k + 1;
-            const uint32_t* cw = prow + 1 + (size_t)min(i0 + g, last) * HEAD_CW;
-            const uint32_t cell = cw[0], aw = cw[1], b0 = cw[2], b1 = cw[3], b2 = cw[4];
-            X.act = g < take && cell < (uint32_t)Q.HW;
-            const uint32_t cs = X.act ? cell : 0u;
-            __syncthreads();  // the previous round has read its expansion
-            for (int w = q; w < (Q.K + 3) / 4; w += 16) xr[w] = headSpread4(headBits4(b0, b1, b2, w));
-            if (q < 7) xr[XW - 7 + q] = (uint32_t)headActComp(aw, q);
-            __syncthreads();
-            X.lrow = Q.logits + (cell0 + cs) * KL;
-            X.mrec = (const uint8_t*)xr;
-            X.arow = (const int32_t*)(xr + XW - 7);
-            X.grow = (float*)sbuf + a + (cs & 63u) * KL;
-            headCell<MODE>(X, Q, lane);
-            i0 += take;
-            cc = take == 1 ? cl[1] : take == 2 ? cl[2] : take == 3 ? cl[3] : cl[4];
-        }
-        if (MODE == HEAD_GRAD) {
-            __syncthreads();
-            headFlush(sbuf, gp, a, nw, lane);
-            __syncthreads();
-        }
-    }
-    if (MODE != HEAD_GRAD) {
-        const float lp = (float)waveSumD(X.lp), ent = (float)waveSumD(X.ent);
-        if (lane == 0) {
-            if (Q.logprob) Q.logprob[row] = lp;
-            if (Q.entropy) Q.entropy[row] = ent;
-        }
-    }
-}
-
 #ifdef MRTS_LANE_AUDIT
 // the audit's negative control: a readlane of lane 40 from a branch only lanes 0..31 take
 __global__ __launch_bounds__(64) void k_lane_audit_probe(int32_t* out) {
@@ -6995,13 +5912,13 @@ hipError_t laneAuditProbe(int32_t* scratch) {
     hipLaunchKernelGGL(k_lane_audit_probe, dim3(1), dim3(64), 0, 0, scratch);
     return hipGetLastError();
 }
-// out[256]: per thread slot the last violation (source line | kind << 24: 1 readlane, 2 DPP, 3 ballot), 0 = none
+// out[256]: per thread slot the last violation of any unit (source line | unit << 20 | kind << 24: 1 readlane, 2 DPP,
+// 3 ballot), 0 = none
 hipError_t laneAudit(int32_t* out, int reset) {
-    hipError_t e = hipMemcpyFromSymbol(out, HIP_SYMBOL(g_laneAudit), sizeof(int32_t) * 256);
-    if (e == hipSuccess && reset) {
-        int32_t z[256] = {};
-        e = hipMemcpyToSymbol(HIP_SYMBOL(g_laneAudit), z, sizeof(z));
-    }
+    std::fill(out, out + 256, 0);
+    hipError_t e = laneAuditUnit<0>(out, reset);
+    if (e == hipSuccess) e = laneAuditUnit<1>(out, reset);
+    if (e == hipSuccess) e = laneAuditUnit<2>(out, reset);
     return e;
 }
 #endif
@@ -7046,432 +5963,78 @@ hipError_t phaseSpans(unsigned long long* out, int n) {  // [11][n]: starts, end
     return e;
 }
 #endif
+// The dynamic LDS sizes.  Game's constructor and Game::lrInit carve the arrays; these two functions are the only other
+// copy of the layout, written in the carvers' order, one term per array, so the two can be read side by side (the
+// carvers stay as they are: taking their pointers from a shared description changed the step kernels' code).
 // LDS of the native LightRush after the game's own (Game::lrInit)
 size_t lrLdsBytes(int HW, int W, int CAP) {
-    return 4 * (size_t)botWords(CAP) + 4 * (size_t)HW + 3 * 4 * (size_t)((HW + 2 * W + 31) / 32) + 4 * (size_t)maskWords(HW) +
-           3 * 2 * (size_t)HW + 2 * 2 * (size_t)CAP;
+    const size_t NB2 = (size_t)((HW + 2 * W + 31) / 32);
+    size_t q = 4 * (size_t)botWords(CAP);  // lrMem
+    q += 4 * (size_t)HW;                   // lrKey
+    q += 3 * 4 * NB2;                      // lrGs, lrRu, lrPa
+    q += 4 * (size_t)maskWords(HW);        // lrFree
+    q += 3 * 2 * (size_t)HW;               // lrCell, lrPar, lrCost
+    q += 2 * 2 * (size_t)CAP;              // lrOrd [2][CAP]
+    return q;
 }
 size_t ldsBytes(int HW, int W, int CAP, int po) {
-    return (size_t)UTT_LDS + (size_t)16 * CAP + 4 * (size_t)((HW + 2 * W + 31) / 32) + 4 * 64 + 8 * (size_t)maskWords(HW) + 64 + 128 +
-           (po ? 4 * (size_t)HW + 8 * (size_t)(HW / W) * (size_t)((W + 31) / 32) : 0) +
-           (po && poDeltaShape(HW / W, W) ? 4 * (6 * (size_t)(HW / W) + 6 * (size_t)poChunkWords(HW)) + 4 * (size_t)((HW / 4 + 1) & ~1) : 0) +
-           6 * (size_t)CAP + 2 * (size_t)HW + 2 * 64 +
-           // the snapshot bytes (PO) — or, full observability on 16x16, the observation byte image (writeObsFullImg)
-           std::max((((size_t)CAP + 3) & ~(size_t)3), (!po && HW == 256) ? 5 * (size_t)HW : (size_t)0);
-}
-// MicroRTS-Py GridnetVecEnv observation encoding (gym_microrts `_encode_obs`: clip each plane to
-// [0, n_k - 1], one-hot, channels-last): int32 obs [S][C][H][W] -> uint8 [S][H][W][F] with plane sizes
-// n = {5 hp, 5 resources, 3 owner, ntypes + 1 type, 6 action, 2 terrain, 2 per PO visibility plane}.
-// One thread per cell over the flattened (slot, cell) index; a block's 256 cells x F bytes are
-// composed in LDS and leave as aligned 16-byte stores (256 * F is a multiple of 16 for any F).
-struct OneHotParams {
-    const int32_t* obs;
-    uint8_t* out;
-    int32_t n_cells, HW, C, F;
-    int32_t sizes[8], offs[8];
-};
-__global__ __launch_bounds__(256) void k_onehot(OneHotParams Q) {
-    __shared__ __align__(16) uint8_t buf[256 * 40];
-    const int t = (int)threadIdx.x;
-    const int64_t i0 = (int64_t)blockIdx.x * 256, i = i0 + t;
-    const int F = Q.F;
-    for (int k = t; k < 256 * F / 4; k += 256) ((uint32_t*)buf)[k] = 0u;
-    __syncthreads();
-    if (i < Q.n_cells) {
-        const int64_t slot = i / Q.HW;
-        const int c = (int)(i - slot * Q.HW);
-        const int32_t* o = Q.obs + slot * Q.C * Q.HW + c;
-        for (int p = 0; p < Q.C; p++) {
-            const int v = min(max(o[(int64_t)p * Q.HW], 0), Q.sizes[p] - 1);
-            buf[t * F + Q.offs[p] + v] = 1;
-        }
+    const size_t H = (size_t)(HW / W), NCW = (size_t)poChunkWords(HW);
+    size_t q = UTT_LDS;                             // the unit-type table copy
+    q += 4 * 4 * (size_t)CAP;                       // uc, ua, at, as
+    q += 4 * (size_t)((HW + 2 * W + 31) / 32);      // bits
+    q += 4 * 64;                                    // rseq
+    q += 8 * (size_t)maskWords(HW);                 // mprev
+    q += 4 * 16 + 4 * 32;                           // rwc, hdr
+    q += 3 * 2 * (size_t)CAP;                       // hp, res, par
+    q += 2 * (size_t)HW + 2 * 64;                   // cell, rslot
+    const size_t snapBytes = ((size_t)CAP + 3) & ~(size_t)3;
+    if (!po)  // snap — on 16x16 under the observation byte image writeObsFullImg lays over it (5 planes of HW bytes)
+        return q + std::max(snapBytes, HW == 256 ? 5 * (size_t)HW : (size_t)0);
+    q += snapBytes;
+    q += 4 * (size_t)HW + 4 * 2 * H * (size_t)((W + 31) / 32);  // scell, vis
+    if (poDeltaShape((int)H, W)) {
+        q += 4 * (4 * H + 2 * NCW + 4 * NCW + 2 * H);  // poVis, poPend, poDirty, vis2
+        q += 4 * (size_t)((HW / 4 + 1) & ~1);          // poList
     }
-    __syncthreads();
-    const int64_t ncell = min((int64_t)256, (int64_t)Q.n_cells - i0);
-    const int64_t nbytes = ncell * F, n16 = nbytes / 16;
-    uint8_t* dst = Q.out + i0 * F;
-    for (int64_t k = t; k < n16; k += 256) ((uint4*)dst)[k] = ((const uint4*)buf)[k];
-    for (int64_t k = 16 * n16 + t; k < nbytes; k += 256) dst[k] = buf[k];
+    return q;
 }
-hipError_t launchOneHot(const int32_t* obs, uint8_t* out, int n_slots, int HW, int C, int ntypes, hipStream_t stream) {
-    OneHotParams Q;
-    Q.obs = obs;
-    Q.out = out;
-    Q.n_cells = n_slots * HW;
-    Q.HW = HW;
-    Q.C = C;
-    const int base[6] = {5, 5, 3, ntypes + 1, 6, 2};
-    int f = 0;
-    for (int p = 0; p < 8; p++) {
-        Q.sizes[p] = p < 6 ? base[p] : 2;
-        Q.offs[p] = f;
-        if (p < C) f += Q.sizes[p];
-    }
-    Q.F = f;
-    if (C > 8 || f > 40 || ((uintptr_t)out & 15)) return hipErrorInvalidValue;
-    hipLaunchKernelGGL(k_onehot, dim3((unsigned)((Q.n_cells + 255) / 256)), dim3(256), 0, stream, Q);
-    return hipGetLastError();
+// what follows the game's own LDS starts at the next 16-byte boundary: the LightRush area (KStatic.bot_lds), or a
+// HELP instance's helper-wave area (KDyn.help_off) of HELP8_LDS (helperLoop's rows) / HELP32PO_LDS (helperLoopPO's
+// header and record words) bytes
+static size_t ldsAlign16(size_t bytes) { return (bytes + 15) & ~(size_t)15; }
+constexpr size_t HELP8_LDS = 2048, HELP32PO_LDS = 4 * (PO_HELP_REC + PO_HELP_REC_WORDS);
+size_t ldsLightRushOff(int HW, int W, int CAP, int po) { return ldsAlign16(ldsBytes(HW, W, CAP, po)); }
+size_t handleLdsBytes(int HW, int W, int CAP, int po, bool lightRush) {
+    return lightRush ? ldsLightRushOff(HW, W, CAP, po) + lrLdsBytes(HW, W, CAP) : ldsBytes(HW, W, CAP, po);
 }
 
-// int32 copy of a uint8 mask buffer (the Java int[][][][] layout), 16 mask bytes per thread
-__global__ __launch_bounds__(256) void k_widen(const uint8_t* __restrict__ in, int32_t* __restrict__ out, size_t n) {
-    const size_t i = ((size_t)blockIdx.x * 256 + threadIdx.x) * 16;
-    if (i + 16 <= n) {
-        const uint4 v = *(const uint4*)(in + i);
-        const uint32_t w[4] = {v.x, v.y, v.z, v.w};
-#pragma unroll
-        for (int q = 0; q < 4; q++)
-            *(int4*)(out + i + 4 * q) = make_int4((int)(w[q] & 0xFF), (int)((w[q] >> 8) & 0xFF), (int)((w[q] >> 16) & 0xFF),
-                                                  (int)(w[q] >> 24));
-    } else {
-        for (size_t k = i; k < n; k++) out[k] = in[k];
-    }
+// The shapes with specialised k_env instances (the sizes are constants in them; each has single-step, MULTI and
+// MODE_TRACE instances but S32PO, which has no MODE_TRACE one) and the condition common to them: the unit-type table
+// the constants were compiled for, a square map, and every game self-play.
+enum { S16 = 0, S8 = 1, S32PO = 2 };
+constexpr struct { int W, CAP; bool po; } SPEC_SHAPES[3] = {{16, 320, false}, {8, 128, false}, {32, 320, true}};
+// index into SPEC_SHAPES, or -1: the generic instances.  anyKind: MODE_TRACE's selection — it steps single games of
+// a forward-model handle through the specialised games' code whatever their kind, so it ignores n_sp_games.
+static int specialisedShape(const KStatic& hs, bool anyKind = false) {
+    if (!(anyKind || hs.n_sp_games == hs.n_games) || hs.utt.K != 79 || hs.utt.ntypes != 7 || hs.utt.maxAttackRadius != 7 || hs.H != hs.W)
+        return -1;
+    for (int i = 0; i < 3; i++)
+        if (hs.W == SPEC_SHAPES[i].W && hs.CAP == SPEC_SHAPES[i].CAP && (hs.partial_obs != 0) == SPEC_SHAPES[i].po) return i;
+    return -1;
 }
-hipError_t launchWiden(const uint8_t* in, int32_t* out, size_t n, hipStream_t stream) {
-    if (n == 0) return hipSuccess;
-    if (((uintptr_t)in & 15) || ((uintptr_t)out & 15)) return hipErrorInvalidValue;
-    const size_t threads = (n + 15) / 16;
-    hipLaunchKernelGGL(k_widen, dim3((unsigned)((threads + 255) / 256)), dim3(256), 0, stream, in, out, n);
-    return hipGetLastError();
-}
-// ---------------------------------------------------------------- forward model
-// GameState.clone() (rts/GameState.java:591-610) of pairs (dst game, src game): units, players,
-// time, the cancel counter and the assignments (LinkedHashMap order = the sequence numbers) travel;
-// the dst game keeps its own random streams (Sampler.generator / GameState.r / UnitAction.r are
-// JVM-global, not part of a GameState), its kind (playout policies), and its mask row sets (they
-// describe the dst handle's mask buffer).  One block of 256 threads per pair.
-// Receiver side of the compact observation exchange: the records of n_ranks x n_games games (rank r's
-// game g at rec + r * rank_stride + g * recWords(units) words) back into both player slots'
-// observation planes — GameState.getVectorObservation (rts/GameState.java:922-968), the owner plane
-// per viewing player (:947-949), the terrain plane from the local handle's map of game g (every rank
-// holds the same maps per game index).  out = [n_ranks][2 * n_games][C][HW] as uint8 (out_bytes 1)
-// or int32 (4).  One wave per game: the units paint a byte image in LDS, then each lane stores 4 cells
-// per plane.  HW <= 256, HW % 4 == 0 (the host checks).
-// A record whose overflow bit is set (its game had more units than the record holds) renders without
-// the missing units: the kernel then sets *err (mrts_render_status reports it).
-__global__ __launch_bounds__(64) void k_render_records(const KStatic* __restrict__ PS, const uint32_t* __restrict__ rec,
-                                                       int units, int64_t rank_stride, void* __restrict__ out, int out_bytes,
-                                                       int32_t* __restrict__ err) {
-    __shared__ uint32_t imgw[5 * 256 / 4];
-    uint8_t* img = (uint8_t*)imgw;
-    const KStatic& P = *PS;
-    const int g = (int)blockIdx.x, r = (int)blockIdx.y, l = (int)threadIdx.x, HW = P.HW, C = P.C, G = P.n_games;
-    const uint32_t* rc = rec + (size_t)r * (size_t)rank_stride + (size_t)g * recWords(units, false);
-    for (int i = l; i < 5 * HW / 4; i += 64) imgw[i] = 0u;
-    const uint32_t hdr = rc[0];
-    if (l == 0 && (hdr >> 31)) *err = 1;  // a vector store from one lane (rare)
-    __syncthreads();
-    const int n = min((int)(hdr & 0xFFFFu), units);
-    for (int i = l; i < n; i += 64) {
-        const uint32_t w = rc[1 + i];
-        const int c = (int)(w & 0xFFu);
-        if (c >= HW) continue;  // (a foreign buffer: no LDS write out of range)
-        img[c] = (uint8_t)(w >> 8);
-        img[HW + c] = (uint8_t)(w >> 16);
-        img[2 * HW + c] = (uint8_t)((w >> 27) & 3u);
-        img[3 * HW + c] = (uint8_t)((w >> 24) & 7u);
-        img[4 * HW + c] = (uint8_t)(w >> 29);
-    }
-    __syncthreads();
-    const uint32_t* terr = (const uint32_t*)(P.tmpl + P.tmpl_off[g] + T_TERR);
-    const size_t slot0 = (size_t)r * 2 * G + 2 * (size_t)g;
-    for (int c4 = 4 * l; c4 < HW; c4 += 256) {
-        uint32_t pw[6];
-#pragma unroll
-        for (int q = 0; q < 5; q++) pw[q] = imgw[(q * HW + c4) >> 2];
-        const uint32_t t = terr[c4 >> 2];  // walls: non-zero terrain bytes
-        uint32_t tw = 0;
-#pragma unroll
-        for (int j = 0; j < 4; j++) tw |= (((t >> (8 * j)) & 0xFFu) ? 1u : 0u) << (8 * j);
-        pw[5] = tw;
-#pragma unroll
-        for (int i = 0; i < 2; i++) {
-#pragma unroll
-            for (int q = 0; q < 6; q++) {
-                uint32_t w = pw[q];
-                if (i == 1 && q == 2) {  // the other player's owners: 1 <-> 2, 0 stays
-                    uint32_t x = 0;
-#pragma unroll
-                    for (int j = 0; j < 4; j++) {
-                        const uint32_t b = (w >> (8 * j)) & 0xFFu;
-                        x |= (b ? 3u - b : 0u) << (8 * j);
-                    }
-                    w = x;
-                }
-                const size_t off = ((slot0 + i) * C + q) * (size_t)HW + c4;
-                if (out_bytes == 1) {
-                    *(uint32_t*)((uint8_t*)out + off) = w;
-                } else {
-                    st4<true>((int32_t*)out + off, (int)(w & 0xFFu), (int)((w >> 8) & 0xFFu), (int)((w >> 16) & 0xFFu),
-                              (int)(w >> 24));
-                }
-            }
-        }
-    }
-}
-// The same for partially observable handles (PartiallyObservableGameState.getVectorObservation,
-// rts/PartiallyObservableGameState.java:82-154, as Game::writeObsPO renders it): per view p, the last
-// unit of p's snapshot on each cell (list order) gives planes 0-4 — its live hp, resources, owner
-// relative to p, type, and the action type p's snapshot saw — plane 5 the map's walls, planes 6 / 7
-// whether a sight disk of one of the view's units owned by p / by the other player covers the cell.
-// out = [n_ranks][2 * n_games][8][HW] as int8 (out_bytes 1: a dead unit's hp can be negative) or int32.
-// One block of 256 threads per game and rank; LDS: the per-view cell owners (2 x HW words), sight rows
-// (2 views x 2 x H x (W + 31) / 32 words) and the record itself (the per-cell lookups stay on chip).
-// HW % 4 == 0 (the host checks).
-__global__ __launch_bounds__(256) void k_render_records_po(const KStatic* __restrict__ PS, const uint32_t* __restrict__ rec,
-                                                           int units, int64_t rank_stride, void* __restrict__ out, int out_bytes,
-                                                           int32_t* __restrict__ err) {
-    extern __shared__ __align__(16) uint32_t lds[];
-    const KStatic& P = *PS;
-    const int g = (int)blockIdx.x, r = (int)blockIdx.y, t = (int)threadIdx.x;
-    const int H = P.H, W = P.W, HW = P.HW, C = P.C, G = P.n_games, NR = H * ((W + 31) >> 5);
-    uint32_t* const sc = lds;             // [view][cell]: index + 1 of the view's last unit on the cell, 0 = none
-    uint32_t* const rows = lds + 2 * HW;  // [view][own, other][NR]
-    uint32_t* const rc = rows + 4 * NR;   // the record (1 + 2 x units words)
-    const uint32_t* rg = rec + (size_t)r * (size_t)rank_stride + (size_t)g * recWords(units, true);
-    const int n = min((int)(rg[0] & 0xFFFFu), units);
-    if (t == 0 && (rg[0] >> 31)) *err = 1;  // overflow: units or an hp / resource value missing
-    for (int i = t; i < 2 * HW + 4 * NR; i += 256) lds[i] = 0u;
-    for (int i = t; i < 1 + 2 * n; i += 256) rc[i] = rg[i];
-    __syncthreads();
-    const int SM = P.utt.maxSight;
-    const bool rowPaint = W <= 32 && SM <= 15;  // one word per sight row, table half-widths
-    for (int i = t; i < n; i += 256) {  // the views' last unit per cell; and the sight disks (general maps)
-        const uint32_t w0 = rc[1 + 2 * i], w1 = rc[2 + 2 * i];
-        const int c = (int)(w0 & 0xFFFFu), ty = (int)(w1 & 15u) - 1, pl = (int)((w1 >> 4) & 3u) - 1;
-        const uint32_t sb = (c < HW && ty >= 0 && ty < MAX_TYPES) ? (w1 >> 8) & 0xFFu : 0u;  // (a foreign buffer: no LDS write out of range)
-        const int x = c % W, y = c / W;
-        for (int p = 0; p < 2; p++) {
-            if (!((sb >> p) & 1u)) continue;
-            atomicMax(&sc[p * HW + c], (uint32_t)(i + 1));
-            if (pl >= 0 && !rowPaint)
-                paintDiskRows(rows + (2 * p + (pl == p ? 0 : 1)) * NR, H, W, x, y, P.utt.sight[ty], P.utt.diskLo[ty],
-                              P.utt.diskHi[ty]);
-        }
-    }
-    if (rowPaint) {
-        // every (unit, row offset) pair on its own thread: 8 units x 32 row offsets per pass (2 SM + 1 <= 31),
-        // one atomicOr per view the unit is in — not one thread looping over a unit's rows
-        const int dy = (t & 31) - SM;
-        for (int i = t >> 5; i < n; i += 8) {
-            const uint32_t w0 = rc[1 + 2 * i], w1 = rc[2 + 2 * i];
-            const int c = (int)(w0 & 0xFFFFu), ty = (int)(w1 & 15u) - 1, pl = (int)((w1 >> 4) & 3u) - 1;
-            const uint32_t sb = (c < HW && ty >= 0 && ty < MAX_TYPES && pl >= 0) ? (w1 >> 8) & 3u : 0u;
-            const int ady = dy < 0 ? -dy : dy, sr = sb ? P.utt.sight[ty] : -1;
-            const int x = c % W, yy = c / W + dy;
-            if (ady <= sr && yy >= 0 && yy < H) {
-                const uint32_t half = ((ady < 8 ? P.utt.diskLo[ty] : P.utt.diskHi[ty]) >> (4 * (ady & 7))) & 0xFu;
-                const int x0 = max(0, x - (int)half), x1 = min(W - 1, x + (int)half);
-                const uint32_t b = ((2u << (x1 - x0)) - 1u) << x0;  // columns x0..x1 (x1 - x0 = 31: 2u << 31 wraps to 0)
-                if (sb & 1u) atomicOr(&rows[(pl == 0 ? 0 : 1) * NR + yy], b);
-                if (sb & 2u) atomicOr(&rows[(2 + (pl == 1 ? 0 : 1)) * NR + yy], b);
-            }
-        }
-    }
-    __syncthreads();
-    const uint32_t* terr = (const uint32_t*)(P.tmpl + P.tmpl_off[g] + T_TERR);
-    const int WPR = (W + 31) >> 5;
-    for (int c4 = 4 * t; c4 < HW; c4 += 4 * 256) {
-        const uint32_t tw = terr[c4 >> 2];  // walls: non-zero terrain bytes
-        for (int p = 0; p < 2; p++) {
-            int v[8][4];
-#pragma unroll
-            for (int j = 0; j < 4; j++) {
-                const int c = c4 + j, x = c % W, y = c / W;
-                const uint32_t s = sc[p * HW + c];
-                const uint32_t w0 = s ? rc[2 * s - 1] : 0u, w1 = s ? rc[2 * s] : 0u;
-                const int pl = (int)((w1 >> 4) & 3u) - 1, ca = (int)((w1 >> (10 + 3 * p)) & 7u);
-                v[0][j] = s ? (int)(int8_t)(uint8_t)(w0 >> 16) : 0;
-                v[1][j] = s ? (int)(w0 >> 24) : 0;
-                v[2][j] = (s && pl >= 0) ? ((pl + p) % 2) + 1 : 0;
-                v[3][j] = s ? (int)(w1 & 15u) : 0;
-                v[4][j] = (s && ca) ? ca - 1 : 0;
-                v[5][j] = ((tw >> (8 * j)) & 0xFFu) ? 1 : 0;
-                v[6][j] = (int)((rows[(2 * p) * NR + y * WPR + (x >> 5)] >> (x & 31)) & 1u);
-                v[7][j] = (int)((rows[(2 * p + 1) * NR + y * WPR + (x >> 5)] >> (x & 31)) & 1u);
-            }
-            const size_t slot = (size_t)r * 2 * G + 2 * (size_t)g + p;
-#pragma unroll
-            for (int q = 0; q < 8; q++) {
-                const size_t off = (slot * C + q) * (size_t)HW + c4;
-                if (out_bytes == 1)
-                    *(uint32_t*)((uint8_t*)out + off) = (uint32_t)(v[q][0] & 0xFF) | ((uint32_t)(v[q][1] & 0xFF) << 8) |
-                                                         ((uint32_t)(v[q][2] & 0xFF) << 16) | ((uint32_t)(v[q][3] & 0xFF) << 24);
-                else
-                    st4<true>((int32_t*)out + off, v[q][0], v[q][1], v[q][2], v[q][3]);
-            }
-        }
-    }
-}
-// A learner's batch straight from the exchanged records, in the layout it consumes: the
-// MicroRTS-Py encoding of the observation (gym_microrts `_encode_obs`, as k_onehot: clip each plane, one-hot,
-// channels last) of n_sel samples: sample i is slot sel[i] (global index r * n_slots + slot over every rank's
-// slots) of the step whose rank-0 records start at rec + step_off[2i] with rank stride step_off[2i + 1] (the
-// rollout's step_offsets row; null: rec and rank_stride) — a minibatch of (step, slot) pairs from a whole
-// rollout window in one launch, with no int32 / uint8 planes of all ranks in between.  Full observability.  One 256-thread block per selected
-// slot: its game's record paints the 5 dynamic planes as bytes in LDS (as k_render_records), each cell's
-// F one-hot bytes are composed in LDS, and the slot's H x W x F bytes leave as aligned 16-byte stores.
-// out = [n_sel][H][W][F] uint8 (HW * F % 16 == 0, the host checks).
-__global__ __launch_bounds__(256) void k_render_records_onehot(const KStatic* __restrict__ PS, const uint32_t* __restrict__ rec,
-                                                               int units, int64_t rank_stride, const int32_t* __restrict__ sel,
-                                                               const int64_t* __restrict__ step_off, uint8_t* __restrict__ out,
-                                                               OneHotParams Q, int32_t* __restrict__ err, int64_t rec_words,
-                                                               int n_ranks) {
-    __shared__ uint32_t imgw[5 * 256 / 4];
-    __shared__ __align__(16) uint8_t buf[256 * 40];
-    uint8_t* img = (uint8_t*)imgw;
-    const KStatic& P = *PS;
-    const int t = (int)threadIdx.x, HW = P.HW, S = 2 * P.n_games, F = Q.F;
-    const int gs = sel[blockIdx.x];
-    const int r = gs / S, slot = gs - r * S, g = slot >> 1, p = slot & 1;
-    const int64_t o = step_off ? step_off[2 * blockIdx.x] : 0, rs = step_off ? step_off[2 * blockIdx.x + 1] : rank_stride;
-    // a sample outside the buffer (a bad sel index or step_off row): a zero image and the render flag
-    // (mrts_render_status), never a read past the receive buffer.  Block-uniform: the whole block returns.
-    const int64_t at = o + (int64_t)r * rs + (int64_t)g * recWords(units, false);
-    if (gs < 0 || r >= n_ranks || o < 0 || rs < 0 || at + recWords(units, false) > rec_words) {
-        if (t == 0) *err = 1;
-        uint4* dz = (uint4*)(out + (size_t)blockIdx.x * HW * F);
-        for (int k = t; k < HW * F / 16; k += 256) dz[k] = make_uint4(0u, 0u, 0u, 0u);
-        return;
-    }
-    const uint32_t* rc = rec + at;
-    for (int i = t; i < 5 * HW / 4; i += 256) imgw[i] = 0u;
-    for (int k = t; k < HW * F / 4; k += 256) ((uint32_t*)buf)[k] = 0u;
-    const uint32_t hdr = rc[0];
-    if (t == 0 && (hdr >> 31)) *err = 1;  // overflow (mrts_render_status)
-    __syncthreads();
-    const int n = min((int)(hdr & 0xFFFFu), units);
-    for (int i = t; i < n; i += 256) {
-        const uint32_t w = rc[1 + i];
-        const int c = (int)(w & 0xFFu);
-        if (c >= HW) continue;
-        img[c] = (uint8_t)(w >> 8);
-        img[HW + c] = (uint8_t)(w >> 16);
-        img[2 * HW + c] = (uint8_t)((w >> 27) & 3u);  // player + 1 (0 = none)
-        img[3 * HW + c] = (uint8_t)((w >> 24) & 7u);
-        img[4 * HW + c] = (uint8_t)(w >> 29);
-    }
-    __syncthreads();
-    const uint8_t* terr = (const uint8_t*)(P.tmpl + P.tmpl_off[g] + T_TERR);
-    for (int c = t; c < HW; c += 256) {
-        const int pl1 = img[2 * HW + c];  // owner plane of slot p: ((player + p) % 2) + 1
-        const int v[6] = {img[c], img[HW + c], pl1 ? ((pl1 - 1 + p) & 1) + 1 : 0, img[3 * HW + c], img[4 * HW + c],
-                          terr[c] ? 1 : 0};
-#pragma unroll
-        for (int q = 0; q < 6; q++) buf[c * F + Q.offs[q] + min(max(v[q], 0), Q.sizes[q] - 1)] = 1;
-    }
-    __syncthreads();
-    uint4* dst = (uint4*)(out + (size_t)blockIdx.x * HW * F);
-    for (int k = t; k < HW * F / 16; k += 256) dst[k] = ((const uint4*)buf)[k];
-}
-hipError_t launchRenderRecordsOneHot(const KStatic& hs, const KStatic* ds, const uint32_t* rec, int64_t rec_words, int n_ranks,
-                                     int units, int64_t rank_stride, const int32_t* sel, const int64_t* step_off, int n_sel,
-                                     uint8_t* out, int32_t* err, hipStream_t stream) {
-    OneHotParams Q{};
-    const int base[6] = {5, 5, 3, hs.utt.ntypes + 1, 6, 2};
-    int f = 0;
-    for (int q = 0; q < 6; q++) {
-        Q.sizes[q] = base[q];
-        Q.offs[q] = f;
-        f += base[q];
-    }
-    Q.F = f;
-    if (hs.partial_obs || hs.HW > 256 || f > 40 || ((size_t)hs.HW * f) % 16 || ((uintptr_t)out & 15)) return hipErrorInvalidValue;
-    if (n_sel <= 0) return hipSuccess;
-    hipLaunchKernelGGL(k_render_records_onehot, dim3((unsigned)n_sel), dim3(256), 0, stream, ds, rec, units, rank_stride, sel,
-                       step_off, out, Q, err, rec_words, n_ranks);
-    return hipGetLastError();
-}
-hipError_t launchRenderRecords(const KStatic& hs, const KStatic* ds, const uint32_t* rec, int units, int n_ranks,
-                               int64_t rank_stride, void* out, int out_bytes, int32_t* err, hipStream_t stream) {
-    if (hs.partial_obs) {
-        const size_t lds = 4 * (size_t)(2 * hs.HW + 4 * hs.H * ((hs.W + 31) / 32) + recWords(units, true));
-        hipLaunchKernelGGL(k_render_records_po, dim3((unsigned)hs.n_games, (unsigned)n_ranks), dim3(256), lds, stream, ds, rec,
-                           units, rank_stride, out, out_bytes, err);
-    } else {
-        hipLaunchKernelGGL(k_render_records, dim3((unsigned)hs.n_games, (unsigned)n_ranks), dim3(64), 0, stream, ds, rec, units,
-                           rank_stride, out, out_bytes, err);
-    }
-    return hipGetLastError();
-}
-
-__global__ __launch_bounds__(256) void k_copy_games(int32_t* __restrict__ dst, const int32_t* __restrict__ src,
-                                                    const int32_t* __restrict__ pairs, int n_dst, int n_src,
-                                                    int words, int src_words, int maskLo, int maskHi) {
-    const int d = pairs[2 * blockIdx.x], s = pairs[2 * blockIdx.x + 1];
-    if (d < 0 || d >= n_dst || s < 0 || s >= n_src) return;
-    int32_t* o = dst + (size_t)d * words;
-    const int32_t* i = src + (size_t)s * src_words;  // a source with LightRush games: longer blocks, same leading words
-    for (int w = threadIdx.x; w < words; w += 256) {
-        const bool keep = (w >= H_RNG_CANCEL && w <= H_KIND) || (w >= maskLo && w < maskHi);
-        if (!keep) o[w] = w == H_STEPS ? 0 : i[w];
-    }
-}
-hipError_t launchCopyGames(int32_t* dst, const int32_t* src, const int32_t* pairs, int n, int n_dst, int n_src,
-                           int CAP, int HW, int src_words, hipStream_t stream) {
-    if (n <= 0) return hipSuccess;
-    // The destination's stride is stateWords: mrts_copy_games' destination is a forward-model handle (checkCopy), and
-    // mrts_create refuses LightRush there, so its blocks never carry bot memory.  A destination with longer blocks
-    // would need its own stride here (and a decision on what a copied game's bot memory is).
-    const int lo = H_WORDS + N_ARRAYS * CAP;
-    hipLaunchKernelGGL(k_copy_games, dim3((unsigned)n), dim3(256), 0, stream, dst, src, pairs, n_dst, n_src,
-                       stateWords(CAP, HW), src_words, lo, lo + 2 * maskWords(HW));
-    return hipGetLastError();
-}
-
-// SimpleSqrtEvaluationFunction3.evaluate(maxplayer, 1 - maxplayer, gs)
-// (ai/evaluation/SimpleSqrtEvaluationFunction3.java:24-44), Java float semantics: the unit loop runs
-// in list order, `score += res * 10f` is a float add, `score += 40f * cost * Math.sqrt(hp / maxHp)`
-// (integer division) is a double add rounded back to float; no contraction into FMAs.  One wave per
-// game: lanes load 64 units at a time, every lane runs the same ordered sum over readlane values.
-__global__ __launch_bounds__(64) void k_evaluate(const KStatic* __restrict__ PS, const int32_t* __restrict__ state,
-                                                 int words, int CAP, int maxplayer, float* __restrict__ out) {
-#pragma clang fp contract(off)
-    const KStatic& P = *PS;
-    const int32_t* s = state + (size_t)blockIdx.x * words;
-    const int nu = uni(s[H_NU]);
-    const int l = lane_id();
-    float score[2];
-    bool any[2] = {false, false};
-    score[0] = __fmul_rn((float)uni(s[H_RES0]), 20.0f);
-    score[1] = __fmul_rn((float)uni(s[H_RES1]), 20.0f);
-    for (int o0 = 0; o0 < nu; o0 += 64) {
-        const int o = o0 + l;
-        uint32_t c = UC_DEAD;
-        int hpv = 0, rv = 0;
-        if (o < nu) {
-            c = (uint32_t)s[H_WORDS + A_UC * CAP + o];
-            hpv = s[H_WORDS + A_HP * CAP + o];
-            rv = s[H_WORDS + A_RES * CAP + o];
-        }
-        const int n = min(64, nu - o0);
-        for (int k = 0; k < n; k++) {
-            const uint32_t ck = (uint32_t)rl((int)c, k);
-            if (ck & UC_DEAD) continue;
-            const int p = uplay(ck);
-            if (p != 0 && p != 1) continue;
-            const int typ = utyp(ck);
-            const int h = rl(hpv, k), r = rl(rv, k);
-            float sc = score[p];
-            sc = __fadd_rn(sc, __fmul_rn((float)r, 10.0f));
-            const double bonus = __dmul_rn((double)__fmul_rn(40.0f, (float)P.utt.cost[typ]),
-                                           __builtin_sqrt((double)(h / P.utt.hp[typ])));
-            sc = (float)__dadd_rn((double)sc, bonus);
-            score[p] = sc;
-            any[p] = true;
-        }
-    }
-    const float s1 = any[maxplayer] ? score[maxplayer] : 0.0f;
-    const float s2 = any[1 - maxplayer] ? score[1 - maxplayer] : 0.0f;
-    const float tot = __fadd_rn(s1, s2);
-    const float v = tot == 0.0f ? 0.5f : __fsub_rn(__fdiv_rn(__fmul_rn(2.0f, s1), tot), 1.0f);
-    if (l == 0) out[blockIdx.x] = v;
-}
-hipError_t launchEvaluate(const KStatic& hs, const KStatic* ds, int maxplayer, float* out, hipStream_t stream) {
-    // the handle's block stride: a handle with a LightRush game has the bot memory after every state block
-    const int words = hs.bot_off ? hs.bot_off + botWords(hs.CAP) : stateWords(hs.CAP, hs.HW);
-    hipLaunchKernelGGL(k_evaluate, dim3((unsigned)hs.n_games), dim3(64), 0, stream, ds, hs.state, words, hs.CAP, maxplayer, out);
-    return hipGetLastError();
+// The generic instances take any map, so theirs is the LDS that can exceed the default limit (the specialised
+// shapes' never does): the attribute is set on every instance envInstance returns for shape -1.
+hipError_t prepareLds(size_t bytes) {
+    hipError_t e = hipFuncSetAttribute((const void*)k_env<MODE_STEP, 0>, hipFuncAttributeMaxDynamicSharedMemorySize, (int)bytes);
+    if (e == hipSuccess) e = hipFuncSetAttribute((const void*)k_env<MODE_RESET, 0>, hipFuncAttributeMaxDynamicSharedMemorySize, (int)bytes);
+    if (e == hipSuccess) e = hipFuncSetAttribute((const void*)k_env<MODE_MASKS, 0>, hipFuncAttributeMaxDynamicSharedMemorySize, (int)bytes);
+    if (e == hipSuccess) e = hipFuncSetAttribute((const void*)k_env<MODE_PLAYOUT, 0>, hipFuncAttributeMaxDynamicSharedMemorySize, (int)bytes);
+    if (e == hipSuccess) e = hipFuncSetAttribute((const void*)k_env<MODE_TRACE, 0>, hipFuncAttributeMaxDynamicSharedMemorySize, (int)bytes);
+    if (e == hipSuccess)
+        e = hipFuncSetAttribute((const void*)k_env<MODE_STEP, 0, 0, false, false, false, true>, hipFuncAttributeMaxDynamicSharedMemorySize, (int)bytes);
+    if (e == hipSuccess)
+        e = hipFuncSetAttribute((const void*)k_env<MODE_RESET, 0, 0, false, false, false, true>, hipFuncAttributeMaxDynamicSharedMemorySize, (int)bytes);
+    return e;
 }
 
 // e0 / e1 (may be null): timing events the launch records itself (hipExtLaunchKernelGGL: the kernel
@@ -7483,8 +6046,7 @@ hipError_t launchEvaluate(const KStatic& hs, const KStatic* ds, int maxplayer, f
 // any of them runs the general instance.  (KDyn.players is not among them: the specialised self-play instances never
 // read it, and the Python front end always passes its players tensor.)
 static bool steadyLaunch(const KStatic& hs, const KDyn& D) {
-    const bool shape = hs.n_sp_games == hs.n_games && hs.utt.K == 79 && hs.utt.ntypes == 7 && hs.utt.maxAttackRadius == 7 &&
-                       hs.H == 16 && hs.W == 16 && hs.CAP == 320 && !hs.partial_obs && !hs.bot_off;
+    const bool shape = specialisedShape(hs) == S16 && !hs.bot_off;
     const bool on = D.n_iter > 1 && D.mask_delta == 1 && D.pol_delta == 1 && D.fwd_read == 1 && D.obs_img == 1;
     const bool has = D.actions && D.obs && D.masks && D.source && D.pol_actions && D.reward && D.done && D.prio_tab && D.bal;
     const bool off = !D.obs8 && !D.obs16 && !D.rec_out && !D.uni_actions && !D.rows;
@@ -7493,17 +6055,10 @@ static bool steadyLaunch(const KStatic& hs, const KDyn& D) {
 }
 // steadyLaunch for a launch that deviates from the steady state in one condition (`dev` < 0: in none): 1 / 0, or -1
 // past the last deviation.  Not part of include/mrts.h: the tests' view of the selection.
-extern "C" int mrts_internal_steady_probe(int dev) {
-    KStatic hs{};
-    hs.n_games = hs.n_sp_games = 512;
-    hs.utt.K = 79;
-    hs.utt.ntypes = 7;
-    hs.utt.maxAttackRadius = 7;
-    hs.H = hs.W = 16;
-    hs.HW = 256;
-    hs.CAP = 320;
-    static int32_t buf[4];
-    void* const some = buf;
+static int32_t g_probeBuf[4];
+// the steady state's launch arguments (the probes below deviate from them); `some`: a non-null buffer
+static KDyn steadyDyn() {
+    void* const some = g_probeBuf;
     KDyn D{};
     D.n_iter = 20;
     D.mask_delta = D.pol_delta = D.fwd_read = D.obs_img = 1;
@@ -7517,6 +6072,19 @@ extern "C" int mrts_internal_steady_probe(int dev) {
     D.prio_tab = (uint32_t*)some;
     D.bal = (int32_t*)some;
     D.n_rewards = 1;
+    return D;
+}
+extern "C" int mrts_internal_steady_probe(int dev) {
+    KStatic hs{};
+    hs.n_games = hs.n_sp_games = 512;
+    hs.utt.K = 79;
+    hs.utt.ntypes = 7;
+    hs.utt.maxAttackRadius = 7;
+    hs.H = hs.W = 16;
+    hs.HW = 256;
+    hs.CAP = 320;
+    void* const some = g_probeBuf;
+    KDyn D = steadyDyn();
     switch (dev) {
         case 0: D.n_iter = 1; break;
         case 1: hs.H = hs.W = 8; hs.HW = 64; hs.CAP = 128; break;
@@ -7550,133 +6118,100 @@ extern "C" int mrts_internal_steady_probe(int dev) {
     return steadyLaunch(hs, D) ? 1 : 0;
 }
 
-hipError_t launchEnv(int mode, const KStatic& hs, const KStatic* ds, const KDyn& D, hipStream_t stream, hipEvent_t e0, hipEvent_t e1) {
-    const size_t lds = hs.bot_off ? (size_t)hs.bot_lds + lrLdsBytes(hs.HW, hs.W, hs.CAP) : ldsBytes(hs.HW, hs.W, hs.CAP, hs.partial_obs);
-    dim3 grid((unsigned)hs.n_games), block(64);
-    const bool fixable = hs.n_sp_games == hs.n_games && D.rows == nullptr && hs.utt.K == 79 && hs.utt.ntypes == 7 &&
-                         hs.utt.maxAttackRadius == 7 && hs.H == hs.W;
-    auto is = [&](int w, int cap, bool po) { return fixable && hs.W == w && hs.CAP == cap && (hs.partial_obs != 0) == po; };
-#define LAUNCH(kern, g_, b_, l_, s_, ...) hipExtLaunchKernelGGL(kern, g_, b_, (uint32_t)(l_), s_, e0, e1, 0, __VA_ARGS__)
+// The instance of k_env a launch runs.  The three selections below start from the one shape test and differ in two
+// things: rows (mrts_step_rows' per-unit rows in place of the action tensor) is a MODE_STEP argument the specialised
+// step instances do not read, so it sends a step to the generic instance and concerns no other mode; and MODE_TRACE
+// steps single games of a forward-model handle, of any kind, so it ignores n_sp_games (and rows: it has none).
+enum EnvInst { EI_STEADY16, EI_MULTI16, EI_STEP16, EI_HELP8, EI_MULTI8, EI_STEP8, EI_HELP32PO, EI_MULTI32PO, EI_STEP32PO,
+               EI_STEP_LR, EI_STEP, EI_RESET_LR, EI_RESET, EI_PLAYOUT, EI_TRACE16, EI_TRACE8, EI_TRACE, EI_MASKS };
+static EnvInst envInstance(int mode, const KStatic& hs, const KDyn& D) {
     switch (mode) {
-        case MODE_STEP:
-            if (is(16, 320, false) && steadyLaunch(hs, D))
-                LAUNCH((k_env<MODE_STEP, 16, 320, false, true, false, false, true>), grid, block, lds, stream, D.state, ds, D);
-            else if (D.n_iter > 1 && is(16, 320, false)) LAUNCH((k_env<MODE_STEP, 16, 320, false, true>), grid, block, lds, stream, D.state, ds, D);
-            else if (D.n_iter > 1 && is(8, 128, false) && D.uni_actions && !D.masks) {
-                // c2's fused uniform rollout: a helper wave per game (helperLoop)
-                KDyn D2 = D;
-                D2.help_off = (int32_t)((lds + 15) & ~(size_t)15);
-                LAUNCH((k_env<MODE_STEP, 8, 128, false, true, true>), grid, dim3(128), (size_t)D2.help_off + 2048, stream,
-                                   D.state, ds, D2);
-            } else if (D.n_iter > 1 && is(8, 128, false)) LAUNCH((k_env<MODE_STEP, 8, 128, false, true>), grid, block, lds, stream, D.state, ds, D);
-            else if (D.n_iter > 1 && is(32, 320, true) && D.obs && !MRTS_NO_PO_HELPER) {
-                // c5's partially observable rollout: a helper wave per game renders the views (helperLoopPO)
-                KDyn D2 = D;
-                D2.help_off = (int32_t)((lds + 15) & ~(size_t)15);
-                LAUNCH((k_env<MODE_STEP, 32, 320, true, true, true>), grid, dim3(128), (size_t)D2.help_off + 4 * (PO_HELP_REC + PO_HELP_REC_WORDS),
-                                   stream, D.state, ds, D2);
-            } else if (D.n_iter > 1 && is(32, 320, true)) LAUNCH((k_env<MODE_STEP, 32, 320, true, true>), grid, block, lds, stream, D.state, ds, D);
-            else if (is(16, 320, false)) LAUNCH((k_env<MODE_STEP, 16, 320, false>), grid, block, lds, stream, D.state, ds, D);
-            else if (is(8, 128, false)) LAUNCH((k_env<MODE_STEP, 8, 128, false>), grid, block, lds, stream, D.state, ds, D);
-            else if (is(32, 320, true)) LAUNCH((k_env<MODE_STEP, 32, 320, true>), grid, block, lds, stream, D.state, ds, D);
-            else if (hs.bot_off) LAUNCH((k_env<MODE_STEP, 0, 0, false, false, false, true>), grid, block, lds, stream, D.state, ds, D);
-            else LAUNCH((k_env<MODE_STEP, 0>), grid, block, lds, stream, D.state, ds, D);
-            break;
-        case MODE_RESET:
-            if (hs.bot_off) LAUNCH((k_env<MODE_RESET, 0, 0, false, false, false, true>), grid, block, lds, stream, D.state, ds, D);
-            else LAUNCH((k_env<MODE_RESET, 0>), grid, block, lds, stream, D.state, ds, D);
-            break;
-        case MODE_PLAYOUT: LAUNCH((k_env<MODE_PLAYOUT, 0>), grid, block, lds, stream, D.state, ds, D); break;
+        case MODE_STEP: {
+            const int s = D.rows == nullptr ? specialisedShape(hs) : -1;
+            const bool multi = D.n_iter > 1;
+            if (s == S16) return steadyLaunch(hs, D) ? EI_STEADY16 : multi ? EI_MULTI16 : EI_STEP16;
+            // c2's fused uniform rollout: a helper wave per game (helperLoop)
+            if (s == S8) return !multi ? EI_STEP8 : (D.uni_actions && !D.masks) ? EI_HELP8 : EI_MULTI8;
+            // c5's partially observable rollout: a helper wave per game renders the views (helperLoopPO)
+            if (s == S32PO) return !multi ? EI_STEP32PO : (D.obs && !MRTS_NO_PO_HELPER) ? EI_HELP32PO : EI_MULTI32PO;
+            return hs.bot_off ? EI_STEP_LR : EI_STEP;
+        }
+        case MODE_RESET: return hs.bot_off ? EI_RESET_LR : EI_RESET;
+        case MODE_PLAYOUT: return EI_PLAYOUT;
         case MODE_TRACE: {
             // the specialised 16x16 / 8x8 step instances' dimensions (their games' code with constant
             // sizes), else the generic kernel
-            const bool fix = !D.trace_generic && hs.utt.K == 79 && hs.utt.ntypes == 7 && hs.utt.maxAttackRadius == 7 &&
-                             hs.H == hs.W && !hs.partial_obs;
-            if (fix && hs.W == 16 && hs.CAP == 320) LAUNCH((k_env<MODE_TRACE, 16, 320>), grid, block, lds, stream, D.state, ds, D);
-            else if (fix && hs.W == 8 && hs.CAP == 128) LAUNCH((k_env<MODE_TRACE, 8, 128>), grid, block, lds, stream, D.state, ds, D);
-            else LAUNCH((k_env<MODE_TRACE, 0>), grid, block, lds, stream, D.state, ds, D);
-        } break;
-        default:LAUNCH((k_env<MODE_MASKS, 0>), grid, block, lds, stream, D.state, ds, D); break;
+            const int s = D.trace_generic ? -1 : specialisedShape(hs, true);
+            return s == S16 ? EI_TRACE16 : s == S8 ? EI_TRACE8 : EI_TRACE;
+        }
+        default: return EI_MASKS;
     }
+}
+hipError_t launchEnv(int mode, const KStatic& hs, const KStatic* ds, const KDyn& D, hipStream_t stream, hipEvent_t e0, hipEvent_t e1) {
+    const size_t lds = handleLdsBytes(hs.HW, hs.W, hs.CAP, hs.partial_obs, hs.bot_off != 0);
+    dim3 grid((unsigned)hs.n_games), block(64);
+    KDyn DH = D;  // a HELP instance's argument: the helper wave's area after the game's LDS
+    DH.help_off = (int32_t)ldsAlign16(lds);
+#define LAUNCH(kern, g_, b_, l_, s_, ...) hipExtLaunchKernelGGL(kern, g_, b_, (uint32_t)(l_), s_, e0, e1, 0, __VA_ARGS__)
+#define ENV(...) LAUNCH((k_env<__VA_ARGS__>), grid, block, lds, stream, D.state, ds, D)
+#define ENV_HELP(bytes, ...) LAUNCH((k_env<__VA_ARGS__>), grid, dim3(128), (size_t)DH.help_off + (bytes), stream, D.state, ds, DH)
+    switch (envInstance(mode, hs, D)) {
+        case EI_STEADY16: ENV(MODE_STEP, 16, 320, false, true, false, false, true); break;
+        case EI_MULTI16: ENV(MODE_STEP, 16, 320, false, true); break;
+        case EI_STEP16: ENV(MODE_STEP, 16, 320, false); break;
+        case EI_HELP8: ENV_HELP(HELP8_LDS, MODE_STEP, 8, 128, false, true, true); break;
+        case EI_MULTI8: ENV(MODE_STEP, 8, 128, false, true); break;
+        case EI_STEP8: ENV(MODE_STEP, 8, 128, false); break;
+        case EI_HELP32PO: ENV_HELP(HELP32PO_LDS, MODE_STEP, 32, 320, true, true, true); break;
+        case EI_MULTI32PO: ENV(MODE_STEP, 32, 320, true, true); break;
+        case EI_STEP32PO: ENV(MODE_STEP, 32, 320, true); break;
+        case EI_STEP_LR: ENV(MODE_STEP, 0, 0, false, false, false, true); break;
+        case EI_STEP: ENV(MODE_STEP, 0); break;
+        case EI_RESET_LR: ENV(MODE_RESET, 0, 0, false, false, false, true); break;
+        case EI_RESET: ENV(MODE_RESET, 0); break;
+        case EI_PLAYOUT: ENV(MODE_PLAYOUT, 0); break;
+        case EI_TRACE16: ENV(MODE_TRACE, 16, 320); break;
+        case EI_TRACE8: ENV(MODE_TRACE, 8, 128); break;
+        case EI_TRACE: ENV(MODE_TRACE, 0); break;
+        case EI_MASKS: ENV(MODE_MASKS, 0); break;
+    }
+#undef ENV_HELP
+#undef ENV
 #undef LAUNCH
     return hipGetLastError();
 }
 // launchEnv(MODE_STEP) would run a specialised self-play kernel (16x16 / 8x8 full observability,
 // 32x32 partially observable), the ones whose games can iterate several steps in one launch
-// (KDyn.n_iter, MULTI instances)
-bool envIterable(const KStatic& hs) {
-    const bool fixable = hs.n_sp_games == hs.n_games && hs.utt.K == 79 && hs.utt.ntypes == 7 && hs.utt.maxAttackRadius == 7 &&
-                         hs.H == hs.W;
-    return fixable && ((hs.W == 16 && hs.CAP == 320 && !hs.partial_obs) || (hs.W == 8 && hs.CAP == 128 && !hs.partial_obs) ||
-                       (hs.W == 32 && hs.CAP == 320 && hs.partial_obs));
-}
-hipError_t prepareLds(size_t bytes) {
-    hipError_t e = hipFuncSetAttribute((const void*)k_env<MODE_STEP, 0>, hipFuncAttributeMaxDynamicSharedMemorySize, (int)bytes);
-    if (e == hipSuccess) e = hipFuncSetAttribute((const void*)k_env<MODE_RESET, 0>, hipFuncAttributeMaxDynamicSharedMemorySize, (int)bytes);
-    if (e == hipSuccess) e = hipFuncSetAttribute((const void*)k_env<MODE_MASKS, 0>, hipFuncAttributeMaxDynamicSharedMemorySize, (int)bytes);
-    if (e == hipSuccess) e = hipFuncSetAttribute((const void*)k_env<MODE_PLAYOUT, 0>, hipFuncAttributeMaxDynamicSharedMemorySize, (int)bytes);
-    if (e == hipSuccess) e = hipFuncSetAttribute((const void*)k_env<MODE_TRACE, 0>, hipFuncAttributeMaxDynamicSharedMemorySize, (int)bytes);
-    if (e == hipSuccess)
-        e = hipFuncSetAttribute((const void*)k_env<MODE_STEP, 0, 0, false, false, false, true>, hipFuncAttributeMaxDynamicSharedMemorySize, (int)bytes);
-    if (e == hipSuccess)
-        e = hipFuncSetAttribute((const void*)k_env<MODE_RESET, 0, 0, false, false, false, true>, hipFuncAttributeMaxDynamicSharedMemorySize, (int)bytes);
-    return e;
-}
-// Unmasked uniform random policy (BASELINE config c2), uniformRow for every cell of
-// every slot.  One thread per (slot, cell): the whole action tensor, dwordx4 + dwordx3 per row.
-__global__ __launch_bounds__(64) void k_policy_uniform(int32_t* __restrict__ actions, int HW, int ntypes, int natt,
-                                                        uint64_t seed, uint32_t step, uint32_t slot_base) {
-    const int slot = (int)blockIdx.y, c = (int)(blockIdx.x * 64 + threadIdx.x);
-    if (c >= HW) return;
-    int32_t a[7];
-    uniformRow(seed, step, slot_base + (uint32_t)slot, c, ntypes, natt, a);
-    int32_t* dst = actions + ((size_t)slot * HW + c) * 7;
-    st4u<false>(dst, a[0], a[1], a[2], a[3]);
-    st3u<false>(dst + 4, a[4], a[5], a[6]);
-}
-hipError_t launchPolicyUniform(int32_t* actions, int n_slots, int HW, int ntypes, int natt, uint64_t seed, uint32_t step,
-                               uint32_t slot_base, hipStream_t stream) {
-    if (n_slots <= 0) return hipSuccess;
-    hipLaunchKernelGGL(k_policy_uniform, dim3((unsigned)((HW + 63) / 64), (unsigned)n_slots), dim3(64), 0, stream, actions, HW,
-                       ntypes, natt, seed, step, slot_base);
-    return hipGetLastError();
-}
+// (KDyn.n_iter, MULTI instances): every shape of SPEC_SHAPES has one
+bool envIterable(const KStatic& hs) { return specialisedShape(hs) >= 0; }
 
-// *prevWritten: the launch recorded its candidate set in Q.prev (a later call may use the delta form)
-hipError_t launchPolicy(const PolicyParams& Q, hipStream_t stream, bool* prevWritten) {
-    dim3 grid((unsigned)((Q.HW + 63) / 64), (unsigned)Q.n_slots), block(64);
-    const bool srcOk = Q.source && ((size_t)Q.HW * Q.K) % 16 == 0 && Q.HW % 4 == 0 && Q.K <= 96 && Q.K >= 65;
-    *prevWritten = srcOk && Q.prev_out;
-    if (srcOk && Q.delta && Q.prev)
-        hipLaunchKernelGGL(k_policy_delta, dim3((unsigned)(((size_t)Q.n_slots * ((Q.HW + 31) / 32) + 63) / 64)), block,
-                           0, stream, Q);
-    else if (srcOk)
-        hipLaunchKernelGGL(k_policy_src, dim3((unsigned)Q.n_slots), block, 0, stream, Q);
-    else if (((size_t)Q.HW * Q.K) % 16 == 0 && (64 * Q.K) % 16 == 0 && Q.HW % 4 == 0 && Q.K <= 96)
-        hipLaunchKernelGGL(k_policy_tiled, grid, block, 0, stream, Q);
-    else
-        hipLaunchKernelGGL(k_policy, grid, block, 0, stream, Q);
-    return hipGetLastError();
+// The handle's LDS bytes, and the selection for a handle and a launch described by a few numbers: EnvInst, plus 256
+// where envIterable holds.  A launch starts from the steady state's arguments (steadyDyn) and changes the fields
+// named.  Not part of include/mrts.h: the tests' view of the host-side facts (tests/test_launch_facts_cpu.py).
+extern "C" int mrts_internal_lds_probe(int HW, int W, int CAP, int po, int light_rush) {
+    return (int)handleLdsBytes(HW, W, CAP, po, light_rush != 0);
 }
-
-// mode: HEAD_SAMPLE / HEAD_SCORE / HEAD_GRAD; one 64-lane block per row (the host checked K - 1 <= HEAD_MAX_LOGITS)
-hipError_t launchHead(int mode, const HeadParams& Q, hipStream_t stream) {
-    if (Q.n_rows <= 0) return hipSuccess;
-    const dim3 grid((unsigned)Q.n_rows), block(64);
-    if (mode == HEAD_SAMPLE) hipLaunchKernelGGL(k_head<HEAD_SAMPLE>, grid, block, 0, stream, Q);
-    else if (mode == HEAD_SCORE) hipLaunchKernelGGL(k_head<HEAD_SCORE>, grid, block, 0, stream, Q);
-    else hipLaunchKernelGGL(k_head<HEAD_GRAD>, grid, block, 0, stream, Q);
-    return hipGetLastError();
-}
-
-// the packed rows' kernels, one 64-lane block per row: HEAD_PACK / HEAD_UNPACK, or HEAD_SCORE / HEAD_GRAD on packed rows
-hipError_t launchHeadPacked(int mode, const HeadPackedParams& P, hipStream_t stream) {
-    if (P.H.n_rows <= 0) return hipSuccess;
-    const dim3 grid((unsigned)P.H.n_rows), block(64);
-    if (mode == HEAD_PACK) hipLaunchKernelGGL(k_head_pack, grid, block, 0, stream, P);
-    else if (mode == HEAD_UNPACK) hipLaunchKernelGGL(k_head_unpack, grid, block, 0, stream, P);
-    else if (mode == HEAD_SCORE) hipLaunchKernelGGL(k_head_packed<HEAD_SCORE>, grid, block, 0, stream, P);
-    else hipLaunchKernelGGL(k_head_packed<HEAD_GRAD>, grid, block, 0, stream, P);
-    return hipGetLastError();
+extern "C" int mrts_internal_launch_probe(int H, int W, int CAP, int po, int K, int ntypes, int radius, int all_selfplay,
+                                          int light_rush, int mode, int n_iter, int rows, int uniform, int masks, int obs) {
+    KStatic hs{};
+    hs.n_games = 512;
+    hs.n_sp_games = all_selfplay ? 512 : 511;
+    hs.utt.K = K;
+    hs.utt.ntypes = ntypes;
+    hs.utt.maxAttackRadius = radius;
+    hs.H = H;
+    hs.W = W;
+    hs.HW = H * W;
+    hs.CAP = CAP;
+    hs.partial_obs = po;
+    hs.bot_off = light_rush ? stateWords(CAP, H * W) : 0;
+    void* const some = g_probeBuf;
+    KDyn D = steadyDyn();
+    D.n_iter = n_iter;
+    D.rows = rows ? (const int32_t*)some : nullptr;
+    D.uni_actions = uniform ? (int32_t*)some : nullptr;
+    if (!masks) D.masks = nullptr;
+    if (!obs) D.obs = nullptr;
+    return (int)envInstance(mode, hs, D) | (envIterable(hs) ? 256 : 0);
 }
 }  // namespace mrts

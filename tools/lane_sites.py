@@ -1,5 +1,6 @@
 #!/usr/bin/env python3
-"""The cross-lane read sites of mrts_kernels.hip and why each reads only lanes that are active.
+"""The cross-lane read sites of the kernels (microrts_amd/csrc: the three .hip units and mrts_device.h) and why each
+reads only lanes that are active.
 
 Lists every `rl()` (readlane) call and every DPP reduction / prefix-sum call site by enclosing function, with the
 argument that its source lanes executed the definition it reads: the call itself runs in wave-uniform control flow
@@ -15,7 +16,10 @@ import re
 import sys
 
 ROOT = os.path.dirname(os.path.dirname(os.path.abspath(__file__)))
-SRC = os.path.join(ROOT, "microrts_amd", "csrc", "mrts_kernels.hip")
+CSRC = os.path.join(ROOT, "microrts_amd", "csrc")
+# the audit build's unit ids (MRTS_UNIT) in order, then the header they share
+UNITS = ["mrts_kernels.hip", "mrts_policy.hip", "mrts_aux.hip"]
+SRCS = UNITS + ["mrts_device.h"]
 
 # function -> why its cross-lane reads are safe
 WHY = {
@@ -100,7 +104,15 @@ WHY = {
 
 
 def sites():
-    lines = open(SRC).read().split("\n")
+    """[(file, line, function, text)]"""
+    out = []
+    for src in SRCS:
+        out += [(src,) + s for s in file_sites(os.path.join(CSRC, src))]
+    return out
+
+
+def file_sites(path):
+    lines = open(path).read().split("\n")
     fn, out = None, []
     for i, l in enumerate(lines, 1):
         m = re.match(r"\s*(?:template\s*<[^>]*>\s*)?(?:static\s+)?(?:DEV|__global__)[^(]*?\b(\w+)\s*\(", l)
@@ -121,18 +133,18 @@ def sites():
 def main():
     md = "--markdown" in sys.argv
     s = sites()
-    missing = sorted({f for _, f, _ in s if f not in WHY})
+    missing = sorted({f for _, _, f, _ in s if f not in WHY})
     by = {}
-    for i, f, _ in s:
-        by.setdefault(f, []).append(i)
+    for src, i, f, _ in s:
+        by.setdefault((src, f), []).append(i)
     if md:
-        print("| function | lines (mrts_kernels.hip) | why the lanes read are active |")
+        print("| function | file: lines | why the lanes read are active |")
         print("|---|---|---|")
-        for f, ls in by.items():
-            print(f"| `{f}` | {', '.join(map(str, ls))} | {WHY.get(f, '**MISSING**')} |")
+        for (src, f), ls in by.items():
+            print(f"| `{f}` | {src}: {', '.join(map(str, ls))} | {WHY.get(f, '**MISSING**')} |")
     else:
-        for i, f, t in s:
-            print(f"{i:5d} {f:20s} {t[:100]}")
+        for src, i, f, t in s:
+            print(f"{src}:{i:<5d} {f:20s} {t[:100]}")
     if missing:
         print(f"sites in functions without a reason: {missing}", file=sys.stderr)
         sys.exit(1)
