@@ -57,7 +57,8 @@ enum {
     MRTS_ERR_OLDER_CONFLICT = 1u << 3,/* issue() older-conflict branch: Java prints (GameState.java:298-317) */
     MRTS_ERR_NEG_RESOURCES = 1u << 4, /* produce skipped at execution: Java prints (UnitAction.java:457-461) */
     MRTS_ERR_MOVE_COLLISION = 1u << 5,/* internal invariant (one unit per cell) violated */
-    MRTS_ERR_RECORD = 1u << 6         /* more live units than an observation record holds (mrts_set_records) */
+    MRTS_ERR_RECORD = 1u << 6,        /* more live units than an observation record holds (mrts_set_records) */
+    MRTS_ERR_INDEX = 1u << 7          /* audit build only: a carried issue index differs from a rebuilt one */
 };
 
 typedef struct {

@@ -252,10 +252,11 @@ DEV int pickBit32(uint32_t r, uint32_t bitsv) {
 // packFwd of a row with every value 0 (each parameter field holds value + 1)
 constexpr uint32_t FWD_ZERO = (1u << 3) | (1u << 6) | (1u << 9) | (1u << 12) | (1u << 15) | (1u << 19);
 // packed (optional): packFwd(a) of the drawn row, built from the picks (no field repacking)
+// picks (optional): the picks themselves — the type (0 = none), the chosen type's parameter pick, the produce type
 // The parameter comes from ONE pick over the chosen type's field, not one pick per case of a switch over the type:
 // the lanes of a wave hold several types, and a switch runs its cases one after the other.
 DEV void sampleBitsRaw(uint64_t seed, uint32_t step, uint32_t slotId, int ntypes, int K, uint64_t lo, uint64_t hi, int c,
-                       int32_t a[7], uint32_t* packed = nullptr) {
+                       int32_t a[7], uint32_t* packed = nullptr, int picks[3] = nullptr) {
     uint32_t ctr[4] = {slotId, step, (uint32_t)c, 0u};
     philox(ctr, (uint32_t)seed, (uint32_t)(seed >> 32));
     // mask slots 1..K-1 as bits of lo:hi (slot k -> bit k - 1): the type field is bits 0..5, the produce
@@ -283,6 +284,11 @@ DEV void sampleBitsRaw(uint64_t seed, uint32_t step, uint32_t slotId, int ntypes
     if (packed)
         *packed = FWD_ZERO + (uint32_t)(t > 0 ? t : 0) + (t > 0 ? (uint32_t)pv << (t == 5 ? 19 : 3 * t) : 0u) +
                   ((uint32_t)ut << 15);
+    if (picks) {
+        picks[0] = t > 0 ? t : 0;
+        picks[1] = pv;
+        picks[2] = ut;
+    }
 }
 
 // Unmasked uniform random row (BASELINE config c2) of cell c of slot id slotId:

@@ -101,7 +101,12 @@ enum { AB_LOAD = 0, AB_OBS = 1, AB_STORE = 2, AB_MASKBITS = 3, AB_RECORD = 4, AB
        // PO observation split: everything but the stores (values kept alive) / only the stores (zeros)
        AB_PO_NOSTORE = 18, AB_PO_ZEROSTORE = 19,
        // PO observation pieces skipped: sight-disk painting, the last-writer cell map, the render record
-       AB_PO_NOPAINT = 20, AB_PO_NOSCELL = 21, AB_PO_NORECORD = 22, AB_PO_NOSNAPSHOT = 23, AB_COUNT = 24 };
+       AB_PO_NOPAINT = 20, AB_PO_NOSCELL = 21, AB_PO_NORECORD = 22, AB_PO_NOSNAPSHOT = 23,
+       // round 9, the step's glue: the forwarded row's decode (decodeFwd on a launch's first step,
+       // else the steady instance's sampledDec + unpack), nextStep, the priority / SIMD-rank block at the top of
+       // the iteration, writeMasksLanes' set-up before maskTables, and cycleLanes' execute loop WITHOUT the
+       // executes (not idempotent): the pick of each ready item and its lane reads
+       AB_DECFWD = 24, AB_NEXTSTEP = 25, AB_PRIO = 26, AB_MASKSETUP = 27, AB_EXECLOOP = 28, AB_COUNT = 29 };
 #endif
 enum { GT_SELFPLAY = 0, GT_AGENT_VS_BOT = 1, GT_BOT_VS_BOT = 2, GT_PLAYOUT = 3 };  // game_kind & 15
 // per-player counters of this step's issued pairs, as the TraceEntry holds them (after issueSafe's
@@ -115,7 +120,8 @@ DEV int prodCategory(uint32_t typeFlags) {  // the reward functions' name tests 
 enum { GK_PASSIVE = 0, GK_RANDOM_BIASED = 1, GK_LIGHT_RUSH = 2 };  // AI kinds (bits 4-7 ai1, 8-11 ai2)
 enum : uint32_t {
     E_CAPACITY = 1u << 0, E_ADDUNIT = 1u << 1, E_PRODUCE_TYPE = 1u << 2, E_OLDER = 1u << 3,
-    E_NEG_RES = 1u << 4, E_COLLISION = 1u << 5, E_RECORD = 1u << 6
+    E_NEG_RES = 1u << 4, E_COLLISION = 1u << 5, E_RECORD = 1u << 6,
+    E_INDEX = 1u << 7  // audit build only: the steady instance's carried issue index differs from a rebuilt one
 };
 // MODE_TRACE per-game result word (KDyn.trace_out)
 enum : uint32_t { TR_ISSUED = 1u, TR_GAMEOVER = 2u, TR_NO_UNIT = 4u };
@@ -246,6 +252,9 @@ struct Game {
     DEV void helperLane() { asm volatile("" : "=v"(lidv) : "0"((int)threadIdx.x - 64)); }
     bool ixValid;
     bool anyMP;
+    // steady instance: the index is carried from step to step of a launch (carryIndex); a present PRODUCE left
+    // since the sums were last right (cycleLanes, kill), so they are walked again at the next step's start
+    bool prodDirty = false;
     // the PRODUCE costs of the issue index, the batch and the candidates summed by a walk over their
     // lanes instead of whole-wave reductions (the masked-policy 16x16 instances: few PRODUCE lanes;
     // c2's uniform rows make many, where the reductions are cheaper; round 5)
@@ -540,7 +549,7 @@ struct Game {
         if (poReload || (!fwdWritten && !D_OFF(uni_actions))) __builtin_amdgcn_fence(__ATOMIC_ACQ_REL, "workgroup");
         fwdWritten = false;
         poLds = false;
-        hset(H_NU, nu);  // "the loaded unit count" of this iteration (PO delta render)
+        if (!steady) hset(H_NU, nu);  // "the loaded unit count" of this iteration (PO delta render)
         if (poRec && !poReload) {  // the previous render's record from its LDS copies
             lkey = (uint32_t)(uint16_t)hp[l] | ((uint32_t)(uint16_t)res[l] << 16);
             lsnap = snap[l];  // after the compaction = the record's snapshot bytes; before clearSnap
@@ -557,12 +566,13 @@ struct Game {
             if (l < 2 * NCW) poPend[l] = (uint32_t)prpd;
             if (l == 0) hdr[HX_POVALID] = prv0;
         }
-        ixValid = false;
+        if (!steady) ixValid = false;  // (steady: carried, see carryIndex)
         deaths = 0;
         polStep++;
         uniStep++;
         // (HX_POVALID stays: it is the PO render record's "views rendered", set by poRecordSnaps)
-        if (l >= H_WORDS && l < 32 && l != HX_POVALID)
+        // (steady: full observability and WinLoss alone — nothing reads the HX_* extras)
+        if (!steady && l >= H_WORDS && l < 32 && l != HX_POVALID)
             hdr[l] = (l >= HX_BASE && l < HX_BASE + 2) ? -1 : (l >= HX_OLDSQ && l < HX_OLDSQ + 2) ? INF : 0;
         wsync();
     }
@@ -575,6 +585,7 @@ struct Game {
         time = 0;
         seq = 0;
         deaths = 0;
+        if (steady) ixValid = false;  // every assignment is gone: the next step builds the index
         pres0 = t[T_RES0];
         pres1 = t[T_RES1];
         nu = nu_t;
@@ -624,7 +635,8 @@ struct Game {
         // action tensor at this cell) and forwarded it in the state block (decodeFwd below, no fetch)
         if (!fwdOn && idle) fetchRow(pl == 0 ? rows0 : rows1, s0 + pl, uy(cu) * W + ux(cu), a);
         const bool useIx = !po && (HW + 2 * W + 31) / 32 <= 64;  // PO: the view's reservations (baseReservations)
-        if (useIx) buildIndex();  // while the rows are in flight
+        if (steady && useIx && ixValid) carryIndex();  // (useIx: a constant of the steady instance's shape)
+        else if (useIx) buildIndex();  // while the rows are in flight
         // PO (round 6): each view's base reservations go to a bitmap of their own in the top words of `scell` (free
         // during the issue: the general render's scratch map is done with; a helper wave's packs and cell map end at
         // word 896 of 32x32's 1,024), so the issue index in `bits` stays valid across both players' issues instead of
@@ -646,9 +658,33 @@ struct Game {
             keepv(t2 + pr2 + ut2 + tx2 + ty2 + (int)bad2);
         }
 #endif
-        if (idle) bad = fwdOn ? decodeFwd(cu, lfwd, t, pr, ut, tx, ty) : decodeFields(cu, a, t, pr, ut, tx, ty);
+        // steady, from the launch's second step on: writeMasksLanes left this row decoded in lfwd (sampledDec)
+        const bool dec = steady && fwdOn && !firstIt;
+        if (dec) {
+            if (idle) {
+                t = ua_type(lfwd);
+                ut = ua_ut(lfwd);
+                tx = ua_tx(lfwd);
+                ty = ua_ty(lfwd);
+                pr = (int)(lfwd >> 24) - 1;
+            }
+        } else if (idle) {
+            bad = fwdOn ? decodeFwd(cu, lfwd, t, pr, ut, tx, ty) : decodeFields(cu, a, t, pr, ut, tx, ty);
+        }
+#ifdef MRTS_ABLATE
+        if (ab(AB_DECFWD) && idle && fwdOn) {
+            if (dec) {
+                const uint32_t w = launder(lfwd);
+                keepv(ua_type(w) + ua_ut(w) + ua_tx(w) + ua_ty(w) + ((int)(w >> 24) - 1) + (int)(w & 0xFFFFFFu));
+            } else {
+                int t2 = 0, pr2 = -1, ut2 = 0, tx2 = 0, ty2 = 0;
+                const bool bad2 = decodeFwd(launder(cu), launder(lfwd), t2, pr2, ut2, tx2, ty2);
+                keepv((int)pack_ua(t2, ut2, tx2, ty2) + pr2 + (int)bad2);
+            }
+        }
+#endif
         if (ballot(bad)) addErr(E_PRODUCE_TYPE);
-        const uint32_t adec = pack_ua(t, ut, tx, ty);
+        const uint32_t adec = dec ? (idle ? lfwd & 0xFFFFFFu : 0u) : pack_ua(t, ut, tx, ty);
         const int c = uy(cu) * W + ux(cu);
         MPHASE(1);
         bool merged = false;
@@ -947,6 +983,19 @@ struct Game {
     // runs each present case's instructions for the whole wave.
     // decodeFields(cu, unpackFwd(w)) straight from a forwarded action word: the direction field picked by
     // the type with one bit-field extract instead of unpacking all seven values and selecting among them
+    // decodeFwd of the row the fused policy's sampler just drew, from its picks (sampleBitsRaw: type t, parameter
+    // pick pv, produce type ut) for the unit with core word cu: pack_ua(t, ut, tx, ty) | (parameter + 1) << 24.  The
+    // picks are members of the unit's mask record, so the tests decodeFwd makes of a foreign row are decided: a
+    // direction is 0..3, a produce type is in the table, an attack target is a unit's cell (on the map).
+    DEV uint32_t sampledDec(uint32_t cu, int t, int pv, int ut) const {
+        // the target cell of window index pv, x | y << 8 in one sum: the unit's x | y << 8, plus pv % R | pv / R << 8
+        // (= pv + (256 - R) (pv / R)), minus the window's centre in both bytes (no byte borrows: the cell is on the map)
+        const uint32_t q = R == 7 ? ((uint32_t)pv * 37u) >> 8 /* pv / 7 for pv < 56 */ : (uint32_t)pv / (uint32_t)R;
+        const uint32_t ctr = (uint32_t)(R / 2);
+        const uint32_t xy = (cu & 0xFFFFu) + (uint32_t)pv + q * (uint32_t)(256 - R) - (ctr | ctr << 8);
+        const bool dirT = (uint32_t)(t - T_MOVE) <= (uint32_t)(T_PRODUCE - T_MOVE);
+        return (uint32_t)t | (uint32_t)ut << 4 | (t == T_ATTACK ? xy << 8 : 0u) | (dirT ? (uint32_t)(pv + 1) << 24 : 0u);
+    }
     DEV bool decodeFwd(uint32_t cu, uint32_t w, int& t, int& pr, int& ut, int& tx, int& ty) const {
         const int ctr = R / 2;
         const int x = ux(cu), y = uy(cu);
@@ -1632,8 +1681,63 @@ struct Game {
             }
         }
         ixValid = true;
+        if (steady) prodDirty = false;
         wsync();
     }
+    // The steady instance's step start in place of buildIndex: the index the previous step of this
+    // launch left is still the state's.  Between a step's issue pass (which keeps the index: issueBothWrite,
+    // issueBatch) and the next one only cycleLanes (the ready assignments), kill (a dead unit's; cycleLanes' last lines) and
+    // resetFromTemplate remove assignments; the first two give the position back — no two present assignments
+    // share one (GameState.issue, rts/GameState.java:252-326: the acceptance chain, issueBothTest and issueBatch
+    // enforce it) — the third, and every path that leaves the lane-parallel ones, clears ixValid.  Left here: the
+    // PRODUCE costs when one of them went.  anyMP is not carried: issueBatch, its one reader, takes it from `bits`.
+    DEV void carryIndex() {
+        if (MRTS_UNLIKELY(prodDirty)) {
+            const bool np = lid() < nu && (lua & UA_PRESENT) && ua_type(lua) == T_PRODUCE;
+            int s0 = 0, s1 = 0, mc0 = -1, mc1 = -1;
+            prodCosts(np, np ? U.cost[ua_ut(lua)] : 0, uplay(lcu) == 0 ? 0 : 1, s0, s1, mc0, mc1);
+            sumProd0 = s0;
+            sumProd1 = s1;
+            maxProd0 = mc0;
+            maxProd1 = mc1;
+            prodDirty = false;
+        }
+#ifdef MRTS_LANE_AUDIT
+        auditIndex();
+#endif
+    }
+#ifdef MRTS_LANE_AUDIT
+    // audit build: the index built the old way into scratch (`rseq`, free at the step's start) against the carried one
+    DEV void auditIndex() {
+        const int NB = (HW + 2 * W + 31) / 32;  // <= 64 (useIx)
+        const int l = lid();
+        uint32_t* const sb = (uint32_t*)rseq;
+        wsync();
+        if (l < NB) sb[l] = 0;
+        wsync();
+        int key = -1;
+        if (l < nu) {
+            const uint32_t a = ua[l];
+            const int t = ua_type(a);
+            if ((a & UA_PRESENT) && (t == T_MOVE || t == T_PRODUCE)) {
+                const uint32_t c = uc[l];
+                const int d = par[l];
+                const int pos = (uy(c) + dyo(d)) * W + ux(c) + dxo(d) + W;
+                atomicOr(&sb[pos >> 5], 1u << (pos & 31));
+                if (t == T_PRODUCE) key = U.cost[ua_ut(a)] | ((uplay(c) == 0 ? 0 : 1) << 16);
+            }
+        }
+        wsync();
+        const int k = key & 0xFFFF;
+        const bool p0 = key >= 0 && (key >> 16) == 0, p1 = key >= 0 && (key >> 16) == 1;
+        const int s0 = wave_sum(p0 ? k : 0), s1 = wave_sum(p1 ? k : 0);
+        const int mc0 = -wave_min(p0 ? -k : 1), mc1 = -wave_min(p1 ? -k : 1);
+        const bool diff = l < NB && sb[l] != bits[l];
+        if (ballot(diff) || s0 != sumProd0 || s1 != sumProd1 || mc0 != maxProd0 || mc1 != maxProd1)
+            addErr(E_INDEX);
+        wsync();
+    }
+#endif
 
     // GameState.issue (rts/GameState.java:252-326) for a batch of (unit s, action) lanes in rank order
     // 0..n-1.  When no new MOVE/PRODUCE conflicts with a present assignment or an earlier one of the
@@ -1674,6 +1778,8 @@ struct Game {
         int ntgt = 0, ncost = 0, pl = 0;
         if (mpm) {
             if (!ixValid) buildIndex();
+            // (steady: a carried index brings no anyMP along — any bit of `bits` is a present MOVE / PRODUCE)
+            if (steady && ballot(np)) anyMP = ballot(lid() < (HW + 2 * W + 31) / 32 && bits[lid()] != 0) != 0;
             if (mp) {
                 const uint32_t cu = cuKnown ? *cuKnown : uc[s];
                 pl = uplay(cu);
@@ -2264,7 +2370,7 @@ struct Game {
     // (ETA + issue time <= time) in insertion order, then remove + execute each in that order.
     DEV void cycle() {
         time++;
-        ixValid = false;
+        if (!steady || nu > 64) ixValid = false;  // (steady: cycleLanes keeps the index, see carryIndex)
         if (MRTS_LIKELY(nu <= 64)) {
             cycleLanes();
             return;
@@ -2372,6 +2478,17 @@ struct Game {
         if (ready) ua[l] = a & ~(UA_READY | UA_PRESENT);
         const bool wk = ready && ua_type(a) != T_NONE;
         const uint64_t work = ballot(wk);
+        // steady, the carried issue index (carryIndex): a MOVE / PRODUCE that leaves the map gives its position back
+        // (buildIndex's position; the unit stands where the assignment found it until its own execute).  A present
+        // MOVE / PRODUCE holds a direction 0..3 (issueSafe's legality test turned any other into NONE), so the
+        // direction's cell offset is byte prm of -W, 1, W, -1 (W <= 127), read by one sign-extending extract
+        const bool mpA = steady && (a & UA_PRESENT) && (ua_type(a) == T_MOVE || ua_type(a) == T_PRODUCE);
+        const uint32_t dirOffs = ((uint32_t)(-W) & 0xFFu) | 1u << 8 | ((uint32_t)W & 0xFFu) << 16 | 0xFFu << 24;
+        const int ipos = uy(cu) * W + ux(cu) + __builtin_amdgcn_sbfe((int)dirOffs, (uint32_t)prm * 8u, 8u) + W;
+        if (steady) {
+            if (mpA && ready) atomicAnd(&bits[ipos >> 5], ~(1u << (ipos & 31)));
+            if (ballot(wk && ua_type(a) == T_PRODUCE)) prodDirty = true;
+        }
         wsync();
         if (!work) return;
         int rank = 0;
@@ -2379,6 +2496,17 @@ struct Game {
         killedLanes = 0;
         readySlot = wk ? l : -1;
         const int nw = __popcll(work);
+#ifdef MRTS_ABLATE
+        if (ab(AB_EXECLOOP)) {  // the loop without its executes: each ready item's pick and lane reads
+            const int rk2 = launder(rank);
+            for (int r = 0; r < nw; r++) {
+                const int k = __builtin_ctzll(ballot(wk && rk2 == r));
+                uint32_t c = uniu((uint32_t)rl((int)cu, k));
+                if ((launder(killedLanes) >> k) & 1ull) c |= UC_DEAD;
+                keepv(c + (uniu((uint32_t)rl((int)a, k)) & ~(UA_READY | UA_PRESENT)) + (uint32_t)rl(prm, k) + (uint32_t)k);
+            }
+        }
+#endif
         for (int r = 0; r < nw; r++) {
             const int k = __builtin_ctzll(ballot(wk && rank == r));
             uint32_t c = uniu((uint32_t)rl((int)cu, k));
@@ -2386,6 +2514,13 @@ struct Game {
             execute(k, c, uniu((uint32_t)rl((int)a, k)) & ~(UA_READY | UA_PRESENT), rl(prm, k));
         }
         readySlot = -1;
+        // steady: a unit killed in the loop takes its assignment with it (kill: GameState.removeUnit,
+        // rts/GameState.java:79-82) — one still present was not ready, so its unit has not moved this cycle
+        if (steady && deaths) {
+            const bool gone = mpA && !ready && (uc[l] & UC_DEAD);
+            if (gone) atomicAnd(&bits[ipos >> 5], ~(1u << (ipos & 31)));
+            if (ballot(gone && ua_type(a) == T_PRODUCE)) prodDirty = true;
+        }
     }
     // PhysicalGameState.gameover/winner (rts/PhysicalGameState.java:334-387)
     DEV void outcome(bool& gameover, int& winner) {
@@ -4323,7 +4458,7 @@ struct Game {
         const bool rowP = !rowS && po && W <= 32 && W >= 16 && 2 * H <= 64;
         uint32_t* rows = rowS ? (uint32_t*)rslot : rowP ? scell + (HW - 2 * H) : nullptr;
         const bool rowB = rowS || rowP;
-        if (rowB && l < 2 * H) rows[l] = 0;
+        if (!steady && rowB && l < 2 * H) rows[l] = 0;
         int si = -1;  // slot index of this lane's unit record, -1 = none
         uint32_t cu = 0;
         if (l < nu) {
@@ -4335,9 +4470,34 @@ struct Game {
             }
         }
         const int c = uy(cu) * W + ux(cu);
+        // steady: the row bitmaps only when an idle unit attacks at range > 1 (farAttackRowsDir, their one reader
+        // there, returns at once otherwise)
+        const bool rowF = rowB && (!steady || ballot(si >= 0 && ((uniu(U.mtAttackFar) >> utyp(cu)) & 1u)) != 0);
+        if (steady && rowF && l < 2 * H) rows[l] = 0;
         wsync();
         if (si >= 0) atomicOr(&nb[si * MW + (c >> 5)], 1u << (c & 31));
-        if (rowB && l < nu && !(cu & UC_DEAD) && uplay(cu) >= 0) atomicOr(&rows[uplay(cu) * H + uy(cu)], 1u << ux(cu));
+        if (rowF && l < nu && !(cu & UC_DEAD) && uplay(cu) >= 0) atomicOr(&rows[uplay(cu) * H + uy(cu)], 1u << ux(cu));
+#ifdef MRTS_ABLATE
+        if (ab(AB_MASKSETUP)) {  // the set-up once more: the same bitmaps cleared and filled again
+            wsync();
+            if (l < NW) nb[l] = 0;
+            if (rowF && l < 2 * H) rows[l] = 0;
+            int si2 = -1;
+            uint32_t cu2 = 0;
+            if (l < nu) {
+                cu2 = launder(uc[l]);
+                if (!(cu2 & UC_DEAD) && !(launder(ua[l]) & UA_PRESENT)) {
+                    const int op = uplay(cu2);
+                    if (op >= 0 && op == pl0) si2 = 0;
+                    else if (nslots > 1 && op >= 0 && op == pl1) si2 = 1;
+                }
+            }
+            const int c2 = uy(cu2) * W + ux(cu2);
+            wsync();
+            if (si2 >= 0) atomicOr(&nb[si2 * MW + (c2 >> 5)], 1u << (c2 & 31));
+            if (rowF && l < nu && !(cu2 & UC_DEAD) && uplay(cu2) >= 0) atomicOr(&rows[uplay(cu2) * H + uy(cu2)], 1u << ux(cu2));
+        }
+#endif
         uint32_t w0 = 0, w1 = 0, w2 = 0;
         {
             MPHASE(16);
@@ -4451,8 +4611,9 @@ struct Game {
                 }
 #endif
                 uint32_t pk;
+                int picks[3];  // steady: the sampler's type, parameter and produce-type picks
                 sampleBitsRaw(D.pol_seed, polStep, D.pol_slot_base + (uint32_t)slot, NT, K, (lo >> 1) | ((uint64_t)w2 << 63),
-                              (uint64_t)(w2 >> 1), c, a, &pk);
+                              (uint64_t)(w2 >> 1), c, a, &pk, steady ? picks : nullptr);
                 if (recOut) {
                     recOut[256 + l] = pk;
                 } else {
@@ -4461,8 +4622,14 @@ struct Game {
                     st3u<WT_MASK>(dst + 4, a[4], a[5], a[6]);
                 }
                 if (fwdW) {
-                    lfwd = pk;  // packFwd(a): the next iteration of a multi-step launch decodes from it
-                    if (lastIt) st1<WT_STATE>(st() + stateFwdOff(CAP, HW) + l, (int32_t)lfwd);  // the next launch's
+                    // packFwd(a): the next launch decodes from it, and so does the next iteration of a multi-step
+                    // launch — but the steady instance's, which takes the row decoded here (no cycle lies between
+                    // the sample and the decode: the unit stands where it stood)
+                    if (lastIt) st1<WT_STATE>(st() + stateFwdOff(CAP, HW) + l, (int32_t)pk);  // the next launch's
+                    lfwd = steady ? sampledDec(cu, picks[0], picks[1], picks[2]) : pk;
+#ifdef MRTS_ABLATE
+                    if (steady && ab(AB_DECFWD)) keepv(sampledDec(launder(cu), launder(picks[0]), launder(picks[1]), launder(picks[2])));
+#endif
                 }
             }
         }
@@ -5521,9 +5688,20 @@ __global__ __launch_bounds__(HELP ? 128 : 64, (HELP || FIX == 16) ? 4 : 1) void 
     const bool ranked = MULTI && FIX == 16 && D_HAS(prio_tab) && niter > 1;
     SimdRank srank;
     if (ranked) srank = simdRankInit(D.prio_tab, D.fwd_stamp);
+    int oc = -1;  // steady: the carried outcome (MODE_STEP below)
     if (HELP && !FPO) __syncthreads();  // A_0: the helper drew step 0's rows
     for (int it = 0; it < niter; it++) {
     if (it > 0) {
+#ifdef MRTS_ABLATE
+        if (G.ab(AB_NEXTSTEP)) {  // once more, from the same flags; the step counters put back
+            const bool fw = G.fwdWritten, pl = G.poLds;
+            G.nextStep();
+            G.fwdWritten = fw;
+            G.poLds = pl;
+            G.polStep--;
+            G.uniStep--;
+        }
+#endif
         G.nextStep();
         freshObs = true;
     }
@@ -5546,6 +5724,14 @@ __global__ __launch_bounds__(HELP ? 128 : 64, (HELP || FIX == 16) ? 4 : 1) void 
             const int wq = G.nu + (int)__popcll(ballot(G.lid() < G.nu && !(G.lua & UA_PRESENT) && uplay(G.lcu) >= 0));
             q = wq >= PRIO_T3 ? 3 : wq >= PRIO_T2 ? 2 : wq >= PRIO_T1 ? 1 : 0;
             if (ranked) {  // from the second step on: the rank among the SIMD's waves by remaining work
+#ifdef MRTS_ABLATE
+                if (G.ab(AB_PRIO)) {  // the idle count and the rank once more (the same entry posted twice)
+                    const int wq2 = G.nu + (int)__popcll(ballot(G.lid() < G.nu && !(launder(G.lua) & UA_PRESENT) && uplay(launder(G.lcu)) >= 0));
+                    SimdRank s2 = srank;
+                    s2.seen = launder(s2.seen);
+                    keepv(simdRankStep(s2, (uint32_t)(wq2 + RANK_C) * (uint32_t)(niter - it)) + (int)s2.seen);
+                }
+#endif
                 const int rk = simdRankStep(srank, (uint32_t)(wq + RANK_C) * (uint32_t)(niter - it));
                 if (it > 0) q = 3 - (rk < 3 ? rk : 3);
             }
@@ -5722,7 +5908,18 @@ __global__ __launch_bounds__(HELP ? 128 : 64, (HELP || FIX == 16) ? 4 : 1) void 
             G.writeRewards(slot0, nslots, selfplay ? 0 : side, selfplay ? 1 : side, gameover, winner);
         }
 #endif
-        G.outcome(gameover, winner);
+        if (steady) {
+            // gameover / winner change only when a unit dies or the game is reset (a PRODUCE adds a unit to a player
+            // that has one): carried between the steps of the launch (oc: winner + 1 | gameover << 2, -1 = not known)
+            if (oc < 0 || G.deaths) {
+                G.outcome(gameover, winner);
+                oc = (winner + 1) | (gameover ? 4 : 0);
+            }
+            gameover = (oc & 4) != 0;
+            winner = (oc & 3) - 1;
+        } else {
+            G.outcome(gameover, winner);
+        }
         // reward functions + VecClient auto-reset on done[0] or max steps, keeping the terminal
         // reward/done and forcing done[0] (tests/JNIGridnetVecClient.java:214-287)
         const int steps = G.hget(H_STEPS) + 1;
@@ -5734,6 +5931,7 @@ __global__ __launch_bounds__(HELP ? 128 : 64, (HELP || FIX == 16) ? 4 : 1) void 
         if (MRTS_UNLIKELY(reset)) {
             G.hset(H_STEPS, 0);  // envSteps[i] = 0 (JNIGridnetVecClient.java:229,264-265,285)
             G.resetFromTemplate();
+            if (steady) oc = -1;
             if (G.po) G.clearSnap();
             if (MRTS_UNLIKELY(lr)) G.lrClear();  // the auto-reset resets the AIs too (JNIBotClient.java:149-167)
         } else {

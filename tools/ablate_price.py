@@ -25,7 +25,10 @@ NAMES = ["load", "obs", "store", "maskbits", "record", "policy", "accept", "lega
          # cyclerank: cycleLanes' ready test and rank
          "gone", "tables", "rank", "decode", "issue", "cyclerank", "SKIP obs", "SKIP records",
          "SKIP PO render pass", "PO render without its stores", "SKIP PO disk painting", "SKIP PO cell map",
-         "SKIP PO render record", "(snapshot)"]
+         "SKIP PO render record", "(snapshot)",
+         # round 9, the step's glue: the forwarded row's decode (first step: decodeFwd; steady: sampledDec + unpack),
+         # nextStep, the priority / SIMD-rank block, writeMasksLanes' set-up, cycleLanes' execute loop without the executes
+         "decodefwd", "nextstep", "prio+rank", "masksetup", "execloop (picks only)"]
 SEED = 0x5EEDC0DE
 
 

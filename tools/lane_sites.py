@@ -30,6 +30,8 @@ WHY = {
     "loadHeader": "called from load() / nextStep() in uniform flow; hv = `l < H_WORDS ? s[l] : 0` is a select on "
                   "every lane, and the lanes read (H_TIME..H_SEQ < H_WORDS) loaded their word",
     "load": "H_FWD read in uniform flow from the same header register as loadHeader",
+    "auditIndex": "audit build only (carryIndex's cross-check, called in uniform flow at the step's start): the "
+                  "reductions take selects defined on every lane (0 / 1 outside the PRODUCE lanes)",
     "baseReservations": "wave_sum of per-lane sums accumulated in a uniform `for (o0 ...)` loop (every lane adds 0 "
                         "outside the list)",
     "cellRank": "uniform loop over the candidate mask m (a ballot); c is the caller's per-lane cell, defined on every "
