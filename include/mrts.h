@@ -16,6 +16,8 @@
  * [pos, ...] with pos = r, in ascending cell order — the MicroRTS-Py gridnet contract.
  *
  * Errors: 0 on success, a negative errno on failure; mrts_last_error() (thread-local) says why.
+ * A null handle is -EINVAL ("null handle") and a failed host allocation -ENOMEM from every entry
+ * point that returns an error code; no C++ exception leaves the library.
  * Java exceptions of the reference become errors: an out-of-range produce type in a decoded row
  * (UnitAction.java:697) → -EINVAL after the step; unit-capacity overflow or an addUnit collision
  * (PhysicalGameState.java:189-201) → -ENOSPC / -EFAULT.  Per-game detail in mrts_error_flags().

@@ -1,6 +1,7 @@
-// mrts_host.cpp — host runtime behind include/mrts.h: map parsing, unit-type tables, per-game
-// state allocation in HBM, kernel launches, the Java-compatible host-pointer API and the
-// canonical state dump.  Compiled by hipcc into microrts_amd/libmrts.so.
+// mrts_host.cpp — host runtime behind include/mrts.h: the handle, per-game state allocation in HBM, kernel
+// launches, the HIP and RCCL plumbing and the Java-compatible host-pointer API.  What needs no GPU (unit-type
+// tables, map parsing, state JSON, the canonical dump, the checkpoint header, mrts_create's configuration half) is
+// in mrts_hostdata.cpp.  Compiled by hipcc into microrts_amd/libmrts.so.
 #include <dlfcn.h>
 #include <hip/hip_runtime.h>
 #include <rccl/rccl.h>  // types only: the entry points are taken from the RCCL library the process loaded
@@ -9,438 +10,31 @@
 #include <cerrno>
 #include <cstdio>
 #include <cstring>
-#include <fstream>
-#include <map>
-#include <sstream>
 #include <string>
 #include <vector>
 
 #include "../../include/mrts.h"
+#include "mrts_hostdata.h"
 #include "mrts_internal.h"
-#include "mrts_json.hpp"
 #include "mrts_launch.h"
 
 using namespace mrts;
 
 static thread_local std::string g_err;
 
-namespace {
-
-struct Fail {
-    int code;
-    std::string msg;
-};
 #define HIPCHK(x)                                                                         \
     do {                                                                                  \
         hipError_t e_ = (x);                                                              \
         if (e_ != hipSuccess) throw Fail{-EIO, std::string(#x) + ": " + hipGetErrorString(e_)}; \
     } while (0)
 
-// ------------------------------------------------------------------ unit type tables
-// The device table (DevUtt) plus what only the host needs: names (map loading, toJSON),
-// returnTime and producedBy (toJSON only; RETURN lasts moveTime, UnitAction.java:321-322).
-struct UttInfo {
-    DevUtt dev;
-    std::vector<std::string> names;
-    std::vector<int> returnT;
-    std::vector<std::vector<int>> producedBy;
-    int typeOf(const std::string& n) const {
-        for (size_t t = 0; t < names.size(); t++)
-            if (names[t] == n) return (int)t;
-        return -1;
-    }
-};
-
-static const char* kTypeNames[7] = {"Resource", "Base", "Barracks", "Worker", "Light", "Heavy", "Ranged"};
-
-// the reward functions' type-name tests as flag bits; K and the attack radius from the table
-static void finishUtt(UttInfo& I) {
-    DevUtt& u = I.dev;
-    for (int t = 0; t < u.ntypes; t++) {
-        const std::string& n = I.names[(size_t)t];
-        if (n == "Resource") u.flags[t] |= N_RESOURCE;
-        if (n == "Base") u.flags[t] |= N_BASE | N_BUILDING;
-        if (n == "Barracks") u.flags[t] |= N_BUILDING;
-        if (n == "Worker") u.flags[t] |= N_WORKER;
-        if (n == "Light" || n == "Heavy" || n == "Ranged") u.flags[t] |= N_COMBAT;
-    }
-    int maxRange = 0;  // UnitTypeTable.getMaxAttackRange (:341-349)
-    for (int t = 0; t < u.ntypes; t++) maxRange = std::max(maxRange, u.range[t]);
-    u.maxAttackRadius = 2 * maxRange + 1;
-    u.K = 1 + 6 + 4 + 4 + 4 + 4 + u.ntypes + u.maxAttackRadius * u.maxAttackRadius;
-    u.mtAttack1 = u.mtAttackFar = u.mtHarvest = u.mtMove = u.mtResource = u.mtStockpile = 0;
-    uint64_t prod = 0;
-    for (int t = 0; t < u.ntypes; t++) {  // the mask tables (Game::maskTables)
-        const uint32_t f = u.flags[t], b = 1u << t;
-        if ((f & F_ATTACK) && u.range[t] == 1) u.mtAttack1 |= b;
-        if ((f & F_ATTACK) && u.range[t] > 1) u.mtAttackFar |= b;
-        if (f & F_HARVEST) u.mtHarvest |= b;
-        if (f & F_MOVE) u.mtMove |= b;
-        if (f & F_RESOURCE) u.mtResource |= b;
-        if (f & F_STOCKPILE) u.mtStockpile |= b;
-        for (int i = 0; i < u.nprod[t]; i++) prod |= (uint64_t)1 << (8 * t + u.prod[t][i]);
-    }
-    u.mtProdLo = (uint32_t)prod;
-    u.mtProdHi = (uint32_t)(prod >> 32);
-    u.maxSight = 0;
-    for (int t = 0; t < u.ntypes; t++) {  // integer floor(sqrt(r^2 - dy^2)): the cells dx^2 + dy^2 <= r^2
-        const int r = u.sight[t];
-        u.maxSight = std::max(u.maxSight, r);
-        u.diskLo[t] = u.diskHi[t] = 0;
-        if (r > 15) continue;  // painted with the sqrt form
-        for (int dy = 0; dy <= r; dy++) {
-            int w = 0;
-            while ((w + 1) * (w + 1) + dy * dy <= r * r) w++;
-            if (dy < 8) u.diskLo[t] |= (uint32_t)w << (4 * dy);
-            else u.diskHi[t] |= (uint32_t)w << (4 * (dy - 8));
-        }
-    }
-}
-
-// new UnitTypeTable(version, crs) — reference src/rts/units/UnitTypeTable.java:104-289
-UttInfo makeUtt(int version, int crs) {
-    if (version < 1 || version > 3) throw Fail{-EINVAL, "utt_version must be 1, 2 or 3"};
-    if (crs < 1 || crs > 3) throw Fail{-EINVAL, "conflict_policy must be 1, 2 or 3"};
-    DevUtt u;
-    std::memset(&u, 0, sizeof(u));
-    u.ntypes = 7;
-    for (int t = 0; t < 7; t++) {  // UnitType defaults (rts/units/UnitType.java:33-100)
-        u.cost[t] = 1;
-        u.hp[t] = 1;
-        u.minD[t] = u.maxD[t] = 1;
-        u.range[t] = 1;
-        u.produceT[t] = u.moveT[t] = u.attackT[t] = u.harvestT[t] = 10;
-        u.harvestAmt[t] = 1;
-        u.sight[t] = 4;
-        u.flags[t] = F_MOVE | F_ATTACK;
-    }
-    const bool v1 = version == 1, v2 = version == 2, v3 = version == 3;
-    // Resource
-    u.flags[0] = F_RESOURCE;
-    u.sight[0] = 0;
-    // Base
-    u.cost[1] = 10; u.hp[1] = 10;
-    if (v1) u.produceT[1] = 250;
-    else if (v2) u.produceT[1] = 200;
-    u.flags[1] = F_STOCKPILE;
-    u.sight[1] = 5;
-    // Barracks
-    u.cost[2] = 5; u.hp[2] = 4;
-    u.produceT[2] = v1 ? 200 : 100;
-    u.flags[2] = 0;
-    u.sight[2] = 3;
-    // Worker
-    u.cost[3] = 1; u.hp[3] = 1;
-    if (v3) { u.minD[3] = 0; u.maxD[3] = 2; }
-    u.range[3] = 1; u.produceT[3] = 50; u.moveT[3] = 10; u.attackT[3] = 5; u.harvestT[3] = 20;
-    u.flags[3] = F_HARVEST | F_MOVE | F_ATTACK;
-    u.sight[3] = 3;
-    // Light
-    u.cost[4] = 2; u.hp[4] = 4;
-    if (v3) { u.minD[4] = 1; u.maxD[4] = 3; } else { u.minD[4] = u.maxD[4] = 2; }
-    u.produceT[4] = 80; u.moveT[4] = 8; u.attackT[4] = 5;
-    u.flags[4] = F_MOVE | F_ATTACK;
-    u.sight[4] = 2;
-    // Heavy
-    if (v3) { u.minD[5] = 0; u.maxD[5] = 6; } else { u.minD[5] = u.maxD[5] = 4; }
-    u.produceT[5] = 120;
-    if (v1) { u.moveT[5] = 12; u.hp[5] = 4; u.cost[5] = 2; } else { u.moveT[5] = 10; u.hp[5] = 8; u.cost[5] = 3; }
-    u.attackT[5] = 5;
-    u.flags[5] = F_MOVE | F_ATTACK;
-    u.sight[5] = 2;
-    // Ranged
-    u.cost[6] = 2; u.hp[6] = 1;
-    if (v3) { u.minD[6] = 1; u.maxD[6] = 2; }
-    u.range[6] = 3; u.produceT[6] = 100; u.moveT[6] = 10; u.attackT[6] = 5;
-    u.flags[6] = F_MOVE | F_ATTACK;
-    u.sight[6] = 3;
-    // produces lists, in declaration order (:283-288)
-    u.nprod[1] = 1; u.prod[1][0] = 3;
-    u.nprod[2] = 3; u.prod[2][0] = 4; u.prod[2][1] = 5; u.prod[2][2] = 6;
-    u.nprod[3] = 2; u.prod[3][0] = 1; u.prod[3][1] = 2;
-    u.crs = crs;
-    UttInfo I;
-    I.dev = u;
-    I.names.assign(kTypeNames, kTypeNames + 7);
-    I.returnT.assign(7, 10);
-    // producedBy in the order of the produces() calls (:283-288): type order here
-    I.producedBy.assign(7, {});
-    for (int t = 0; t < 7; t++)
-        for (int i = 0; i < u.nprod[t]; i++) I.producedBy[(size_t)u.prod[t][i]].push_back(t);
-    finishUtt(I);
-    return I;
-}
-
-// UnitTypeTable.fromJSON (:414-433) + UnitType.createStub / updateFromJSON
-// (UnitType.java:156-161, 217-248), including its quirks: harvestTime is read from "produceTime",
-// returnTime is not read, and absent members take updateFromJSON's defaults (harvestAmount and sightRadius default to 10,
-// canMove / canAttack to false).  Limits of this build: <= 8 types, type IDs equal to their list
-// positions, <= 4 produced types, attack range <= 3 (K <= 80 mask slots: an idle unit's mask is
-// parked as 80 bits in its free assignment words), hp in int16, positive durations; every produced /
-// producedBy name must exist.
-UttInfo uttFromJson(const std::string& text) {
-    mjson::Value o;
-    try {
-        o = mjson::parse(text);
-    } catch (const std::exception& e) {
-        throw Fail{-EINVAL, std::string("utt_json: ") + e.what()};
-    }
-    try {
-        if (o.kind != mjson::Value::OBJ) throw Fail{-EINVAL, "utt_json: not an object"};
-        const int crs = o.getInt("moveConflictResolutionStrategy", 1);
-        if (crs < 1 || crs > 3) throw Fail{-ENOTSUP, "utt_json: moveConflictResolutionStrategy must be 1, 2 or 3"};
-        const mjson::Value& a = o.at("unitTypes");
-        if (a.kind != mjson::Value::ARR) throw Fail{-EINVAL, "utt_json: unitTypes is not an array"};
-        const int n = (int)a.arr.size();
-        if (n < 1 || n > MAX_TYPES) throw Fail{-ENOTSUP, "utt_json: 1..8 unit types supported"};
-        UttInfo I;
-        DevUtt& u = I.dev;
-        std::memset(&u, 0, sizeof(u));
-        u.ntypes = n;
-        u.crs = crs;
-        for (int t = 0; t < n; t++) {  // createStub: ID and name
-            const mjson::Value& ut = a.arr[(size_t)t];
-            if (ut.getInt("ID", -1) != t) throw Fail{-ENOTSUP, "utt_json: type IDs must equal their list positions"};
-            I.names.push_back(ut.getString("name", ""));
-        }
-        I.returnT.assign((size_t)n, 10);
-        I.producedBy.assign((size_t)n, {});
-        auto lookup = [&](const mjson::Value& v) {
-            if (v.kind != mjson::Value::STR) throw Fail{-EINVAL, "utt_json: type names must be strings"};
-            const int k = I.typeOf(v.s);
-            if (k < 0) throw Fail{-EINVAL, "utt_json: unknown unit type " + v.s};
-            return k;
-        };
-        for (int t = 0; t < n; t++) {  // updateFromJSON
-            const mjson::Value& ut = a.arr[(size_t)t];
-            u.cost[t] = ut.getInt("cost", 1);
-            u.hp[t] = ut.getInt("hp", 1);
-            u.minD[t] = ut.getInt("minDamage", 1);
-            u.maxD[t] = ut.getInt("maxDamage", 1);
-            u.range[t] = ut.getInt("attackRange", 1);
-            u.produceT[t] = ut.getInt("produceTime", 10);
-            u.moveT[t] = ut.getInt("moveTime", 10);
-            u.attackT[t] = ut.getInt("attackTime", 10);
-            u.harvestT[t] = ut.getInt("produceTime", 10);  // sic (UnitType.java:227)
-            u.harvestAmt[t] = ut.getInt("harvestAmount", 10);
-            u.sight[t] = ut.getInt("sightRadius", 10);
-            uint32_t f = 0;
-            if (ut.getBool("isResource", false)) f |= F_RESOURCE;
-            if (ut.getBool("isStockpile", false)) f |= F_STOCKPILE;
-            if (ut.getBool("canHarvest", false)) f |= F_HARVEST;
-            if (ut.getBool("canMove", false)) f |= F_MOVE;
-            if (ut.getBool("canAttack", false)) f |= F_ATTACK;
-            u.flags[t] = f;
-            const mjson::Value& pr = ut.at("produces");
-            if (pr.kind != mjson::Value::ARR || pr.arr.size() > (size_t)MAX_PRODUCES)
-                throw Fail{-ENOTSUP, "utt_json: at most 4 produced types per type"};
-            u.nprod[t] = (int)pr.arr.size();
-            for (size_t i = 0; i < pr.arr.size(); i++) u.prod[t][i] = lookup(pr.arr[i]);
-            const mjson::Value& pb = ut.at("producedBy");
-            if (pb.kind != mjson::Value::ARR) throw Fail{-EINVAL, "utt_json: producedBy is not an array"};
-            for (auto& v : pb.arr) I.producedBy[(size_t)t].push_back(lookup(v));
-            if (u.hp[t] < 1 || u.hp[t] > 32767 || u.cost[t] < 0 || u.cost[t] > 32767 || u.minD[t] < 0 ||
-                u.maxD[t] < u.minD[t] || u.maxD[t] > 32767 || u.range[t] < 1 || u.range[t] > 3 ||
-                u.produceT[t] < 1 || u.moveT[t] < 1 || u.attackT[t] < 1 || u.harvestT[t] < 1 ||
-                u.harvestAmt[t] < 0 || u.harvestAmt[t] > 32767 || u.sight[t] < 0 || u.sight[t] > 64)
-                throw Fail{-ENOTSUP, "utt_json: a value of type " + I.names[(size_t)t] + " is outside this build's limits"};
-        }
-        finishUtt(I);
-        return I;
-    } catch (const std::runtime_error& e) {
-        throw Fail{-EINVAL, std::string("utt_json: ") + e.what()};
-    }
-}
-
-// UnitTypeTable.toJSON (:372-383) + UnitType.toJSON (UnitType.java:299-343), byte for byte
-std::string uttToJson(const UttInfo& I) {
-    const DevUtt& u = I.dev;
-    auto b = [](bool v) { return v ? "true" : "false"; };
-    std::ostringstream w;
-    w << "{\"moveConflictResolutionStrategy\":" << u.crs << ",\"unitTypes\":[";
-    for (int t = 0; t < u.ntypes; t++) {
-        if (t) w << ", ";
-        const uint32_t f = u.flags[t];
-        w << "{\"ID\":" << t << ", \"name\":\"" << I.names[(size_t)t] << "\", \"cost\":" << u.cost[t] << ", \"hp\":" << u.hp[t]
-          << ", \"minDamage\":" << u.minD[t] << ", \"maxDamage\":" << u.maxD[t] << ", \"attackRange\":" << u.range[t]
-          << ", \"produceTime\":" << u.produceT[t] << ", \"moveTime\":" << u.moveT[t] << ", \"attackTime\":" << u.attackT[t]
-          << ", \"harvestTime\":" << u.harvestT[t] << ", \"returnTime\":" << I.returnT[(size_t)t]
-          << ", \"harvestAmount\":" << u.harvestAmt[t] << ", \"sightRadius\":" << u.sight[t]
-          << ", \"isResource\":" << b(f & F_RESOURCE) << ", \"isStockpile\":" << b(f & F_STOCKPILE)
-          << ", \"canHarvest\":" << b(f & F_HARVEST) << ", \"canMove\":" << b(f & F_MOVE)
-          << ", \"canAttack\":" << b(f & F_ATTACK) << ", \"produces\":[";
-        for (int i = 0; i < u.nprod[t]; i++) w << (i ? ", " : "") << "\"" << I.names[(size_t)u.prod[t][i]] << "\"";
-        w << "], \"producedBy\":[";
-        for (size_t i = 0; i < I.producedBy[(size_t)t].size(); i++)
-            w << (i ? ", " : "") << "\"" << I.names[(size_t)I.producedBy[(size_t)t][i]] << "\"";
-        w << "]}";
-    }
-    w << "]}";
-    return w.str();
-}
-
-// ------------------------------------------------------------------ XML map reader
-// rts/PhysicalGameState.java:700-726 (fromXML), :765-777 + :577-607 (terrain, raw or A/B RLE),
-// rts/units/Unit.java:597-620 (unit attributes).
-struct MapDef {
-    int W = 0, H = 0;
-    std::vector<uint8_t> terrain;
-    int res[2] = {0, 0};
-    struct U { int type, player, x, y, res, hp; long long id; };
-    std::vector<U> units;
-};
-
-std::string attrOf(const std::string& tag, const char* name) {
-    const std::string key(name);
-    size_t p = 0;
-    while ((p = tag.find(key, p)) != std::string::npos) {
-        const bool start = p == 0 || isspace((unsigned char)tag[p - 1]);
-        size_t q = p + key.size();
-        while (q < tag.size() && isspace((unsigned char)tag[q])) q++;
-        if (start && q < tag.size() && tag[q] == '=') {
-            q++;
-            while (q < tag.size() && isspace((unsigned char)tag[q])) q++;
-            if (q < tag.size() && tag[q] == '"') {
-                const size_t e = tag.find('"', q + 1);
-                return tag.substr(q + 1, e - q - 1);
-            }
-        }
-        p += key.size();
-    }
-    throw Fail{-EINVAL, std::string("map: missing attribute ") + name};
-}
-
-int toInt(const std::string& s) {
-    try {
-        return std::stoi(s);
-    } catch (...) {
-        throw Fail{-EINVAL, "map: bad integer '" + s + "'"};
-    }
-}
-
-// terrain text, raw digits or the A/B run-length form (PhysicalGameState.java:577-607,765-777)
-std::vector<int> decodeTerrain(const std::string& ts, int HW) {
-    std::vector<int> terr;
-    if (ts.find('A') != std::string::npos || ts.find('B') != std::string::npos) {
-        std::string counter;
-        for (char ch : ts) {
-            if (ch == 'A' || ch == 'B') {
-                if (!counter.empty()) {
-                    const int n = toInt(counter);
-                    if (terr.empty() || n < 1 || n > HW) throw Fail{-EINVAL, "terrain: bad run length"};
-                    for (int i = 0; i < n - 1; i++) terr.push_back(terr.back());
-                    counter.clear();
-                }
-                terr.push_back(ch == 'A' ? 0 : 1);
-            } else if (!isspace((unsigned char)ch)) {
-                counter.push_back(ch);
-            }
-        }
-        if (!counter.empty()) {
-            const int n = toInt(counter);
-            if (terr.empty() || n < 1 || n > HW) throw Fail{-EINVAL, "terrain: bad run length"};
-            for (int i = 0; i < n - 1; i++) terr.push_back(terr.back());
-        }
-    } else {
-        for (char ch : ts)
-            if (!isspace((unsigned char)ch)) terr.push_back(ch - '0');
-    }
-    if ((int)terr.size() < HW) throw Fail{-EINVAL, "terrain too short"};
-    return terr;
-}
-
-MapDef parseMap(const std::string& path, const UttInfo& utt) {
-    std::ifstream f(path);
-    if (!f) throw Fail{-ENOENT, "cannot open map " + path};
-    std::stringstream ss;
-    ss << f.rdbuf();
-    const std::string x = ss.str();
-    MapDef m;
-    size_t p = x.find("<rts.PhysicalGameState");
-    if (p == std::string::npos) throw Fail{-EINVAL, "map: no rts.PhysicalGameState in " + path};
-    size_t e = x.find('>', p);
-    const std::string root = x.substr(p, e - p);
-    m.W = toInt(attrOf(root, "width"));
-    m.H = toInt(attrOf(root, "height"));
-    if (m.W <= 0 || m.H <= 0 || m.W > 250 || m.H > 250) throw Fail{-EINVAL, "map: unsupported size"};
-    const size_t t0 = x.find("<terrain>", e), t1 = x.find("</terrain>", t0);
-    if (t0 == std::string::npos || t1 == std::string::npos) throw Fail{-EINVAL, "map: no terrain"};
-    const std::string ts = x.substr(t0 + 9, t1 - t0 - 9);
-    const int HW = m.W * m.H;
-    const std::vector<int> terr = decodeTerrain(ts, HW);
-    m.terrain.resize((size_t)HW);
-    for (int i = 0; i < HW; i++) m.terrain[(size_t)i] = terr[(size_t)i] != 0;
-    const size_t end = x.find("</rts.PhysicalGameState>", t1);
-    size_t q = t1;
-    int np = 0;
-    while (true) {
-        const size_t a = x.find("<rts.Player", q);
-        if (a == std::string::npos || a > end) break;
-        const size_t b = x.find('>', a);
-        const std::string pt = x.substr(a, b - a);
-        const int id = toInt(attrOf(pt, "ID"));
-        if (id != np || np >= 2) throw Fail{-EINVAL, "map: players must be 0 and 1 in order"};
-        m.res[np++] = toInt(attrOf(pt, "resources"));
-        q = b;
-    }
-    if (np != 2) throw Fail{-EINVAL, "map: need exactly 2 players"};
-    q = t1;
-    std::vector<long long> ids;
-    std::vector<uint8_t> occ((size_t)HW, 0);
-    while (true) {
-        const size_t a = x.find("<rts.units.Unit ", q);
-        if (a == std::string::npos || a > end) break;
-        const size_t b = x.find('>', a);
-        const std::string ut = x.substr(a, b - a);
-        MapDef::U u;
-        const std::string tn = attrOf(ut, "type");
-        u.type = utt.typeOf(tn);  // utt.getUnitType(name) (Unit.java:610)
-        if (u.type < 0) throw Fail{-EINVAL, "map: unknown unit type " + tn};
-        u.id = std::stoll(attrOf(ut, "ID"));
-        u.player = toInt(attrOf(ut, "player"));
-        u.x = toInt(attrOf(ut, "x"));
-        u.y = toInt(attrOf(ut, "y"));
-        u.res = toInt(attrOf(ut, "resources"));
-        u.hp = toInt(attrOf(ut, "hitpoints"));
-        if (u.player < -1 || u.player > 1) throw Fail{-EINVAL, "map: unit player out of range"};
-        if (u.x < 0 || u.y < 0 || u.x >= m.W || u.y >= m.H) throw Fail{-EINVAL, "map: unit off the map"};
-        if (u.res < -32768 || u.res > 32767 || u.hp < -32768 || u.hp > 32767) throw Fail{-EINVAL, "map: value exceeds int16"};
-        if (std::find(ids.begin(), ids.end(), u.id) != ids.end()) throw Fail{-EINVAL, "map: repeated unit ID"};
-        if (occ[(size_t)(u.y * m.W + u.x)]) throw Fail{-EINVAL, "map: two units in one position"};  // addUnit :192
-        occ[(size_t)(u.y * m.W + u.x)] = 1;
-        ids.push_back(u.id);
-        m.units.push_back(u);
-        q = b;
-    }
-    return m;
-}
-
-}  // namespace
-
-struct mrts_env {
-    int device = 0;
+struct mrts_env : HandleConfig {
     hipStream_t stream = nullptr;
-    int H = 0, W = 0, HW = 0, CAP = 0, C = 6, K = 79;
-    int nSlots = 0, nGames = 0, nSpGames = 0, maxSteps = 0, partialObs = 0;
-    int forwardModel = 0;  // games advance through mrts_playout* only (GT_PLAYOUT)
-    int botOnly = 0;       // the bot-only client (ai1_kinds): reward / done only, no observation or masks
-    int maxUnits = 0;      // live-unit bound (H*W unless mrts_config.max_units)
-    // native LightRush: the handle has a LightRush game, so every state block carries the bot's memory
-    // (mrts_internal.h botWords) after its stateWords; botTypes = the types named Base, Barracks, Worker, Light
-    int hasLightRush = 0;
-    uint32_t botTypes = 0;
-    size_t blockWords() const { return (size_t)stateWords(CAP, HW) + (hasLightRush ? (size_t)botWords(CAP) : 0); }
     size_t ldsNeed() const { return handleLdsBytes(HW, W, CAP, partialObs, hasLightRush != 0); }
-    uint32_t slotIdBase = 0;
-    DevUtt utt;
-    UttInfo uttInfo;
-    std::vector<int> tmplOffHost;
-    uint32_t cfgHash = 0;  // game kinds, map templates, max_steps, reward kinds, PO (checkpoint compatibility)
     int32_t* d_state = nullptr;
     int32_t* d_tmpl = nullptr;
     int32_t* d_tmplOff = nullptr;
     int32_t* d_gameKind = nullptr;
-    std::vector<int32_t> gameKindHost;
     // library-owned buffers for the host-pointer API
     int32_t* d_actions = nullptr;
     int32_t* d_players = nullptr;
@@ -471,7 +65,6 @@ struct mrts_env {
     int32_t* d_renderErr = nullptr; // the record renders' overflow flag (mrts_render_status)
     unsigned long long* d_packOverflow = nullptr;  // rows mrts_policy_head_pack_dev cut at cap (mrts_policy_head_pack_status)
     int32_t* d_bal = nullptr;       // multi-step launches: balanced game placement (KDyn.bal)
-    int obsImg = 0;                 // KDyn.obs_img: every observation value fits a byte
     bool exPending[2] = {false, false};  // exDone[b] was recorded by an earlier (eager) exchange call
     hipStream_t exLastStream = nullptr;  // the stream of the last eager exchange call (already waits for them)
     // native observation exchange (mrts_exchange_init): an RCCL communicator over this handle's ranks,
@@ -489,7 +82,6 @@ struct mrts_env {
     hipGraphExec_t capExec = nullptr;
     int poWords = 0;
     // delta mask writes: which buffer / player the last mask write went to
-    int maskDelta = 0;
     const uint8_t* lastMaskPtr = nullptr;
     int lastMaskPlayer = -1;
     uint32_t* d_source = nullptr;
@@ -504,7 +96,6 @@ struct mrts_env {
     int32_t* d_copyPairs = nullptr;  // mrts_copy_games staging
     int copyPairsCap = 0;
     float* d_eval = nullptr;         // mrts_evaluate staging
-    std::vector<int32_t> rewardKinds{RF_WINLOSS};  // a_rfs
     const int32_t* lastPolicyActions = nullptr;
     bool polValid = false;
     const int32_t* fusedActions = nullptr;  // buffer the last fused-policy step wrote (delta base), or null
@@ -543,6 +134,38 @@ struct mrts_env {
             lastMaskPtr = D.masks;
             lastMaskPlayer = D.mask_player;
         }
+    }
+    // launch arguments with nothing set (the launches that take no caller buffers fill in their few fields)
+    static KDyn noArgs() {
+        KDyn D;
+        std::memset(&D, 0, sizeof(D));
+        return D;
+    }
+    // The arguments of a reset or step launch from the caller's buffers (grid actions or Java rows, either may be
+    // null), with the mask and observation writes' delta bookkeeping done (prepMasks, then prepObs).  What only one
+    // path sets (fused policy or uniform fields, n_rows, n_iter, records) is added by that path.
+    KDyn launchArgs(const int32_t* actions, const int32_t* rows, const int32_t* players, int32_t* obs, double* reward,
+                    uint8_t* done, uint8_t* masks, int32_t mask_player) {
+        KDyn D = noArgs();
+        D.actions = actions;
+        D.rows = rows;
+        D.players = players;
+        D.obs = obs;
+        D.reward = reward;
+        D.done = done;
+        D.masks = masks;
+        D.mask_player = mask_player;
+        prepMasks(D);
+        prepObs(D);
+        return D;
+    }
+    // the state changed behind the kernels' backs (an injected state, a restore): the next mask, observation and
+    // policy writes are full ones
+    void invalidateWrites() {
+        lastMaskPtr = nullptr;
+        lastObsPtr = nullptr;
+        polValid = false;
+        fusedActions = nullptr;
     }
     void buildStatic() {
         std::memset(&hstatic, 0, sizeof(hstatic));
@@ -593,7 +216,7 @@ struct mrts_env {
         D.prio_tab = D.n_iter > 1 ? d_prioTab : nullptr;
         D.bal = D.n_iter > 1 ? d_bal : nullptr;
         D.obs_img = obsImg;
-        if (mode == 0 /* MODE_STEP */ && respK >= 0 && respRew) {  // the call's Responses ring (RespScope)
+        if (mode == MODE_STEP && respK >= 0 && respRew) {  // the call's Responses ring (RespScope)
             const size_t stride = (size_t)nSlots * hstatic.n_rewards;
             D.reward = respRew + (size_t)respK * stride;
             D.done = respDone + (size_t)respK * stride;
@@ -606,12 +229,7 @@ struct mrts_env {
     // renders (KDyn.obs_img, the uint8 exchange transport) can no longer show it — turn them off for
     // good (300 would have rendered as 44, -5 as 251)
     void noteValues(const int32_t* s) {
-        const int nu = s[H_NU];
-        const int32_t* A = s + H_WORDS;
-        for (int i = 0; i < nu && i < CAP; i++) {
-            const int hpv = A[A_HP * CAP + i], rv = A[A_RES * CAP + i];
-            if (hpv < 0 || hpv > 255 || rv < 0 || rv > 255) obsImg = 0;
-        }
+        if (!valuesFitBytes(s, CAP)) obsImg = 0;
     }
     int gameOfSlot(int slot, int* player) const {
         if (slot < 2 * nSpGames) {
@@ -625,9 +243,18 @@ struct mrts_env {
 
 namespace {
 
-int fail(const Fail& f) {
-    g_err = f.msg;
-    return f.code;
+// Every entry point that returns an error code runs its body through one of these two (guardCall,
+// mrts_hostdata.h): a refusal's text goes to mrts_last_error(), a null handle is -EINVAL "null handle".
+template <class F>
+int guardedCall(F&& body) {
+    return guardCall(g_err, body);
+}
+template <class F>
+int guarded(const mrts_env* env, F&& body) {
+    return guardCall(g_err, [&] {
+        if (!env) throw Fail{-EINVAL, "null handle"};
+        return body();
+    });
 }
 
 hipStream_t pickStream(mrts_env*, void* s) { return (hipStream_t)s; }  // NULL = HIP's default stream, like every HIP API
@@ -650,119 +277,11 @@ const char* mrts_last_error(void) { return g_err.c_str(); }
 
 int mrts_create(const mrts_config* cfg, mrts_env** out) {
     mrts_env* env = nullptr;
-    try {
+    const int r = guardedCall([&] {
         if (!cfg || !out) throw Fail{-EINVAL, "null argument"};
-        if (cfg->n_selfplay_slots < 0 || (cfg->n_selfplay_slots & 1)) throw Fail{-EINVAL, "n_selfplay_slots must be even"};
-        if (cfg->n_bot_envs < 0) throw Fail{-EINVAL, "n_bot_envs < 0"};
-        const int nSlots = cfg->n_selfplay_slots + cfg->n_bot_envs;
-        if (nSlots <= 0) throw Fail{-EINVAL, "no environments"};
-        if (!cfg->map_paths) throw Fail{-EINVAL, "map_paths is null"};
+        const CreatePlan P = planCreate(cfg);  // host-only validation (testable without a GPU); device work starts below
         env = new mrts_env();
-        env->device = cfg->device;
-        env->uttInfo = cfg->utt_json ? uttFromJson(cfg->utt_json) : makeUtt(cfg->utt_version, cfg->conflict_policy);
-        env->utt = env->uttInfo.dev;
-        env->K = env->utt.K;
-        env->C = cfg->partial_obs ? 8 : 6;
-        env->partialObs = cfg->partial_obs;
-        env->maxSteps = cfg->max_steps;
-        env->nSlots = nSlots;
-        env->nSpGames = cfg->n_selfplay_slots / 2;
-        env->nGames = env->nSpGames + cfg->n_bot_envs;
-        env->slotIdBase = (uint32_t)cfg->slot_id_base;
-        env->maskDelta = cfg->mask_delta;
-        if (cfg->n_rewards < 0 || cfg->n_rewards > MAX_REWARDS) throw Fail{-EINVAL, "n_rewards must be 0..8"};
-        if (cfg->n_rewards > 0) {
-            if (!cfg->reward_kinds) throw Fail{-EINVAL, "reward_kinds is null"};
-            env->rewardKinds.assign(cfg->reward_kinds, cfg->reward_kinds + cfg->n_rewards);
-            for (int k : env->rewardKinds)
-                if (k < 0 || k >= RF_COUNT) throw Fail{-EINVAL, "unknown reward function"};
-        }
-        if (cfg->ai1_kinds && cfg->n_selfplay_slots) throw Fail{-EINVAL, "the bot-only client has no self-play slots"};
-        env->forwardModel = cfg->forward_model ? 1 : 0;
-        env->botOnly = cfg->ai1_kinds ? 1 : 0;
-        if (env->forwardModel && !cfg->ai1_kinds) throw Fail{-EINVAL, "a forward model needs ai1_kinds (player 0's playout policy)"};
-        if (env->forwardModel && cfg->partial_obs) throw Fail{-EINVAL, "a forward model plays on the full state (partial_obs must be 0)"};
-        env->gameKindHost.assign((size_t)env->nGames, 0);  // self-play = 0
-        for (int j = 0; j < cfg->n_bot_envs; j++) {
-            const int k2 = cfg->bot_kinds ? cfg->bot_kinds[j] : MRTS_BOT_PASSIVE;
-            const int k1 = cfg->ai1_kinds ? cfg->ai1_kinds[j] : MRTS_BOT_PASSIVE;
-            if (k1 < 0 || k1 > MRTS_BOT_LIGHT_RUSH || k2 < 0 || k2 > MRTS_BOT_LIGHT_RUSH)
-                throw Fail{-ENOTSUP, "only PassiveAI / RandomBiasedAI / LightRush are native"};
-            const int type = env->forwardModel ? 3 : (cfg->ai1_kinds ? 2 : 1);  // GT_PLAYOUT / BOT_VS_BOT / AGENT_VS_BOT
-            if (k1 == MRTS_BOT_LIGHT_RUSH || k2 == MRTS_BOT_LIGHT_RUSH) {
-                // refused, not approximated: a playout policy has no memory to carry between copies of a game, and
-                // JNIGridnetClient.gameStep runs the opponent on its PartiallyObservableGameState
-                // (tests/JNIGridnetClient.java:164-173) — LightRush on a view is a different bot
-                if (env->forwardModel)
-                    throw Fail{-ENOTSUP, "LightRush is not available as a forward-model playout policy (its memory of abstract "
-                                         "actions is not part of a copied game)"};
-                if (cfg->partial_obs && type == 1)
-                    throw Fail{-ENOTSUP, "partial_obs + LightRush opponent: Java runs the bot on the player's partially "
-                                         "observable view, which this build does not compute for LightRush"};
-                int ids[4] = {-1, -1, -1, -1};
-                static const char* const need[4] = {"Base", "Barracks", "Worker", "Light"};
-                for (int q = 0; q < 4; q++)
-                    for (int t = 0; t < env->utt.ntypes; t++)
-                        if (env->uttInfo.names[(size_t)t] == need[q] && ids[q] < 0) ids[q] = t;
-                for (int q = 0; q < 4; q++)
-                    if (ids[q] < 0)
-                        throw Fail{-ENOTSUP, std::string("LightRush needs a unit type named ") + need[q] + " in the unit-type table"};
-                env->botTypes = (uint32_t)ids[0] | ((uint32_t)ids[1] << 4) | ((uint32_t)ids[2] << 8) | ((uint32_t)ids[3] << 12);
-                env->hasLightRush = 1;
-            }
-            env->gameKindHost[(size_t)(env->nSpGames + j)] = type | (k1 << 4) | (k2 << 8);
-            // JNIGridnetClient.gameStep runs the opponent on its PartiallyObservableGameState
-            // (tests/JNIGridnetClient.java:164-173).  The GPU RandomBiasedAI takes getUnitActions of an
-            // owned unit from the full cell map, which equals the view's only when every cell the unit
-            // can act on (its 4 neighbours, its attack disk) lies inside its own sight disk.  Every
-            // built-in table satisfies that; a custom table that does not is refused, not run with
-            // different action lists.
-            if (cfg->partial_obs && type == 1 && k2 == MRTS_BOT_RANDOM_BIASED) {
-                const DevUtt& u = env->utt;
-                for (int t = 0; t < u.ntypes; t++) {
-                    const bool acts = (u.flags[t] & (F_MOVE | F_ATTACK | F_HARVEST)) || u.nprod[t] > 0;
-                    const int need = std::max(1, (u.flags[t] & F_ATTACK) ? u.range[t] : 1);
-                    if (acts && u.sight[t] < need)
-                        throw Fail{-ENOTSUP, "partial_obs + RandomBiasedAI: unit type " + env->uttInfo.names[(size_t)t] +
-                                                 " has sightRadius < max(1, attackRange); its PO action list would "
-                                                 "differ from the full-state one this build computes"};
-                }
-            }
-        }
-        // maps: one template per distinct path
-        std::map<std::string, int> tmplIndex;
-        std::vector<MapDef> maps;
-        std::vector<int> gameTmpl((size_t)env->nGames);
-        for (int g = 0; g < env->nGames; g++) {
-            const int slot = g < env->nSpGames ? 2 * g : 2 * env->nSpGames + (g - env->nSpGames);
-            const char* p = cfg->map_paths[slot];
-            if (!p) throw Fail{-EINVAL, "null map path"};
-            auto it = tmplIndex.find(p);
-            if (it == tmplIndex.end()) {
-                maps.push_back(parseMap(p, env->uttInfo));
-                it = tmplIndex.emplace(p, (int)maps.size() - 1).first;
-            }
-            gameTmpl[(size_t)g] = it->second;
-        }
-        env->H = maps[0].H;
-        env->W = maps[0].W;
-        env->HW = env->H * env->W;
-        for (auto& m : maps)
-            if (m.H != env->H || m.W != env->W) throw Fail{-EINVAL, "all maps must share env 0's size (JNIGridnetVecClient.java:127-133)"};
-        // capacity: one live unit per cell, plus slack for the step's births over its deaths
-        // unit slots: at most one live unit per cell, plus slack for the births of a step over its
-        // deaths (dead slots are compacted at the end of the step).  max_units lowers the bound on
-        // live units (fewer LDS bytes per game -> more games resident per CU); a game that would
-        // exceed it sets MRTS_ERR_CAPACITY instead of continuing.
-        if (cfg->max_units < 0) throw Fail{-EINVAL, "max_units < 0"};
-        const int maxUnits = cfg->max_units ? std::min(cfg->max_units, env->HW) : env->HW;
-        env->CAP = maxUnits + std::max(64, maxUnits / 4);
-        env->maxUnits = maxUnits;
-        if (env->CAP > 0xFFF0) throw Fail{-EINVAL, "map too large"};
-        if ((size_t)env->nSlots * env->HW >= (size_t)1 << 31) throw Fail{-EINVAL, "n_slots * H * W must be < 2^31"};
-        if (env->hasLightRush && env->HW > LR_MAX_CELLS)
-            throw Fail{-ENOTSUP, "LightRush: the map has more than 1024 cells (the size limit of the native A* pathfinder)"};
-        // everything above is host-only validation (testable without a GPU); device work starts here
+        static_cast<HandleConfig&>(*env) = P.cfg;
         HIPCHK(hipSetDevice(cfg->device));
         HIPCHK(hipStreamCreateWithFlags(&env->stream, hipStreamNonBlocking));
         hipDeviceProp_t prop;
@@ -770,56 +289,7 @@ int mrts_create(const mrts_config* cfg, mrts_env** out) {
         const size_t lds = env->ldsNeed();
         if (lds > 160 * 1024) throw Fail{-EINVAL, "map too large for LDS"};
         if (lds > 64 * 1024) HIPCHK(prepareLds(lds));
-        for (auto& m : maps)
-            if ((int)m.units.size() > maxUnits) throw Fail{-ENOSPC, "a map holds more units than max_units"};
-        {  // the hp / resources range an observation plane can show: the maps' units, the table's types
-            // (a unit's hp only falls; its resources fall, or rise by harvestAmount from 0).  A state
-            // injected later (mrts_set_state_json, mrts_restore) can hold other values: noteValues.
-            int mx = 0, mn = 0;
-            for (auto& m : maps)
-                for (auto& u : m.units) {
-                    mx = std::max(mx, std::max(u.hp, u.res));
-                    mn = std::min(mn, std::min(u.hp, u.res));
-                }
-            for (int t = 0; t < env->utt.ntypes; t++) mx = std::max(mx, std::max(env->utt.hp[t], env->utt.harvestAmt[t]));
-            env->obsImg = (mx <= 255 && mn >= 0) ? 1 : 0;
-        }
-        // templates blob
-        std::vector<int32_t> blob;
-        std::vector<int> off;
-        for (auto& m : maps) {
-            off.push_back((int)blob.size());
-            const int nu = (int)m.units.size();
-            blob.push_back(m.H);
-            blob.push_back(m.W);
-            blob.push_back(m.res[0]);
-            blob.push_back(m.res[1]);
-            blob.push_back(nu);
-            std::vector<int32_t> terr((size_t)(env->HW + 3) / 4, 0);
-            std::memcpy(terr.data(), m.terrain.data(), (size_t)env->HW);
-            blob.insert(blob.end(), terr.begin(), terr.end());
-            for (auto& u : m.units)
-                blob.push_back((int32_t)((uint32_t)u.x | ((uint32_t)u.y << 8) | ((uint32_t)u.type << 16) | ((uint32_t)(u.player + 1) << 20)));
-            for (auto& u : m.units) blob.push_back(u.hp);
-            for (auto& u : m.units) blob.push_back(u.res);
-        }
-        env->tmplOffHost.resize((size_t)env->nGames);
-        for (int g = 0; g < env->nGames; g++) env->tmplOffHost[(size_t)g] = off[(size_t)gameTmpl[(size_t)g]];
-        {  // what a state block does not carry but its meaning depends on: a restore must match it
-            uint32_t hv = 2166136261u;
-            auto mix = [&hv](const void* p, size_t n) {
-                for (size_t i = 0; i < n; i++) hv = (hv ^ ((const uint8_t*)p)[i]) * 16777619u;
-            };
-            mix(env->gameKindHost.data(), env->gameKindHost.size() * 4);
-            mix(blob.data(), blob.size() * 4);
-            mix(env->tmplOffHost.data(), env->tmplOffHost.size() * 4);
-            mix(&env->maxSteps, 4);
-            mix(&env->partialObs, sizeof(env->partialObs));
-            const int nrk = (int)env->rewardKinds.size();
-            mix(&nrk, 4);
-            mix(env->rewardKinds.data(), env->rewardKinds.size() * sizeof(env->rewardKinds[0]));
-            env->cfgHash = hv;
-        }
+        if (P.mostMapUnits > env->maxUnits) throw Fail{-ENOSPC, "a map holds more units than max_units"};
         const size_t sw = env->blockWords();
         HIPCHK(hipMalloc(&env->d_state, sw * env->nGames * 4));
         if (env->partialObs && poDeltaShape(env->H, env->W)) {  // PO render records (delta observations)
@@ -827,30 +297,19 @@ int mrts_create(const mrts_config* cfg, mrts_env** out) {
             HIPCHK(hipMalloc(&env->d_poPrev, (size_t)env->poWords * env->nGames * 4));
             HIPCHK(hipMemset(env->d_poPrev, 0, (size_t)env->poWords * env->nGames * 4));
         }
-        HIPCHK(hipMalloc(&env->d_tmpl, blob.size() * 4));
+        HIPCHK(hipMalloc(&env->d_tmpl, P.blob.size() * 4));
         HIPCHK(hipMalloc(&env->d_tmplOff, (size_t)env->nGames * 4));
         HIPCHK(hipMalloc(&env->d_gameKind, (size_t)env->nGames * 4));
-        HIPCHK(hipMemcpy(env->d_tmpl, blob.data(), blob.size() * 4, hipMemcpyHostToDevice));
+        HIPCHK(hipMemcpy(env->d_tmpl, P.blob.data(), P.blob.size() * 4, hipMemcpyHostToDevice));
         HIPCHK(hipMemcpy(env->d_tmplOff, env->tmplOffHost.data(), (size_t)env->nGames * 4, hipMemcpyHostToDevice));
         HIPCHK(hipMemcpy(env->d_gameKind, env->gameKindHost.data(), (size_t)env->nGames * 4, hipMemcpyHostToDevice));
-        // headers: java.util.Random seeds per game (same derivation as the CPU oracle)
+        // headers: the random streams' seeds, the rest zero
+        static_assert(H_RNG_DAMAGE == H_RNG_CANCEL + 2 && H_RNG_SAMPLER == H_RNG_CANCEL + 4, "CreatePlan::rngWords");
         std::vector<int32_t> hdr(sw * env->nGames, 0);
-        auto scramble = [](uint64_t s) { return (s ^ 0x5DEECE66DULL) & ((1ULL << 48) - 1); };
-        for (int g = 0; g < env->nGames; g++) {
-            const int slot = g < env->nSpGames ? 2 * g : 2 * env->nSpGames + (g - env->nSpGames);
-            const uint64_t es = cfg->seed + (uint64_t)(env->slotIdBase + (uint32_t)slot);
-            int32_t* h = &hdr[(size_t)g * sw];
-            const uint64_t rc = scramble(es ^ 0x9E3779B97F4A7C15ULL), rd = scramble(es ^ 0xC2B2AE3D27D4EB4FULL), rs = scramble(es);
-            h[H_RNG_CANCEL] = (int32_t)(uint32_t)rc;
-            h[H_RNG_CANCEL + 1] = (int32_t)(uint32_t)(rc >> 32);
-            h[H_RNG_DAMAGE] = (int32_t)(uint32_t)rd;
-            h[H_RNG_DAMAGE + 1] = (int32_t)(uint32_t)(rd >> 32);
-            h[H_RNG_SAMPLER] = (int32_t)(uint32_t)rs;
-            h[H_RNG_SAMPLER + 1] = (int32_t)(uint32_t)(rs >> 32);
-        }
+        for (int g = 0; g < env->nGames; g++) std::memcpy(&hdr[(size_t)g * sw + H_RNG_CANCEL], &P.rngWords[(size_t)6 * g], 6 * 4);
         HIPCHK(hipMemcpy(env->d_state, hdr.data(), hdr.size() * 4, hipMemcpyHostToDevice));
         // host-API buffers
-        const size_t S = (size_t)nSlots;
+        const size_t S = (size_t)env->nSlots;
         HIPCHK(hipMalloc(&env->d_actions, S * env->HW * 7 * 4));
         HIPCHK(hipMalloc(&env->d_players, S * 4));
         HIPCHK(hipMalloc(&env->d_obs, S * env->C * env->HW * 4));
@@ -881,20 +340,15 @@ int mrts_create(const mrts_config* cfg, mrts_env** out) {
             HIPCHK(hipMemcpy(env->d_bal, bal.data(), bal.size() * 4, hipMemcpyHostToDevice));
         }
         // initial state = reset (the Java constructor loads the maps)
-        KDyn D;
-        std::memset(&D, 0, sizeof(D));
+        KDyn D = mrts_env::noArgs();
         D.players = env->d_players;
-        HIPCHK(env->launch(1, D, env->stream));
+        HIPCHK(env->launch(MODE_RESET, D, env->stream));
         HIPCHK(hipStreamSynchronize(env->stream));
         *out = env;
         return 0;
-    } catch (const Fail& f) {
-        if (env) mrts_destroy(env);
-        return fail(f);
-    } catch (const std::exception& e) {
-        if (env) mrts_destroy(env);
-        return fail(Fail{-EINVAL, e.what()});
-    }
+    });
+    if (r && env) mrts_destroy(env);
+    return r;
 }
 
 int mrts_dims(const mrts_env* env, int32_t* n_slots, int32_t* H, int32_t* W, int32_t* C, int32_t* K) {
@@ -911,49 +365,26 @@ void* mrts_stream(mrts_env* env) { return env ? (void*)env->stream : nullptr; }
 
 int mrts_reset_dev(mrts_env* env, const int32_t* d_players, int32_t* d_obs, double* d_reward, uint8_t* d_done,
                    uint8_t* d_masks, int32_t mask_player, void* stream) {
-    try {
+    return guarded(env, [&] {
         HIPCHK(hipSetDevice(env->device));
-        KDyn D;
-        std::memset(&D, 0, sizeof(D));
-        D.players = d_players;
-        D.obs = d_obs;
-        D.reward = d_reward;
-        D.done = d_done;
-        D.masks = d_masks;
-        D.mask_player = mask_player;
-        env->prepMasks(D);
-        env->prepObs(D);
+        const KDyn D = env->launchArgs(nullptr, nullptr, d_players, d_obs, d_reward, d_done, d_masks, mask_player);
         env->fusedActions = nullptr;
-        HIPCHK(env->launch(1, D, pickStream(env, stream)));
+        HIPCHK(env->launch(MODE_RESET, D, pickStream(env, stream)));
         return 0;
-    } catch (const Fail& f) {
-        return fail(f);
-    }
+    });
 }
 
 int mrts_step_dev(mrts_env* env, const int32_t* d_actions, const int32_t* d_players, int32_t* d_obs, double* d_reward,
                   uint8_t* d_done, uint8_t* d_masks, int32_t mask_player, void* stream) {
-    try {
+    return guarded(env, [&] {
         if (env->forwardModel) throw Fail{-EINVAL, "a forward-model handle advances through mrts_playout*"};
         if (!d_actions) throw Fail{-EINVAL, "actions is null"};
         HIPCHK(hipSetDevice(env->device));
-        KDyn D;
-        std::memset(&D, 0, sizeof(D));
-        D.actions = d_actions;
-        D.players = d_players;
-        D.obs = d_obs;
-        D.reward = d_reward;
-        D.done = d_done;
-        D.masks = d_masks;
-        D.mask_player = mask_player;
-        env->prepMasks(D);
-        env->prepObs(D);
+        const KDyn D = env->launchArgs(d_actions, nullptr, d_players, d_obs, d_reward, d_done, d_masks, mask_player);
         if (d_masks || d_actions == env->fusedActions) env->fusedActions = nullptr;
-        HIPCHK(env->launch(0, D, pickStream(env, stream)));
+        HIPCHK(env->launch(MODE_STEP, D, pickStream(env, stream)));
         return 0;
-    } catch (const Fail& f) {
-        return fail(f);
-    }
+    });
 }
 
 namespace {
@@ -980,17 +411,7 @@ int stepFused(mrts_env* env, int32_t* d_actions, const int32_t* d_players, int32
     if (!d_actions || !d_masks) throw Fail{-EINVAL, "actions and masks are required"};
     if (env->forwardModel) throw Fail{-EINVAL, "a forward-model handle advances through mrts_playout*"};
     HIPCHK(hipSetDevice(env->device));
-    KDyn D;
-    std::memset(&D, 0, sizeof(D));
-    D.actions = d_actions;
-    D.players = d_players;
-    D.obs = d_obs;
-    D.reward = d_reward;
-    D.done = d_done;
-    D.masks = d_masks;
-    D.mask_player = mask_player;
-    env->prepMasks(D);
-    env->prepObs(D);
+    KDyn D = env->launchArgs(d_actions, nullptr, d_players, d_obs, d_reward, d_done, d_masks, mask_player);
     D.pol_actions = d_actions;
     D.pol_seed = seed;
     D.pol_step = next_step;
@@ -1000,7 +421,7 @@ int stepFused(mrts_env* env, int32_t* d_actions, const int32_t* d_players, int32
     const bool steady = D.pol_delta && D.fwd_read && D.mask_delta && envIterable(env->hstatic);
     D.n_iter = (steady && n_iter > 1) ? n_iter : 1;
     planRecords(env, D, rec);
-    HIPCHK(env->launch(0, D, pickStream(env, stream), e0, e1));
+    HIPCHK(env->launch(MODE_STEP, D, pickStream(env, stream), e0, e1));
     env->fusedActions = d_actions;
     if (env->lastPolicyActions == d_actions) env->polValid = false;  // the standalone policy's delta base is stale
     return D.n_iter;
@@ -1010,12 +431,10 @@ int stepFused(mrts_env* env, int32_t* d_actions, const int32_t* d_players, int32
 int mrts_step_fused_dev(mrts_env* env, int32_t* d_actions, const int32_t* d_players, int32_t* d_obs, double* d_reward,
                         uint8_t* d_done, uint8_t* d_masks, int32_t mask_player, uint64_t seed, uint32_t next_step,
                         void* stream) {
-    try {
+    return guarded(env, [&] {
         stepFused(env, d_actions, d_players, d_obs, d_reward, d_done, d_masks, mask_player, seed, next_step, 1, stream);
         return 0;
-    } catch (const Fail& f) {
-        return fail(f);
-    }
+    });
 }
 
 namespace {
@@ -1043,6 +462,7 @@ namespace {
 struct RespScope {
     mrts_env* env;
     RespScope(mrts_env* e, int32_t n_steps) : env(e) {
+        if (n_steps < 0) throw Fail{-EINVAL, "bad rollout arguments"};
         if (!env->respRew) return;
         if (n_steps > env->respMax) throw Fail{-EINVAL, "more steps than the Responses ring holds (mrts_set_step_responses)"};
         env->respK = 0;
@@ -1052,29 +472,30 @@ struct RespScope {
 }  // namespace
 
 int mrts_set_step_responses(mrts_env* env, double* d_rewards, uint8_t* d_dones, int32_t max_steps) {
-    if (!env) return fail(Fail{-EINVAL, "null handle"});
-    if (!d_rewards != !d_dones || (d_rewards && max_steps < 1)) return fail(Fail{-EINVAL, "both rings and max_steps >= 1, or both NULL"});
-    // the kernel forms a ring step's offset as a 32-bit product (it x n_slots x n_rewards)
-    if (d_rewards && (uint64_t)max_steps * (uint64_t)env->nSlots * (uint64_t)env->hstatic.n_rewards >= (1ull << 32))
-        return fail(Fail{-EINVAL, "the Responses ring exceeds 2^32 entries"});
-    env->respRew = d_rewards;
-    env->respDone = d_dones;
-    env->respMax = d_rewards ? max_steps : 0;
-    return 0;
+    return guarded(env, [&] {
+        if (!d_rewards != !d_dones || (d_rewards && max_steps < 1)) throw Fail{-EINVAL, "both rings and max_steps >= 1, or both NULL"};
+        // the kernel forms a ring step's offset as a 32-bit product (it x n_slots x n_rewards)
+        if (d_rewards && (uint64_t)max_steps * (uint64_t)env->nSlots * (uint64_t)env->hstatic.n_rewards >= (1ull << 32))
+            throw Fail{-EINVAL, "the Responses ring exceeds 2^32 entries"};
+        env->respRew = d_rewards;
+        env->respDone = d_dones;
+        env->respMax = d_rewards ? max_steps : 0;
+        return 0;
+    });
 }
 
 int mrts_set_rollout_events(mrts_env* env, void* start, void* end) {
-    if (!env) return fail(Fail{-EINVAL, "null handle"});
-    env->evStart = (hipEvent_t)start;
-    env->evEnd = (hipEvent_t)end;
-    return 0;
+    return guarded(env, [&] {
+        env->evStart = (hipEvent_t)start;
+        env->evEnd = (hipEvent_t)end;
+        return 0;
+    });
 }
 
 int mrts_rollout_fused_dev(mrts_env* env, int32_t* d_actions, const int32_t* d_players, int32_t* d_obs, double* d_reward,
                            uint8_t* d_done, uint8_t* d_masks, int32_t mask_player, uint64_t seed, uint32_t first_next_step,
                            int32_t n_steps, void* stream) {
-    if (!env || n_steps < 0) return fail(Fail{-EINVAL, "bad rollout arguments"});
-    try {
+    return guarded(env, [&] {
         // the timing events ride on the launches: start with the first, end re-recorded by each (the last wins)
         RespScope rs(env, n_steps);
         hipEvent_t e0 = env->evStart, e1 = env->evEnd;
@@ -1090,22 +511,21 @@ int mrts_rollout_fused_dev(mrts_env* env, int32_t* d_actions, const int32_t* d_p
             e0 = nullptr;
         }
         return 0;
-    } catch (const Fail& f) {
-        return fail(f);
-    }
+    });
 }
 
 int mrts_set_multi_step(mrts_env* env, int32_t on) {
-    if (!env) return fail(Fail{-EINVAL, "null handle"});
-    env->multiStep = on ? 1 : 0;
-    return 0;
+    return guarded(env, [&] {
+        env->multiStep = on ? 1 : 0;
+        return 0;
+    });
 }
 
 int mrts_multi_step_capable(const mrts_env* env) { return (env && env->multiStep && envIterable(env->hstatic)) ? 1 : 0; }
 
 int mrts_step_rows_dev(mrts_env* env, const int32_t* d_rows, int32_t n_rows, const int32_t* d_players, int32_t* d_obs,
                        double* d_reward, uint8_t* d_done, uint8_t* d_masks, int32_t mask_player, void* stream) {
-    try {
+    return guarded(env, [&] {
         if (env->forwardModel) throw Fail{-EINVAL, "a forward-model handle advances through mrts_playout*"};
         if (!d_rows && n_rows > 0) throw Fail{-EINVAL, "rows is null"};
         if (n_rows < 0 || (size_t)n_rows * env->nSlots * 8 >= ((size_t)1 << 31)) throw Fail{-EINVAL, "bad n_rows"};
@@ -1118,37 +538,23 @@ int mrts_step_rows_dev(mrts_env* env, const int32_t* d_rows, int32_t n_rows, con
             HIPCHK(hipMalloc(&env->d_pairs, (size_t)env->nGames * n_rows * 2 * 4));
             env->pairsRows = n_rows;
         }
-        KDyn D;
-        std::memset(&D, 0, sizeof(D));
-        D.rows = d_rows;
+        KDyn D = env->launchArgs(nullptr, d_rows, d_players, d_obs, d_reward, d_done, d_masks, mask_player);
         D.n_rows = n_rows;
         D.pairs = env->d_pairs;
-        D.players = d_players;
-        D.obs = d_obs;
-        D.reward = d_reward;
-        D.done = d_done;
-        D.masks = d_masks;
-        D.mask_player = mask_player;
-        env->prepMasks(D);
-        env->prepObs(D);
         if (d_masks) env->fusedActions = nullptr;
-        HIPCHK(env->launch(0, D, pickStream(env, stream)));
+        HIPCHK(env->launch(MODE_STEP, D, pickStream(env, stream)));
         return 0;
-    } catch (const Fail& f) {
-        return fail(f);
-    }
+    });
 }
 
 int mrts_get_masks_i32_dev(mrts_env* env, int32_t player, int32_t* d_out, void* stream) {
-    try {
+    return guarded(env, [&] {
         if (!d_out) throw Fail{-EINVAL, "out is null"};
         int r = mrts_get_masks_dev(env, player, env->d_masks, stream);
         if (r) return r;
         HIPCHK(launchWiden(env->d_masks, d_out, (size_t)env->nSlots * env->HW * env->K, pickStream(env, stream)));
         return 0;
-    } catch (const Fail& f) {
-        return fail(f);
-    }
+    });
 }
 
 int mrts_onehot_features(const mrts_env* env) {
@@ -1157,37 +563,32 @@ int mrts_onehot_features(const mrts_env* env) {
 }
 
 int mrts_onehot_dev(mrts_env* env, const int32_t* d_obs, uint8_t* d_out, void* stream) {
-    try {
+    return guarded(env, [&] {
         if (!d_obs || !d_out) throw Fail{-EINVAL, "null buffer"};
         HIPCHK(hipSetDevice(env->device));
         HIPCHK(launchOneHot(d_obs, d_out, env->nSlots, env->HW, env->C, env->utt.ntypes, pickStream(env, stream)));
         return 0;
-    } catch (const Fail& f) {
-        return fail(f);
-    }
+    });
 }
 
 int mrts_get_masks_dev(mrts_env* env, int32_t player, uint8_t* d_out, void* stream) {
-    try {
+    return guarded(env, [&] {
         if (!d_out) throw Fail{-EINVAL, "out is null"};
         HIPCHK(hipSetDevice(env->device));
-        KDyn D;
-        std::memset(&D, 0, sizeof(D));
+        KDyn D = mrts_env::noArgs();  // no observation write: lastObsPtr stays
         D.masks = d_out;
         D.mask_player = player;
         D.players = env->d_players;
         env->prepMasks(D);
         env->fusedActions = nullptr;
-        HIPCHK(env->launch(2, D, pickStream(env, stream)));
+        HIPCHK(env->launch(MODE_MASKS, D, pickStream(env, stream)));
         return 0;
-    } catch (const Fail& f) {
-        return fail(f);
-    }
+    });
 }
 
 int mrts_policy_uniform_dev(mrts_env* env, uint64_t seed, uint32_t step, int32_t* d_actions, void* stream) {
-    try {
-        if (!env || !d_actions) throw Fail{-EINVAL, "null argument"};
+    return guarded(env, [&] {
+        if (!d_actions) throw Fail{-EINVAL, "null argument"};
         if ((uintptr_t)d_actions & 3) throw Fail{-EINVAL, "misaligned buffer"};
         HIPCHK(hipSetDevice(env->device));
         HIPCHK(launchPolicyUniform(d_actions, env->nSlots, env->HW, env->utt.ntypes, env->K - 23 - env->utt.ntypes, seed, step,
@@ -1196,9 +597,7 @@ int mrts_policy_uniform_dev(mrts_env* env, uint64_t seed, uint32_t step, int32_t
         if (env->fusedActions == d_actions) env->fusedActions = nullptr;
         if (env->lastPolicyActions == d_actions) env->polValid = false;
         return 0;
-    } catch (const Fail& f) {
-        return fail(f);
-    }
+    });
 }
 
 namespace {
@@ -1207,21 +606,11 @@ namespace {
 int stepUniform(mrts_env* env, int32_t* d_actions, const int32_t* d_players, int32_t* d_obs, double* d_reward, uint8_t* d_done,
                 uint8_t* d_masks, int32_t mask_player, uint64_t seed, uint32_t step, int32_t n_iter, void* stream,
                 hipEvent_t e0 = nullptr, hipEvent_t e1 = nullptr, const RecPlan* rec = nullptr) {
-    if (!env || !d_actions) throw Fail{-EINVAL, "null argument"};
+    if (!d_actions) throw Fail{-EINVAL, "null argument"};
     if ((uintptr_t)d_actions & 3) throw Fail{-EINVAL, "misaligned buffer"};
     if (env->forwardModel) throw Fail{-EINVAL, "a forward-model handle advances through mrts_playout*"};
     HIPCHK(hipSetDevice(env->device));
-    KDyn D;
-    std::memset(&D, 0, sizeof(D));
-    D.actions = d_actions;
-    D.players = d_players;
-    D.obs = d_obs;
-    D.reward = d_reward;
-    D.done = d_done;
-    D.masks = d_masks;
-    D.mask_player = mask_player;
-    env->prepMasks(D);
-    env->prepObs(D);
+    KDyn D = env->launchArgs(d_actions, nullptr, d_players, d_obs, d_reward, d_done, d_masks, mask_player);
     D.uni_actions = d_actions;
     D.uni_seed = seed;
     D.uni_step = step;
@@ -1232,28 +621,25 @@ int stepUniform(mrts_env* env, int32_t* d_actions, const int32_t* d_players, int
     planRecords(env, D, rec);
     if (d_masks || env->fusedActions == d_actions) env->fusedActions = nullptr;
     if (env->lastPolicyActions == d_actions) env->polValid = false;
-    HIPCHK(env->launch(0, D, pickStream(env, stream), e0, e1));
+    HIPCHK(env->launch(MODE_STEP, D, pickStream(env, stream), e0, e1));
     return D.n_iter;
 }
 }  // namespace
 
 int mrts_step_uniform_dev(mrts_env* env, int32_t* d_actions, const int32_t* d_players, int32_t* d_obs, double* d_reward,
                           uint8_t* d_done, uint8_t* d_masks, int32_t mask_player, uint64_t seed, uint32_t step, void* stream) {
-    try {
+    return guarded(env, [&] {
         stepUniform(env, d_actions, d_players, d_obs, d_reward, d_done, d_masks, mask_player, seed, step, 1, stream);
         return 0;
-    } catch (const Fail& f) {
-        return fail(f);
-    }
+    });
 }
 
 int mrts_rollout_uniform_dev(mrts_env* env, int32_t* d_actions, const int32_t* d_players, int32_t* d_obs, double* d_reward,
                              uint8_t* d_done, uint64_t seed, uint32_t first_step, int32_t n_steps, int32_t fused,
                              void* stream) {
-    if (!env || n_steps < 0) return fail(Fail{-EINVAL, "bad rollout arguments"});
-    if (fused) {
-        try {
-            RespScope rs(env, n_steps);
+    return guarded(env, [&] {
+        RespScope rs(env, n_steps);
+        if (fused) {
             hipEvent_t e0 = env->evStart, e1 = env->evEnd;  // on the launches (see mrts_rollout_fused_dev)
             env->evStart = env->evEnd = nullptr;
             for (int32_t k = 0; k < n_steps;) {
@@ -1263,21 +649,14 @@ int mrts_rollout_uniform_dev(mrts_env* env, int32_t* d_actions, const int32_t* d
                 e0 = nullptr;
             }
             return 0;
-        } catch (const Fail& f) {
-            return fail(f);
         }
-    }
-    try {
-        RespScope rs(env, n_steps);
         for (int32_t k = 0; k < n_steps; k++) {
             int r = mrts_policy_uniform_dev(env, seed, first_step + (uint32_t)k, d_actions, stream);
             if (!r) r = mrts_step_dev(env, d_actions, d_players, d_obs, d_reward, d_done, nullptr, 0, stream);
             if (r) return r;
         }
-    } catch (const Fail& f) {
-        return fail(f);
-    }
-    return 0;
+        return 0;
+    });
 }
 
 }  // extern "C" (the exchange loop below is a template)
@@ -1445,46 +824,43 @@ void recordsLoop(mrts_env* env, int32_t n_steps, const int32_t* d_obs, uint32_t*
 extern "C" {
 
 int mrts_set_records(mrts_env* env, int32_t units_per_record, int32_t steps_per_launch) {
-    if (!env) return fail(Fail{-EINVAL, "null handle"});
-    if (units_per_record == 0) {
-        env->recUnits = 0;
-        return 0;
-    }
-    if (units_per_record < 1 || units_per_record > 0xFFFF || steps_per_launch < 0)
-        return fail(Fail{-EINVAL, "units per record 1..65535, steps per launch >= 0"});
-    if (env->nSpGames != env->nGames || (env->HW & 3))
-        return fail(Fail{-ENOTSUP, "records: self-play handles, maps whose cell count is a multiple of 4"});
-    if (!env->partialObs && (env->HW > 256 || env->utt.ntypes > 7 || !env->obsImg))
-        return fail(Fail{-ENOTSUP, "records (full observability): maps of <= 256 cells, <= 7 unit types, every observation "
-                                   "value < 256"});
-    if (env->partialObs && (env->HW > 65536 || env->utt.ntypes > 15 || env->hstatic.C != 8 ||
-                            4 * (size_t)(2 * env->HW + 4 * env->H * ((env->W + 31) / 32) + recWords(units_per_record, true)) >
-                                64 * 1024))
-        return fail(Fail{-ENOTSUP, "records (partial observability): <= 15 unit types, the receiver's render state and one "
-                                   "record in 64 KB of LDS"});
-    try {  // the renders' overflow flag: allocated and zeroed here, never on a render path (a lazy
-           // hipMalloc there would break a stream capture, and a null-stream memset is unordered with a
-           // non-blocking render stream)
+    return guarded(env, [&] {
+        if (units_per_record == 0) {
+            env->recUnits = 0;
+            return 0;
+        }
+        if (units_per_record < 1 || units_per_record > 0xFFFF || steps_per_launch < 0)
+            throw Fail{-EINVAL, "units per record 1..65535, steps per launch >= 0"};
+        if (env->nSpGames != env->nGames || (env->HW & 3))
+            throw Fail{-ENOTSUP, "records: self-play handles, maps whose cell count is a multiple of 4"};
+        if (!env->partialObs && (env->HW > 256 || env->utt.ntypes > 7 || !env->obsImg))
+            throw Fail{-ENOTSUP, "records (full observability): maps of <= 256 cells, <= 7 unit types, every observation "
+                                 "value < 256"};
+        if (env->partialObs && (env->HW > 65536 || env->utt.ntypes > 15 || env->hstatic.C != 8 ||
+                                4 * (size_t)(2 * env->HW + 4 * env->H * ((env->W + 31) / 32) + recWords(units_per_record, true)) >
+                                    64 * 1024))
+            throw Fail{-ENOTSUP, "records (partial observability): <= 15 unit types, the receiver's render state and one "
+                                 "record in 64 KB of LDS"};
+        // the renders' overflow flag: allocated and zeroed here, never on a render path (a lazy
+        // hipMalloc there would break a stream capture, and a null-stream memset is unordered with a
+        // non-blocking render stream)
         if (!env->d_renderErr) {
             HIPCHK(hipSetDevice(env->device));
             HIPCHK(hipMalloc(&env->d_renderErr, 4));
             HIPCHK(hipMemset(env->d_renderErr, 0, 4));
             HIPCHK(hipDeviceSynchronize());
         }
-    } catch (const Fail& f) {
-        return fail(f);
-    }
-    env->recUnits = units_per_record;
-    env->recSteps = steps_per_launch;
-    return 0;
+        env->recUnits = units_per_record;
+        env->recSteps = steps_per_launch;
+        return 0;
+    });
 }
 
 int mrts_rollout_fused_records_dev(mrts_env* env, int32_t* d_actions, const int32_t* d_players, int32_t* d_obs,
                                    double* d_reward, uint8_t* d_done, uint8_t* d_masks, int32_t mask_player, uint64_t seed,
                                    uint32_t first_next_step, int32_t n_steps, uint32_t* d_recv, int64_t* step_offsets,
                                    void* stream) {
-    if (!env || n_steps < 0) return fail(Fail{-EINVAL, "bad rollout arguments"});
-    try {
+    return guarded(env, [&] {
         RespScope rs(env, n_steps);
         RolloutEvents ev(env, stream);
         recordsLoop(env, n_steps, d_obs, d_recv, step_offsets, stream, [&](int32_t k, int32_t n, const RecPlan* rp) {
@@ -1493,16 +869,13 @@ int mrts_rollout_fused_records_dev(mrts_env* env, int32_t* d_actions, const int3
         });
         ev.done();
         return 0;
-    } catch (const Fail& f) {
-        return fail(f);
-    }
+    });
 }
 
 int mrts_rollout_uniform_records_dev(mrts_env* env, int32_t* d_actions, const int32_t* d_players, int32_t* d_obs,
                                      double* d_reward, uint8_t* d_done, uint64_t seed, uint32_t first_step, int32_t n_steps,
                                      uint32_t* d_recv, int64_t* step_offsets, void* stream) {
-    if (!env || n_steps < 0) return fail(Fail{-EINVAL, "bad rollout arguments"});
-    try {
+    return guarded(env, [&] {
         RespScope rs(env, n_steps);
         RolloutEvents ev(env, stream);
         recordsLoop(env, n_steps, d_obs, d_recv, step_offsets, stream, [&](int32_t k, int32_t n, const RecPlan* rp) {
@@ -1511,15 +884,13 @@ int mrts_rollout_uniform_records_dev(mrts_env* env, int32_t* d_actions, const in
         });
         ev.done();
         return 0;
-    } catch (const Fail& f) {
-        return fail(f);
-    }
+    });
 }
 
 int mrts_render_records_onehot_dev(mrts_env* env, const uint32_t* d_rec, int64_t rec_words, int32_t n_ranks, int64_t rank_stride,
                                    const int32_t* d_sel, const int64_t* d_step_off, int32_t n_sel, uint8_t* d_out, void* stream) {
-    try {
-        if (!env || !d_rec || !d_out || (n_sel > 0 && !d_sel) || n_sel < 0 || rank_stride < 0 || rec_words < 0 || n_ranks < 1)
+    return guarded(env, [&] {
+        if (!d_rec || !d_out || (n_sel > 0 && !d_sel) || n_sel < 0 || rank_stride < 0 || rec_words < 0 || n_ranks < 1)
             throw Fail{-EINVAL, "bad argument"};
         if (!env->recUnits || !env->d_renderErr) throw Fail{-EINVAL, "mrts_set_records first"};
         if (env->partialObs) throw Fail{-ENOTSUP, "one-hot from records: full observability only"};
@@ -1528,14 +899,11 @@ int mrts_render_records_onehot_dev(mrts_env* env, const uint32_t* d_rec, int64_t
         HIPCHK(launchRenderRecordsOneHot(env->hstatic, env->d_static, d_rec, rec_words, n_ranks, env->recUnits, rank_stride, d_sel,
                                          d_step_off, n_sel, d_out, env->d_renderErr, pickStream(env, stream)));
         return 0;
-    } catch (const Fail& f) {
-        return fail(f);
-    }
+    });
 }
 
 int mrts_render_status(mrts_env* env) {
-    try {
-        if (!env) throw Fail{-EINVAL, "null handle"};
+    return guarded(env, [&] {
         if (!env->d_renderErr) return 0;
         HIPCHK(hipSetDevice(env->device));
         HIPCHK(hipDeviceSynchronize());
@@ -1543,20 +911,17 @@ int mrts_render_status(mrts_env* env) {
         HIPCHK(hipMemcpy(&v, env->d_renderErr, 4, hipMemcpyDeviceToHost));
         if (v) HIPCHK(hipMemset(env->d_renderErr, 0, 4));
         return v ? 1 : 0;
-    } catch (const Fail& f) {
-        return fail(f);
-    }
+    });
 }
 
 int32_t mrts_record_words(const mrts_env* env) {
-    if (!env) return fail(Fail{-EINVAL, "null handle"});
-    return env->recUnits ? recWords(env->recUnits, env->partialObs) : 0;
+    return guarded(env, [&] { return env->recUnits ? recWords(env->recUnits, env->partialObs) : 0; });
 }
 
 int mrts_render_records_dev(mrts_env* env, const uint32_t* d_rec, int64_t rec_words, int32_t n_ranks, int64_t rank_stride,
                             void* d_out, int32_t out_bytes, void* stream) {
-    try {
-        if (!env || !d_rec || !d_out || n_ranks < 1 || rank_stride < 0 || rec_words < 0) throw Fail{-EINVAL, "bad argument"};
+    return guarded(env, [&] {
+        if (!d_rec || !d_out || n_ranks < 1 || rank_stride < 0 || rec_words < 0) throw Fail{-EINVAL, "bad argument"};
         if (!env->recUnits || !env->d_renderErr) throw Fail{-EINVAL, "mrts_set_records first"};
         if (out_bytes != 1 && out_bytes != 4) throw Fail{-EINVAL, "out_bytes: 1 (uint8) or 4 (int32)"};
         if (((uintptr_t)d_out & (out_bytes == 4 ? 15 : 3)) || ((uintptr_t)d_rec & 3)) throw Fail{-EINVAL, "misaligned buffer"};
@@ -1567,25 +932,21 @@ int mrts_render_records_dev(mrts_env* env, const uint32_t* d_rec, int64_t rec_wo
         HIPCHK(launchRenderRecords(env->hstatic, env->d_static, d_rec, env->recUnits, n_ranks, rank_stride, d_out, out_bytes,
                                    env->d_renderErr, pickStream(env, stream)));
         return 0;
-    } catch (const Fail& f) {
-        return fail(f);
-    }
+    });
 }
 
 int mrts_capture_begin(mrts_env* env, void* stream) {
-    try {
-        if (!env || !stream) throw Fail{-EINVAL, "capture needs a handle and a non-default stream"};
+    return guarded(env, [&] {
+        if (!stream) throw Fail{-EINVAL, "capture needs a handle and a non-default stream"};
         HIPCHK(hipSetDevice(env->device));
         HIPCHK(hipStreamBeginCapture((hipStream_t)stream, hipStreamCaptureModeThreadLocal));
         return 0;
-    } catch (const Fail& f) {
-        return fail(f);
-    }
+    });
 }
 
 int mrts_capture_end(mrts_env* env, void* stream) {
-    try {
-        if (!env || !stream) throw Fail{-EINVAL, "capture needs a handle and a non-default stream"};
+    return guarded(env, [&] {
+        if (!stream) throw Fail{-EINVAL, "capture needs a handle and a non-default stream"};
         hipGraph_t g = nullptr;
         HIPCHK(hipStreamEndCapture((hipStream_t)stream, &g));
         if (env->capExec) (void)hipGraphExecDestroy(env->capExec);
@@ -1594,38 +955,43 @@ int mrts_capture_end(mrts_env* env, void* stream) {
         env->capGraph = g;
         HIPCHK(hipGraphInstantiate(&env->capExec, g, nullptr, nullptr, 0));
         return 0;
-    } catch (const Fail& f) {
-        return fail(f);
-    }
+    });
 }
 
 int mrts_replay(mrts_env* env, void* stream) {
-    try {
-        if (!env || !env->capExec) throw Fail{-EINVAL, "nothing captured"};
+    return guarded(env, [&] {
+        if (!env->capExec) throw Fail{-EINVAL, "nothing captured"};
         HIPCHK(hipSetDevice(env->device));
         HIPCHK(hipGraphLaunch(env->capExec, pickStream(env, stream)));
         return 0;
-    } catch (const Fail& f) {
-        return fail(f);
-    }
+    });
 }
 
 int mrts_rccl_unique_id(const char* rccl_path, void* out) {
-    try {
+    return guardedCall([&] {
         if (!out) throw Fail{-EINVAL, "null argument"};
         loadRccl(rccl_path);
         ncclUniqueId id;
         ncclChk(g_rccl.getUniqueId(&id), "ncclGetUniqueId");
         std::memcpy(out, &id, sizeof(id));
         return 0;
-    } catch (const Fail& f) {
-        return fail(f);
-    }
+    });
 }
 
+namespace {
+// the exchange's own stream and per send buffer its step-ready / collective-done events
+void exchangeStreams(mrts_env* env) {
+    HIPCHK(hipStreamCreateWithFlags(&env->exStream, hipStreamNonBlocking));
+    for (int b = 0; b < 2; b++) {
+        HIPCHK(hipEventCreateWithFlags(&env->exReady[b], hipEventDisableTiming));
+        HIPCHK(hipEventCreateWithFlags(&env->exDone[b], hipEventDisableTiming));
+    }
+}
+}  // namespace
+
 int mrts_exchange_init(mrts_env* env, const char* rccl_path, int32_t nranks, int32_t rank, const void* unique_id) {
-    try {
-        if (!env || !unique_id || nranks < 1 || rank < 0 || rank >= nranks) throw Fail{-EINVAL, "bad exchange arguments"};
+    return guarded(env, [&] {
+        if (!unique_id || nranks < 1 || rank < 0 || rank >= nranks) throw Fail{-EINVAL, "bad exchange arguments"};
         if (exInited(env)) throw Fail{-EINVAL, "the exchange is already initialised"};
         loadRccl(rccl_path);
         HIPCHK(hipSetDevice(env->device));
@@ -1634,42 +1000,29 @@ int mrts_exchange_init(mrts_env* env, const char* rccl_path, int32_t nranks, int
         ncclChk(g_rccl.commInitRank(&env->exComm, nranks, id, rank), "ncclCommInitRank");
         env->exRanks = nranks;
         env->exRank = rank;
-        HIPCHK(hipStreamCreateWithFlags(&env->exStream, hipStreamNonBlocking));
-        for (int b = 0; b < 2; b++) {
-            HIPCHK(hipEventCreateWithFlags(&env->exReady[b], hipEventDisableTiming));
-            HIPCHK(hipEventCreateWithFlags(&env->exDone[b], hipEventDisableTiming));
-        }
+        exchangeStreams(env);
         return 0;
-    } catch (const Fail& f) {
-        return fail(f);
-    }
+    });
 }
 
 int mrts_exchange_init_loopback(mrts_env* env, int32_t nranks, int32_t rank) {
-    try {
-        if (!env || nranks < 1 || rank < 0 || rank >= nranks) throw Fail{-EINVAL, "bad exchange arguments"};
+    return guarded(env, [&] {
+        if (nranks < 1 || rank < 0 || rank >= nranks) throw Fail{-EINVAL, "bad exchange arguments"};
         if (exInited(env)) throw Fail{-EINVAL, "the exchange is already initialised"};
         HIPCHK(hipSetDevice(env->device));
-        HIPCHK(hipStreamCreateWithFlags(&env->exStream, hipStreamNonBlocking));
-        for (int b = 0; b < 2; b++) {
-            HIPCHK(hipEventCreateWithFlags(&env->exReady[b], hipEventDisableTiming));
-            HIPCHK(hipEventCreateWithFlags(&env->exDone[b], hipEventDisableTiming));
-        }
+        exchangeStreams(env);
         env->exRanks = nranks;
         env->exRank = rank;
         env->exLoop = true;
         return 0;
-    } catch (const Fail& f) {
-        return fail(f);
-    }
+    });
 }
 
 int mrts_rollout_fused_exchange_dev(mrts_env* env, int32_t* d_actions, const int32_t* d_players, int32_t* d_obs,
                                     double* d_reward, uint8_t* d_done, uint8_t* d_masks, int32_t mask_player, uint64_t seed,
                                     uint32_t first_next_step, int32_t n_steps, int16_t* d_send0, int16_t* d_send1,
                                     int16_t* d_recv, void* stream) {
-    if (!env || n_steps < 0) return fail(Fail{-EINVAL, "bad rollout arguments"});
-    try {
+    return guarded(env, [&] {
         RespScope rs(env, n_steps);
         RolloutEvents ev(env, stream);
         exchangeLoop(env, n_steps, d_obs, d_send0, d_send1, d_recv, stream, [&](int32_t k) {
@@ -1678,16 +1031,13 @@ int mrts_rollout_fused_exchange_dev(mrts_env* env, int32_t* d_actions, const int
         });
         ev.done();
         return 0;
-    } catch (const Fail& f) {
-        return fail(f);
-    }
+    });
 }
 
 int mrts_rollout_uniform_exchange_dev(mrts_env* env, int32_t* d_actions, const int32_t* d_players, int32_t* d_obs,
                                       double* d_reward, uint8_t* d_done, uint64_t seed, uint32_t first_step, int32_t n_steps,
                                       int16_t* d_send0, int16_t* d_send1, int16_t* d_recv, void* stream) {
-    if (!env || n_steps < 0) return fail(Fail{-EINVAL, "bad rollout arguments"});
-    try {
+    return guarded(env, [&] {
         RespScope rs(env, n_steps);
         RolloutEvents ev(env, stream);
         exchangeLoop(env, n_steps, d_obs, d_send0, d_send1, d_recv, stream, [&](int32_t k) {
@@ -1696,64 +1046,68 @@ int mrts_rollout_uniform_exchange_dev(mrts_env* env, int32_t* d_actions, const i
         });
         ev.done();
         return 0;
-    } catch (const Fail& f) {
-        return fail(f);
-    }
+    });
 }
 
 int mrts_policy_invalidate(mrts_env* env) {
-    if (!env) return fail(Fail{-EINVAL, "null handle"});
-    env->polValid = false;
-    env->fusedActions = nullptr;
-    return 0;
+    return guarded(env, [&] {
+        env->polValid = false;
+        env->fusedActions = nullptr;
+        return 0;
+    });
 }
 
 int mrts_set_obs_delta(mrts_env* env, int32_t on) {
-    if (!env) return fail(Fail{-EINVAL, "null handle"});
-    env->obsDelta = on ? 1 : 0;
-    env->lastObsPtr = nullptr;
-    return 0;
+    return guarded(env, [&] {
+        env->obsDelta = on ? 1 : 0;
+        env->lastObsPtr = nullptr;
+        return 0;
+    });
 }
 
 int mrts_set_exchange_bytes(mrts_env* env, int32_t bytes_per_value) {
-    if (!env) return fail(Fail{-EINVAL, "null handle"});
-    if (bytes_per_value == 2) {
-        env->exBytes = 2;
+    return guarded(env, [&] {
+        if (bytes_per_value == 2) {
+            env->exBytes = 2;
+            return 0;
+        }
+        if (bytes_per_value != 1) throw Fail{-EINVAL, "bytes per value: 1 or 2"};
+        // the uint8 transport is written by the 16x16 byte-image render and the one-cell-per-lane render of
+        // maps of <= 64 cells: full observability whose every value fits a byte (checked at create over the
+        // maps and the unit-type table)
+        if (env->partialObs || !(env->HW == 256 || env->HW <= 64) || !env->obsImg)
+            throw Fail{-ENOTSUP, "uint8 exchange: full observability on 16x16 or <= 64-cell maps, every value < 256"};
+        env->exBytes = 1;
         return 0;
-    }
-    if (bytes_per_value != 1) return fail(Fail{-EINVAL, "bytes per value: 1 or 2"});
-    // the uint8 transport is written by the 16x16 byte-image render and the one-cell-per-lane render of
-    // maps of <= 64 cells: full observability whose every value fits a byte (checked at create over the
-    // maps and the unit-type table)
-    if (env->partialObs || !(env->HW == 256 || env->HW <= 64) || !env->obsImg)
-        return fail(Fail{-ENOTSUP, "uint8 exchange: full observability on 16x16 or <= 64-cell maps, every value < 256"});
-    env->exBytes = 1;
-    return 0;
+    });
 }
 
 int mrts_set_obs16(mrts_env* env, int16_t* d_obs16) {
-    if (!env) return fail(Fail{-EINVAL, "null handle"});
-    if (d_obs16 && env->partialObs) return fail(Fail{-EINVAL, "the int16 observation copy is for full observability"});
-    if ((uintptr_t)d_obs16 & 7) return fail(Fail{-EINVAL, "misaligned buffer (8 bytes)"});
-    env->obs16 = d_obs16;
-    return 0;
+    return guarded(env, [&] {
+        if (d_obs16 && env->partialObs) throw Fail{-EINVAL, "the int16 observation copy is for full observability"};
+        if ((uintptr_t)d_obs16 & 7) throw Fail{-EINVAL, "misaligned buffer (8 bytes)"};
+        env->obs16 = d_obs16;
+        return 0;
+    });
 }
 
 int mrts_obs_invalidate(mrts_env* env) {
-    if (!env) return fail(Fail{-EINVAL, "null handle"});
-    env->lastObsPtr = nullptr;
-    return 0;
+    return guarded(env, [&] {
+        env->lastObsPtr = nullptr;
+        return 0;
+    });
 }
 
 int mrts_set_source_output(mrts_env* env, uint32_t* d_source) {
-    if (!env) return -EINVAL;
-    env->d_source = d_source;
-    return 0;
+    return guarded(env, [&] {
+        env->d_source = d_source;
+        return 0;
+    });
 }
 
 int mrts_policy_dev(mrts_env* env, const uint8_t* d_masks, const uint32_t* d_source, uint64_t seed, uint32_t step,
                     int32_t* d_actions, void* stream) {
-    try {
+    return guarded(env, [&] {
         HIPCHK(hipSetDevice(env->device));
         PolicyParams Q;
         Q.HW = env->HW;
@@ -1783,15 +1137,12 @@ int mrts_policy_dev(mrts_env* env, const uint8_t* d_masks, const uint32_t* d_sou
         if (prevWritten) env->polParity ^= 1;
         env->lastPolicyActions = d_actions;
         return 0;
-    } catch (const Fail& f) {
-        return fail(f);
-    }
+    });
 }
 
 namespace {
 // the policy head's shared argument checks; n_rows rows of the handle's H*W cells
 HeadParams headParams(mrts_env* env, int32_t n_rows, const float* d_logits, const uint8_t* d_masks, const int32_t* d_actions) {
-    if (!env) throw Fail{-EINVAL, "null handle"};
     if (env->botOnly || env->forwardModel)
         throw Fail{-ENOTSUP, "the policy head needs a handle that writes masks (not a bot-only or forward-model handle)"};
     if (!d_logits || !d_masks || !d_actions) throw Fail{-EINVAL, "null argument"};
@@ -1817,8 +1168,8 @@ HeadParams headParams(mrts_env* env, int32_t n_rows, const float* d_logits, cons
 int mrts_policy_head_sample_dev(mrts_env* env, const float* d_logits, const uint8_t* d_masks, const uint32_t* d_source,
                                 uint64_t seed, uint32_t step, int32_t* d_actions, float* d_logprob, float* d_entropy,
                                 void* stream) {
-    try {
-        HeadParams Q = headParams(env, env ? env->nSlots : 0, d_logits, d_masks, d_actions);
+    return guarded(env, [&] {
+        HeadParams Q = headParams(env, env->nSlots, d_logits, d_masks, d_actions);
         if (((uintptr_t)d_source & 3) || ((uintptr_t)d_logprob & 3) || ((uintptr_t)d_entropy & 3)) throw Fail{-EINVAL, "misaligned buffer"};
         HIPCHK(hipSetDevice(env->device));
         Q.source = d_source;
@@ -1831,14 +1182,12 @@ int mrts_policy_head_sample_dev(mrts_env* env, const float* d_logits, const uint
         env->fusedActions = nullptr;
         HIPCHK(launchHead(HEAD_SAMPLE, Q, pickStream(env, stream)));
         return 0;
-    } catch (const Fail& f) {
-        return fail(f);
-    }
+    });
 }
 
 int mrts_policy_head_score_dev(mrts_env* env, int32_t n_rows, const float* d_logits, const uint8_t* d_masks,
                                const int32_t* d_actions, float* d_logprob, float* d_entropy, void* stream) {
-    try {
+    return guarded(env, [&] {
         HeadParams Q = headParams(env, n_rows, d_logits, d_masks, d_actions);
         if (((uintptr_t)d_logprob & 3) || ((uintptr_t)d_entropy & 3)) throw Fail{-EINVAL, "misaligned buffer"};
         HIPCHK(hipSetDevice(env->device));
@@ -1846,15 +1195,13 @@ int mrts_policy_head_score_dev(mrts_env* env, int32_t n_rows, const float* d_log
         Q.entropy = d_entropy;
         HIPCHK(launchHead(HEAD_SCORE, Q, pickStream(env, stream)));
         return 0;
-    } catch (const Fail& f) {
-        return fail(f);
-    }
+    });
 }
 
 int mrts_policy_head_grad_dev(mrts_env* env, int32_t n_rows, const float* d_logits, const uint8_t* d_masks,
                               const int32_t* d_actions, const float* d_g_logprob, const float* d_g_entropy,
                               float* d_grad_logits, void* stream) {
-    try {
+    return guarded(env, [&] {
         HeadParams Q = headParams(env, n_rows, d_logits, d_masks, d_actions);
         if (!d_grad_logits) throw Fail{-EINVAL, "null argument"};
         if (((uintptr_t)d_g_logprob & 3) || ((uintptr_t)d_g_entropy & 3) || ((uintptr_t)d_grad_logits & 3))
@@ -1865,15 +1212,12 @@ int mrts_policy_head_grad_dev(mrts_env* env, int32_t n_rows, const float* d_logi
         Q.grad = d_grad_logits;
         HIPCHK(launchHead(HEAD_GRAD, Q, pickStream(env, stream)));
         return 0;
-    } catch (const Fail& f) {
-        return fail(f);
-    }
+    });
 }
 
 namespace {
 // the packed rows' shared argument checks: the handle as headParams wants it, n_rows rows of H*W cells, 1 <= cap <= H*W
 HeadPackedParams headPackedParams(mrts_env* env, int32_t n_rows, int32_t cap) {
-    if (!env) throw Fail{-EINVAL, "null handle"};
     if (env->botOnly || env->forwardModel)
         throw Fail{-ENOTSUP, "the policy head needs a handle that writes masks (not a bot-only or forward-model handle)"};
     if (n_rows < 0 || (int64_t)n_rows * env->HW >= ((int64_t)1 << 31)) throw Fail{-EINVAL, "n_rows: 0 <= n_rows * H*W < 2^31"};
@@ -1904,15 +1248,16 @@ void headPackedSource(HeadPackedParams& P, const uint32_t* d_packed, int32_t n_p
 }  // namespace
 
 int32_t mrts_policy_head_packed_words(const mrts_env* env, int32_t cap) {
-    if (!env) return fail(Fail{-EINVAL, "null handle"});
-    if (env->botOnly || env->forwardModel) return fail(Fail{-ENOTSUP, "the policy head needs a handle that writes masks"});
-    if (cap < 1 || cap > env->HW) return fail(Fail{-EINVAL, "cap: 1 <= cap <= H*W"});
-    return headPackedWords(cap);
+    return guarded(env, [&] {
+        if (env->botOnly || env->forwardModel) throw Fail{-ENOTSUP, "the policy head needs a handle that writes masks"};
+        if (cap < 1 || cap > env->HW) throw Fail{-EINVAL, "cap: 1 <= cap <= H*W"};
+        return headPackedWords(cap);
+    });
 }
 
 int mrts_policy_head_pack_dev(mrts_env* env, int32_t n_rows, const uint8_t* d_masks, const uint32_t* d_source,
                               const int32_t* d_actions, int32_t cap, uint32_t* d_packed, void* stream) {
-    try {
+    return guarded(env, [&] {
         HeadPackedParams P = headPackedParams(env, n_rows, cap);
         if (!d_masks || !d_actions || !d_packed) throw Fail{-EINVAL, "null argument"};
         if (((uintptr_t)d_source & 3) || ((uintptr_t)d_actions & 3) || ((uintptr_t)d_packed & 3)) throw Fail{-EINVAL, "misaligned buffer"};
@@ -1928,14 +1273,12 @@ int mrts_policy_head_pack_dev(mrts_env* env, int32_t n_rows, const uint8_t* d_ma
         P.overflow = env->d_packOverflow;
         HIPCHK(launchHeadPacked(HEAD_PACK, P, pickStream(env, stream)));
         return 0;
-    } catch (const Fail& f) {
-        return fail(f);
-    }
+    });
 }
 
 int mrts_policy_head_pack_status(mrts_env* env, int64_t* overflow_rows) {
-    try {
-        if (!env || !overflow_rows) throw Fail{-EINVAL, "null argument"};
+    return guarded(env, [&] {
+        if (!overflow_rows) throw Fail{-EINVAL, "null argument"};
         *overflow_rows = 0;
         if (!env->d_packOverflow) return 0;
         HIPCHK(hipSetDevice(env->device));
@@ -1945,14 +1288,12 @@ int mrts_policy_head_pack_status(mrts_env* env, int64_t* overflow_rows) {
         if (v) HIPCHK(hipMemset(env->d_packOverflow, 0, 8));
         *overflow_rows = (int64_t)v;
         return 0;
-    } catch (const Fail& f) {
-        return fail(f);
-    }
+    });
 }
 
 int mrts_policy_head_unpack_dev(mrts_env* env, int32_t n_rows, const uint32_t* d_packed, int32_t n_packed, int32_t cap,
                                 const int32_t* d_index, uint8_t* d_masks_out, int32_t* d_actions_out, void* stream) {
-    try {
+    return guarded(env, [&] {
         HeadPackedParams P = headPackedParams(env, n_rows, cap);
         headPackedSource(P, d_packed, n_packed, d_index);
         if (!d_masks_out || !d_actions_out) throw Fail{-EINVAL, "null argument"};
@@ -1962,15 +1303,13 @@ int mrts_policy_head_unpack_dev(mrts_env* env, int32_t n_rows, const uint32_t* d
         P.actions_out = d_actions_out;
         HIPCHK(launchHeadPacked(HEAD_UNPACK, P, pickStream(env, stream)));
         return 0;
-    } catch (const Fail& f) {
-        return fail(f);
-    }
+    });
 }
 
 int mrts_policy_head_score_packed_dev(mrts_env* env, int32_t n_rows, const float* d_logits, const uint32_t* d_packed,
                                       int32_t n_packed, int32_t cap, const int32_t* d_index, float* d_logprob,
                                       float* d_entropy, void* stream) {
-    try {
+    return guarded(env, [&] {
         HeadPackedParams P = headPackedParams(env, n_rows, cap);
         headPackedSource(P, d_packed, n_packed, d_index);
         if (!d_logits) throw Fail{-EINVAL, "null argument"};
@@ -1981,15 +1320,13 @@ int mrts_policy_head_score_packed_dev(mrts_env* env, int32_t n_rows, const float
         P.H.entropy = d_entropy;
         HIPCHK(launchHeadPacked(HEAD_SCORE, P, pickStream(env, stream)));
         return 0;
-    } catch (const Fail& f) {
-        return fail(f);
-    }
+    });
 }
 
 int mrts_policy_head_grad_packed_dev(mrts_env* env, int32_t n_rows, const float* d_logits, const uint32_t* d_packed,
                                      int32_t n_packed, int32_t cap, const int32_t* d_index, const float* d_g_logprob,
                                      const float* d_g_entropy, float* d_grad_logits, void* stream) {
-    try {
+    return guarded(env, [&] {
         HeadPackedParams P = headPackedParams(env, n_rows, cap);
         headPackedSource(P, d_packed, n_packed, d_index);
         if (!d_logits || !d_grad_logits) throw Fail{-EINVAL, "null argument"};
@@ -2002,9 +1339,7 @@ int mrts_policy_head_grad_packed_dev(mrts_env* env, int32_t n_rows, const float*
         P.H.grad = d_grad_logits;
         HIPCHK(launchHeadPacked(HEAD_GRAD, P, pickStream(env, stream)));
         return 0;
-    } catch (const Fail& f) {
-        return fail(f);
-    }
+    });
 }
 
 static void fillResponses(mrts_env* env, mrts_responses* out) {
@@ -2021,41 +1356,41 @@ static void fillResponses(mrts_env* env, mrts_responses* out) {
     }
 }
 
+// the host-pointer calls' players: the caller's, or zeros
+static void stagePlayers(mrts_env* env, const int32_t* players) {
+    const size_t S = (size_t)env->nSlots;
+    if (players) HIPCHK(hipMemcpyAsync(env->d_players, players, S * 4, hipMemcpyHostToDevice, env->stream));
+    else HIPCHK(hipMemsetAsync(env->d_players, 0, S * 4, env->stream));
+}
+
 int mrts_reset(mrts_env* env, const int32_t* players, mrts_responses* out) {
-    try {
+    return guarded(env, [&] {
         HIPCHK(hipSetDevice(env->device));
-        const size_t S = (size_t)env->nSlots;
-        if (players) HIPCHK(hipMemcpyAsync(env->d_players, players, S * 4, hipMemcpyHostToDevice, env->stream));
-        else HIPCHK(hipMemsetAsync(env->d_players, 0, S * 4, env->stream));
+        stagePlayers(env, players);
         int r = mrts_reset_dev(env, env->d_players, env->d_obs, env->d_reward, env->d_done, nullptr, 0, env->stream);
         if (r) return r;
         fillResponses(env, out);
         return 0;
-    } catch (const Fail& f) {
-        return fail(f);
-    }
+    });
 }
 
 int mrts_step(mrts_env* env, const int32_t* actions, const int32_t* players, mrts_responses* out) {
-    try {
+    return guarded(env, [&] {
         if (!actions) throw Fail{-EINVAL, "actions is null"};
         HIPCHK(hipSetDevice(env->device));
         const size_t S = (size_t)env->nSlots;
         HIPCHK(hipMemcpyAsync(env->d_actions, actions, S * env->HW * 7 * 4, hipMemcpyHostToDevice, env->stream));
-        if (players) HIPCHK(hipMemcpyAsync(env->d_players, players, S * 4, hipMemcpyHostToDevice, env->stream));
-        else HIPCHK(hipMemsetAsync(env->d_players, 0, S * 4, env->stream));
+        stagePlayers(env, players);
         int r = mrts_step_dev(env, env->d_actions, env->d_players, env->d_obs, env->d_reward, env->d_done, nullptr, 0, env->stream);
         if (r) return r;
         fillResponses(env, out);
         checkFlagsAfter(env);
         return 0;
-    } catch (const Fail& f) {
-        return fail(f);
-    }
+    });
 }
 
 int mrts_step_rows(mrts_env* env, const int32_t* rows, int32_t n_rows, const int32_t* players, mrts_responses* out) {
-    try {
+    return guarded(env, [&] {
         if (!rows && n_rows > 0) throw Fail{-EINVAL, "rows is null"};
         if (n_rows < 0) throw Fail{-EINVAL, "bad n_rows"};
         HIPCHK(hipSetDevice(env->device));
@@ -2068,21 +1403,18 @@ int mrts_step_rows(mrts_env* env, const int32_t* rows, int32_t n_rows, const int
             env->rowsStageInts = n;
         }
         if (n) HIPCHK(hipMemcpyAsync(env->d_rowsStage, rows, n * 4, hipMemcpyHostToDevice, env->stream));
-        if (players) HIPCHK(hipMemcpyAsync(env->d_players, players, S * 4, hipMemcpyHostToDevice, env->stream));
-        else HIPCHK(hipMemsetAsync(env->d_players, 0, S * 4, env->stream));
+        stagePlayers(env, players);
         int r = mrts_step_rows_dev(env, env->d_rowsStage, n_rows, env->d_players, env->d_obs, env->d_reward, env->d_done,
                                    nullptr, 0, env->stream);
         if (r) return r;
         fillResponses(env, out);
         checkFlagsAfter(env);
         return 0;
-    } catch (const Fail& f) {
-        return fail(f);
-    }
+    });
 }
 
 int mrts_get_masks_i32(mrts_env* env, int32_t player, int32_t* out) {
-    try {
+    return guarded(env, [&] {
         if (!out) throw Fail{-EINVAL, "out is null"};
         const size_t n = (size_t)env->nSlots * env->HW * env->K;
         if (!env->d_masks32) HIPCHK(hipMalloc(&env->d_masks32, n * 4));
@@ -2091,29 +1423,25 @@ int mrts_get_masks_i32(mrts_env* env, int32_t player, int32_t* out) {
         HIPCHK(hipMemcpyAsync(out, env->d_masks32, n * 4, hipMemcpyDeviceToHost, env->stream));
         HIPCHK(hipStreamSynchronize(env->stream));
         return 0;
-    } catch (const Fail& f) {
-        return fail(f);
-    }
+    });
 }
 
 int mrts_get_masks(mrts_env* env, int32_t player, uint8_t* out) {
-    try {
+    return guarded(env, [&] {
         if (!out) throw Fail{-EINVAL, "out is null"};
         int r = mrts_get_masks_dev(env, player, env->d_masks, env->stream);
         if (r) return r;
         HIPCHK(hipMemcpyAsync(out, env->d_masks, (size_t)env->nSlots * env->HW * env->K, hipMemcpyDeviceToHost, env->stream));
         HIPCHK(hipStreamSynchronize(env->stream));
         return 0;
-    } catch (const Fail& f) {
-        return fail(f);
-    }
+    });
 }
 
 // getMasks into a library-owned pinned buffer (valid until the next call on the handle, like the Java
 // client's reused mask array, JNIGridnetClient.java:211-215): the D2H copy runs at pinned-memory rate
 // instead of staging through a pageable caller buffer
 int mrts_get_masks_host(mrts_env* env, int32_t player, const uint8_t** out) {
-    try {
+    return guarded(env, [&] {
         if (!out) throw Fail{-EINVAL, "out is null"};
         const size_t n = (size_t)env->nSlots * env->HW * env->K;
         if (!env->h_masks) HIPCHK(hipHostMalloc(&env->h_masks, n, hipHostMallocDefault));
@@ -2121,13 +1449,11 @@ int mrts_get_masks_host(mrts_env* env, int32_t player, const uint8_t** out) {
         if (r) return r;
         *out = env->h_masks;
         return 0;
-    } catch (const Fail& f) {
-        return fail(f);
-    }
+    });
 }
 
 int mrts_get_masks_i32_host(mrts_env* env, int32_t player, const int32_t** out) {
-    try {
+    return guarded(env, [&] {
         if (!out) throw Fail{-EINVAL, "out is null"};
         const size_t n = (size_t)env->nSlots * env->HW * env->K;
         if (!env->h_masks32) HIPCHK(hipHostMalloc(&env->h_masks32, n * 4, hipHostMallocDefault));
@@ -2135,13 +1461,11 @@ int mrts_get_masks_i32_host(mrts_env* env, int32_t player, const int32_t** out) 
         if (r) return r;
         *out = env->h_masks32;
         return 0;
-    } catch (const Fail& f) {
-        return fail(f);
-    }
+    });
 }
 
 int mrts_get_state(mrts_env* env, int32_t slot, int32_t* buf, int32_t cap) {
-    try {
+    return guarded(env, [&] {
         if (slot < 0 || slot >= env->nSlots) throw Fail{-EINVAL, "slot out of range"};
         int pl;
         const int g = env->gameOfSlot(slot, &pl);
@@ -2149,57 +1473,20 @@ int mrts_get_state(mrts_env* env, int32_t slot, int32_t* buf, int32_t cap) {
         std::vector<int32_t> s(sw);
         HIPCHK(hipStreamSynchronize(env->stream));
         HIPCHK(hipMemcpy(s.data(), env->d_state + (size_t)g * sw, sw * 4, hipMemcpyDeviceToHost));
-        const int CAP = env->CAP;
-        const int32_t* A = s.data() + H_WORDS;
-        const int nu = s[H_NU];
-        std::vector<int32_t> d;
-        d.push_back(s[H_TIME]);
-        d.push_back(2);
-        d.push_back(s[H_RES0]);
-        d.push_back(s[H_RES1]);
-        d.push_back(nu);
-        struct Asg { int seq, unit; };
-        std::vector<Asg> asg;
-        for (int i = 0; i < nu; i++) {
-            const uint32_t c = (uint32_t)A[A_UC * CAP + i];
-            d.push_back((int32_t)((c >> 16) & 0xF));
-            d.push_back((int32_t)((c >> 20) & 3) - 1);
-            d.push_back((int32_t)(c & 0xFF));
-            d.push_back((int32_t)((c >> 8) & 0xFF));
-            d.push_back(A[A_HP * CAP + i]);
-            d.push_back(A[A_RES * CAP + i]);
-            if ((uint32_t)A[A_UA * CAP + i] & UA_PRESENT) asg.push_back({A[A_AS * CAP + i], i});
-        }
-        std::sort(asg.begin(), asg.end(), [](const Asg& a, const Asg& b) { return a.seq < b.seq; });
-        d.push_back((int32_t)asg.size());
-        for (auto& e : asg) {
-            const uint32_t a = (uint32_t)A[A_UA * CAP + e.unit];
-            const int t = (int)(a & 0xF);
-            d.push_back(e.unit);
-            d.push_back(t);
-            d.push_back(t == 5 ? -1 : A[A_PAR * CAP + e.unit]);
-            d.push_back(t == 5 ? (int32_t)((a >> 8) & 0xFF) : 0);
-            d.push_back(t == 5 ? (int32_t)((a >> 16) & 0xFF) : 0);
-            d.push_back(t == 4 ? (int32_t)((a >> 4) & 0xF) : -1);
-            d.push_back(A[A_AT * CAP + e.unit]);
-        }
+        const std::vector<int32_t> d = canonicalDump(s.data(), env->CAP);
         if ((int)d.size() > cap) return -(int)d.size();
         std::memcpy(buf, d.data(), d.size() * 4);
         return (int)d.size();
-    } catch (const Fail& f) {
-        return fail(f);
-    }
+    });
 }
 
 int mrts_utt_json(int32_t utt_version, int32_t conflict_policy, const char* utt_json, char* buf, int32_t cap) {
-    try {
+    return guardedCall([&] {
         const std::string j = uttToJson(utt_json ? uttFromJson(utt_json) : makeUtt(utt_version, conflict_policy));
         if (!buf || cap < (int32_t)j.size() + 1) return -((int)j.size() + 1);
         std::memcpy(buf, j.c_str(), j.size() + 1);
         return (int)j.size();
-    } catch (const Fail& f) {
-        return fail(f);
-    }
+    });
 }
 
 static int readHeaderWord(mrts_env* env, int word, int32_t* out_per_slot) {
@@ -2215,19 +1502,11 @@ static int readHeaderWord(mrts_env* env, int word, int32_t* out_per_slot) {
 }
 
 int mrts_error_flags(mrts_env* env, uint32_t* flags) {
-    try {
-        return readHeaderWord(env, H_ERR, (int32_t*)flags);
-    } catch (const Fail& f) {
-        return fail(f);
-    }
+    return guarded(env, [&] { return readHeaderWord(env, H_ERR, (int32_t*)flags); });
 }
 
 int mrts_env_steps(mrts_env* env, int32_t* out) {
-    try {
-        return readHeaderWord(env, H_STEPS, out);
-    } catch (const Fail& f) {
-        return fail(f);
-    }
+    return guarded(env, [&] { return readHeaderWord(env, H_STEPS, out); });
 }
 
 void mrts_destroy(mrts_env* env) {
@@ -2283,264 +1562,71 @@ static void readBlock(mrts_env* env, int g, std::vector<int32_t>& s) {
     HIPCHK(hipMemcpy(s.data(), env->d_state + (size_t)g * sw, sw * 4, hipMemcpyDeviceToHost));
 }
 
-// GameState.toJSON(w, true, false) (rts/GameState.java:819-837) with PhysicalGameState.toJSON
-// (:658-691), Player.toJSON (Player.java:86-88), Unit.toJSON (Unit.java:577-588) and
-// UnitAction.toJSON (UnitAction.java:569-582).  Unit IDs are list positions: Java's IDs come from a
-// JVM-global counter and are not part of a game's reproducible state.
-static std::string gameToJson(const mrts_env* env, const std::vector<int32_t>& s) {
-    const int CAP = env->CAP, HW = env->HW;
-    const int32_t* A = s.data() + H_WORDS;
-    const uint8_t* terr = (const uint8_t*)(s.data() + stateTerrOff(CAP, HW));
-    const int nu = s[H_NU];
-    std::ostringstream w;
-    w << "{\"time\":" << s[H_TIME] << ",\"pgs\":{\"width\":" << env->W << ",\"height\":" << env->H << ",\"terrain\":\"";
-    for (int i = 0; i < HW; i++) w << (int)terr[i];
-    w << "\",\"players\":[{\"ID\":0, \"resources\":" << s[H_RES0] << "},{\"ID\":1, \"resources\":" << s[H_RES1]
-      << "}],\"units\":[";
-    struct Asg { int seq, unit; };
-    std::vector<Asg> asg;
-    for (int i = 0; i < nu; i++) {
-        const uint32_t c = (uint32_t)A[A_UC * CAP + i];
-        if (i) w << ",";
-        w << "{\"type\":\"" << env->uttInfo.names[(c >> 16) & 0xF] << "\", \"ID\":" << i << ", \"player\":"
-          << (int)((c >> 20) & 3) - 1 << ", \"x\":" << (c & 0xFF) << ", \"y\":" << ((c >> 8) & 0xFF)
-          << ", \"resources\":" << A[A_RES * CAP + i] << ", \"hitpoints\":" << A[A_HP * CAP + i] << "}";
-        if ((uint32_t)A[A_UA * CAP + i] & UA_PRESENT) asg.push_back({A[A_AS * CAP + i], i});
-    }
-    w << "]},\"actions\":[";
-    std::sort(asg.begin(), asg.end(), [](const Asg& a, const Asg& b) { return a.seq < b.seq; });
-    for (size_t k = 0; k < asg.size(); k++) {
-        const int i = asg[k].unit;
-        const uint32_t a = (uint32_t)A[A_UA * CAP + i];
-        const int t = (int)(a & 0xF), prm = (int16_t)A[A_PAR * CAP + i];
-        if (k) w << ",";
-        w << "{\"ID\":" << i << ", \"time\":" << A[A_AT * CAP + i] << ", \"action\":{\"type\":" << t;
-        if (t == 5) {
-            w << ", \"x\":" << ((a >> 8) & 0xFF) << ",\"y\":" << ((a >> 16) & 0xFF);
-        } else {
-            if (prm != -1) w << ", \"parameter\":" << prm;
-            if (t == 4) w << ", \"unitType\":\"" << env->uttInfo.names[(a >> 4) & 0xF] << "\"";
-        }
-        w << "}}";
-    }
-    w << "]}";
-    return w.str();
-}
-
-// GameState.fromJSON (rts/GameState.java:897-915): PhysicalGameState.fromJSON (:735-756, terrain raw
-// or A/B), Player.fromJSON, Unit.fromJSON (Unit.java:629-642: hitpoints default 1), the actions by
-// unit ID in array order (UnitAction.fromJSON, UnitAction.java:647-658).  A new GameState: time from
-// the JSON, unitCancelationCounter 0.  Writes the words of block `s` it describes; everything else
-// (random streams, kind, mask row sets) is kept.  Rejects what Java would throw on (unknown type or
-// ID, two units in a cell) and what this build cannot hold.
-static void jsonToBlock(const mrts_env* env, const std::string& text, std::vector<int32_t>& s) {
-    mjson::Value o;
-    try {
-        o = mjson::parse(text);
-    } catch (const std::exception& e) {
-        throw Fail{-EINVAL, std::string("state json: ") + e.what()};
-    }
-    try {
-        const int CAP = env->CAP, HW = env->HW, W = env->W, H = env->H;
-        const mjson::Value& pg = o.at("pgs");
-        if (pg.getInt("width", 8) != W || pg.getInt("height", 8) != H) throw Fail{-EINVAL, "state json: map size differs from the handle's"};
-        const std::vector<int> terr = decodeTerrain(pg.getString("terrain", ""), HW);
-        const mjson::Value& pl = pg.at("players");
-        if (pl.arr.size() != 2 || pl.arr[0].getInt("ID", -1) != 0 || pl.arr[1].getInt("ID", -1) != 1)
-            throw Fail{-ENOTSUP, "state json: players must be 0 and 1"};
-        const mjson::Value& us = pg.at("units");
-        const int nu = (int)us.arr.size();
-        if (nu > env->maxUnits) throw Fail{-ENOSPC, "state json: more units than the handle's max_units"};
-        int32_t* A = s.data() + H_WORDS;
-        std::vector<int64_t> ids((size_t)nu);
-        std::vector<char> occ((size_t)HW, 0);
-        for (int a = 0; a < N_ARRAYS; a++)
-            for (int i = 0; i < CAP; i++) A[a * CAP + i] = 0;
-        for (int i = 0; i < nu; i++) {
-            const mjson::Value& u = us.arr[(size_t)i];
-            const int type = env->uttInfo.typeOf(u.getString("type", ""));
-            const int p = u.getInt("player", -1), x = u.getInt("x", 0), y = u.getInt("y", 0);
-            const int r = u.getInt("resources", 0), hp = u.getInt("hitpoints", 1);
-            ids[(size_t)i] = u.getLong("ID", -1);
-            if (type < 0) throw Fail{-EINVAL, "state json: unknown unit type"};
-            if (p < -1 || p > 1 || x < 0 || y < 0 || x >= W || y >= H) throw Fail{-EINVAL, "state json: unit out of range"};
-            if (r < -32768 || r > 32767 || hp < -32768 || hp > 32767) throw Fail{-EINVAL, "state json: value exceeds int16"};
-            if (occ[(size_t)(y * W + x)]) throw Fail{-EINVAL, "state json: two units in one position (addUnit)"};
-            for (int j = 0; j < i; j++)
-                if (ids[(size_t)j] == ids[(size_t)i]) throw Fail{-EINVAL, "state json: repeated unit ID"};
-            occ[(size_t)(y * W + x)] = 1;
-            A[A_UC * CAP + i] = (int32_t)((uint32_t)x | ((uint32_t)y << 8) | ((uint32_t)type << 16) | ((uint32_t)(p + 1) << 20));
-            A[A_HP * CAP + i] = hp;
-            A[A_RES * CAP + i] = r;
-            A[A_PAR * CAP + i] = -1;
-        }
-        const mjson::Value& acts = o.at("actions");
-        int seq = 0;
-        for (auto& av : acts.arr) {
-            const int64_t id = av.getLong("ID", -1);
-            int i = 0;
-            while (i < nu && ids[(size_t)i] != id) i++;
-            if (i == nu) throw Fail{-EINVAL, "state json: action for an unknown unit ID"};
-            const uint32_t c = (uint32_t)A[A_UC * CAP + i];
-            if ((int)((c >> 20) & 3) - 1 < 0) throw Fail{-EINVAL, "state json: action for a neutral unit"};
-            const mjson::Value& ua = av.at("action");
-            const int t = ua.getInt("type", 0), prm = ua.getInt("parameter", -1);
-            const int tx = ua.getInt("x", -1), ty = ua.getInt("y", -1);
-            const std::string utn = ua.getString("unitType", "");
-            int ut = 0;
-            if (t < 0 || t > 5) throw Fail{-EINVAL, "state json: bad action type"};
-            if (t == 5 && (tx < 0 || ty < 0 || tx >= W || ty >= H)) throw Fail{-ENOTSUP, "state json: attack target off the map"};
-            if (t >= 1 && t <= 4 && (prm < 0 || prm > 3)) throw Fail{-ENOTSUP, "state json: bad direction"};
-            if (t == 0 && (prm < -1 || prm > 32767)) throw Fail{-ENOTSUP, "state json: bad NONE duration"};
-            if (t == 4) {
-                ut = env->uttInfo.typeOf(utn);
-                if (ut < 0) throw Fail{-EINVAL, "state json: unknown produced type"};
-            }
-            const bool again = (uint32_t)A[A_UA * CAP + i] & UA_PRESENT;  // put() on a present key keeps its place
-            A[A_UA * CAP + i] = (int32_t)((uint32_t)t | ((uint32_t)ut << 4) |
-                                          (t == 5 ? ((uint32_t)tx << 8) | ((uint32_t)ty << 16) : 0u) | UA_PRESENT);
-            A[A_PAR * CAP + i] = t == 5 ? -1 : prm;
-            A[A_AT * CAP + i] = av.getInt("time", 0);
-            if (!again) A[A_AS * CAP + i] = seq++;
-        }
-        const mjson::Value& p0 = pl.arr[0];
-        const mjson::Value& p1 = pl.arr[1];
-        s[H_TIME] = o.getInt("time", 0);
-        s[H_NU] = nu;
-        s[H_RES0] = p0.getInt("resources", 0);
-        s[H_RES1] = p1.getInt("resources", 0);
-        s[H_SEQ] = seq;
-        s[H_STEPS] = 0;
-        s[H_ERR] = 0;
-        s[H_CANCEL_CNT] = 0;
-        uint8_t* tb = (uint8_t*)(s.data() + stateTerrOff(CAP, HW));
-        for (int i = 0; i < HW; i++) tb[i] = terr[(size_t)i] != 0;
-        for (int i = HW; i < 4 * ((HW + 3) / 4); i++) tb[i] = 0;
-        for (int i = 0; i < nu; i++) {  // units may not stand on walls (the cell map has one owner per cell)
-            const uint32_t c = (uint32_t)A[A_UC * CAP + i];
-            if (tb[(c & 0xFF) + ((c >> 8) & 0xFF) * W]) throw Fail{-ENOTSUP, "state json: unit on a wall"};
-        }
-    } catch (const std::runtime_error& e) {
-        throw Fail{-EINVAL, std::string("state json: ") + e.what()};
-    }
-}
-
 int mrts_get_state_json(mrts_env* env, int32_t slot, char* buf, int32_t cap) {
-    try {
-        if (!env || slot < 0 || slot >= env->nSlots) throw Fail{-EINVAL, "slot out of range"};
+    return guarded(env, [&] {
+        if (slot < 0 || slot >= env->nSlots) throw Fail{-EINVAL, "slot out of range"};
         int pl;
         std::vector<int32_t> s;
         readBlock(env, env->gameOfSlot(slot, &pl), s);
-        const std::string j = gameToJson(env, s);
+        const std::string j = gameToJson(*env, s);
         if (!buf || cap < (int32_t)j.size() + 1) return -((int)j.size() + 1);
         std::memcpy(buf, j.c_str(), j.size() + 1);
         return (int)j.size();
-    } catch (const Fail& f) {
-        return fail(f);
-    }
+    });
 }
 
 int mrts_set_state_json(mrts_env* env, int32_t slot, const char* json) {
-    try {
-        if (!env || !json || slot < 0 || slot >= env->nSlots) throw Fail{-EINVAL, "bad argument"};
+    return guarded(env, [&] {
+        if (!json || slot < 0 || slot >= env->nSlots) throw Fail{-EINVAL, "bad argument"};
         int pl;
         const int g = env->gameOfSlot(slot, &pl);
         std::vector<int32_t> s;
         readBlock(env, g, s);
-        jsonToBlock(env, json, s);
+        jsonToBlock(*env, json, s);
         // an injected state starts with fresh AIs: the LightRush memory of this game is cleared
         std::fill(s.begin() + stateWords(env->CAP, env->HW), s.end(), 0);
         env->noteValues(s.data());
         const size_t sw = s.size();
         HIPCHK(hipMemcpy(env->d_state + (size_t)g * sw, s.data(), sw * 4, hipMemcpyHostToDevice));
-        env->lastMaskPtr = nullptr;  // the next mask and observation writes are full ones
-        env->lastObsPtr = nullptr;
-        env->polValid = false;
-        env->fusedActions = nullptr;
+        env->invalidateWrites();
         return 0;
-    } catch (const Fail& f) {
-        return fail(f);
-    }
+    });
 }
 
 // whole-handle checkpoint: a header + every game's state block (random streams, envSteps, kind included)
-namespace {
-struct CkptHeader {
-    char magic[8];
-    int32_t version, H, W, CAP, nGames, nSpGames, words;
-    uint32_t uttHash;
-    uint32_t cfgHash;  // mrts_env::cfgHash: game kinds (opponents), map templates, max_steps, reward kinds, PO
-    int32_t pad_;
-};
-uint32_t uttHash(const DevUtt& u) {
-    uint32_t h = 2166136261u;
-    const uint8_t* p = (const uint8_t*)&u;
-    for (size_t i = 0; i < sizeof(DevUtt); i++) h = (h ^ p[i]) * 16777619u;
-    return h;
-}
-}  // namespace
-
 int64_t mrts_checkpoint_size(const mrts_env* env) {
     if (!env) return -EINVAL;
-    return (int64_t)sizeof(CkptHeader) + (int64_t)env->blockWords() * env->nGames * 4;
+    return ckptSize(*env);
 }
 
 int mrts_checkpoint(mrts_env* env, void* buf, int64_t cap) {
-    try {
-        if (!env || !buf) throw Fail{-EINVAL, "null argument"};
-        if (cap < mrts_checkpoint_size(env)) throw Fail{-ENOSPC, "buffer too small"};
-        CkptHeader h;
-        std::memset(&h, 0, sizeof(h));
-        std::memcpy(h.magic, "MRTSCKP1", 8);
-        h.version = 3;
-        h.H = env->H;
-        h.W = env->W;
-        h.CAP = env->CAP;
-        h.nGames = env->nGames;
-        h.nSpGames = env->nSpGames;
-        h.words = (int32_t)env->blockWords();
-        h.uttHash = uttHash(env->utt);
-        h.cfgHash = env->cfgHash;
+    return guarded(env, [&] {
+        if (!buf) throw Fail{-EINVAL, "null argument"};
+        if (cap < ckptSize(*env)) throw Fail{-ENOSPC, "buffer too small"};
+        const CkptHeader h = ckptHeader(*env);
         std::memcpy(buf, &h, sizeof(h));
         HIPCHK(hipDeviceSynchronize());
         HIPCHK(hipMemcpy((char*)buf + sizeof(h), env->d_state, (size_t)h.words * h.nGames * 4, hipMemcpyDeviceToHost));
         return 0;
-    } catch (const Fail& f) {
-        return fail(f);
-    }
+    });
 }
 
 int mrts_restore(mrts_env* env, const void* buf, int64_t size) {
-    try {
-        if (!env || !buf) throw Fail{-EINVAL, "null argument"};
-        CkptHeader h;
-        if (size < (int64_t)sizeof(h)) throw Fail{-EINVAL, "checkpoint too short"};
-        std::memcpy(&h, buf, sizeof(h));
-        if (std::memcmp(h.magic, "MRTSCKP1", 8) != 0 || h.version != 3) throw Fail{-EINVAL, "not a checkpoint"};
-        if (h.H != env->H || h.W != env->W || h.CAP != env->CAP || h.nGames != env->nGames || h.nSpGames != env->nSpGames ||
-            h.words != (int32_t)env->blockWords() || h.uttHash != uttHash(env->utt))
-            throw Fail{-EINVAL, "checkpoint of a different configuration"};
-        if (h.cfgHash != env->cfgHash)
-            throw Fail{-EINVAL, "checkpoint of a different configuration (opponents, maps, max_steps, reward functions "
-                                "or partial observability differ)"};
-        if (size != mrts_checkpoint_size(env)) throw Fail{-EINVAL, "checkpoint size mismatch"};
-        for (int g = 0; g < h.nGames; g++)
-            env->noteValues((const int32_t*)((const char*)buf + sizeof(h)) + (size_t)g * h.words);
+    return guarded(env, [&] {
+        if (!buf) throw Fail{-EINVAL, "null argument"};
+        checkCkpt(*env, buf, size);
+        const char* blocks = (const char*)buf + sizeof(CkptHeader);
+        const size_t words = env->blockWords();
+        for (int g = 0; g < env->nGames; g++) env->noteValues((const int32_t*)blocks + (size_t)g * words);
         HIPCHK(hipDeviceSynchronize());
-        HIPCHK(hipMemcpy(env->d_state, (const char*)buf + sizeof(h), (size_t)h.words * h.nGames * 4, hipMemcpyHostToDevice));
-        env->lastMaskPtr = nullptr;
-        env->lastObsPtr = nullptr;
-        env->polValid = false;
-        env->fusedActions = nullptr;
+        HIPCHK(hipMemcpy(env->d_state, blocks, words * env->nGames * 4, hipMemcpyHostToDevice));
+        env->invalidateWrites();
         return 0;
-    } catch (const Fail& f) {
-        return fail(f);
-    }
+    });
 }
 
 // ---------------------------------------------------------------- forward model
 static void checkCopy(const mrts_env* dst, const mrts_env* src) {
-    if (!dst || !src) throw Fail{-EINVAL, "null handle"};
     if (!dst->forwardModel) throw Fail{-EINVAL, "copy destination must be a forward-model handle"};
     // launchCopyGames writes destination blocks of stateWords: a forward model never has LightRush memory (mrts_create)
     if (dst->hasLightRush) throw Fail{-ENOTSUP, "copy destination carries LightRush memory"};
@@ -2550,7 +1636,7 @@ static void checkCopy(const mrts_env* dst, const mrts_env* src) {
 }
 
 int mrts_copy_games_dev(mrts_env* dst, const mrts_env* src, const int32_t* d_pairs, int32_t n, void* stream) {
-    try {
+    return guarded(dst, [&] {
         if (!src) src = dst;
         checkCopy(dst, src);
         if (n < 0 || (n > 0 && !d_pairs)) throw Fail{-EINVAL, "bad pairs"};
@@ -2559,13 +1645,11 @@ int mrts_copy_games_dev(mrts_env* dst, const mrts_env* src, const int32_t* d_pai
                                (int)src->blockWords(), pickStream(dst, stream)));
         dst->lastObsPtr = nullptr;
         return 0;
-    } catch (const Fail& f) {
-        return fail(f);
-    }
+    });
 }
 
 int mrts_copy_games(mrts_env* dst, const mrts_env* src, const int32_t* pairs, int32_t n) {
-    try {
+    return guarded(dst, [&] {
         if (!src) src = dst;
         checkCopy(dst, src);
         if (n < 0 || (n > 0 && !pairs)) throw Fail{-EINVAL, "bad pairs"};
@@ -2596,43 +1680,36 @@ int mrts_copy_games(mrts_env* dst, const mrts_env* src, const int32_t* pairs, in
         dst->lastObsPtr = nullptr;
         HIPCHK(hipStreamSynchronize(dst->stream));
         return 0;
-    } catch (const Fail& f) {
-        return fail(f);
-    }
+    });
 }
 
 int mrts_playout_dev(mrts_env* env, int32_t horizon, void* stream) {
-    try {
-        if (!env || !env->forwardModel) throw Fail{-EINVAL, "not a forward-model handle"};
+    return guarded(env, [&] {
+        if (!env->forwardModel) throw Fail{-EINVAL, "not a forward-model handle"};
         if (horizon < -MRTS_MAX_HORIZON || horizon > MRTS_MAX_HORIZON) throw Fail{-EINVAL, "horizon out of range"};
         HIPCHK(hipSetDevice(env->device));
-        KDyn D;
-        std::memset(&D, 0, sizeof(D));
+        KDyn D = mrts_env::noArgs();
         D.horizon = horizon;
-        HIPCHK(env->launch(3, D, pickStream(env, stream)));
+        HIPCHK(env->launch(MODE_PLAYOUT, D, pickStream(env, stream)));
         env->lastObsPtr = nullptr;
         return 0;
-    } catch (const Fail& f) {
-        return fail(f);
-    }
+    });
 }
 
 int mrts_playout(mrts_env* env, int32_t horizon) {
-    try {
-        int r = mrts_playout_dev(env, horizon, env ? env->stream : nullptr);
+    return guarded(env, [&] {
+        int r = mrts_playout_dev(env, horizon, env->stream);
         if (r) return r;
         HIPCHK(hipStreamSynchronize(env->stream));
         checkFlagsAfter(env);
         return 0;
-    } catch (const Fail& f) {
-        return fail(f);
-    }
+    });
 }
 
 int mrts_trace_step(mrts_env* env, const int32_t* pairs, int32_t n_pairs, const int32_t* until, int32_t* out,
                     int32_t generic) {
-    try {
-        if (!env || !env->forwardModel) throw Fail{-EINVAL, "not a forward-model handle"};
+    return guarded(env, [&] {
+        if (!env->forwardModel) throw Fail{-EINVAL, "not a forward-model handle"};
         if (!until || (n_pairs > 0 && !pairs)) throw Fail{-EINVAL, "null argument"};
         if (n_pairs < 0 || (size_t)n_pairs * env->nGames * 8 >= ((size_t)1 << 31)) throw Fail{-EINVAL, "bad n_pairs"};
         const size_t nr = (size_t)env->nGames * n_pairs;
@@ -2657,14 +1734,13 @@ int mrts_trace_step(mrts_env* env, const int32_t* pairs, int32_t n_pairs, const 
         int32_t* d_until = env->d_rowsStage + nr * 8;
         if (nr) HIPCHK(hipMemcpyAsync(env->d_rowsStage, pairs, nr * 8 * 4, hipMemcpyHostToDevice, env->stream));
         HIPCHK(hipMemcpyAsync(d_until, until, (size_t)env->nGames * 4, hipMemcpyHostToDevice, env->stream));
-        KDyn D;
-        std::memset(&D, 0, sizeof(D));
+        KDyn D = mrts_env::noArgs();
         D.rows = env->d_rowsStage;
         D.n_rows = n_pairs;
         D.trace_until = d_until;
         D.trace_out = d_until + env->nGames;
         D.trace_generic = generic ? 1 : 0;
-        HIPCHK(env->launch(4, D, env->stream));
+        HIPCHK(env->launch(MODE_TRACE, D, env->stream));
         env->lastObsPtr = nullptr;
         env->fusedActions = nullptr;
         std::vector<int32_t> o((size_t)env->nGames);
@@ -2673,35 +1749,29 @@ int mrts_trace_step(mrts_env* env, const int32_t* pairs, int32_t n_pairs, const 
         if (out) std::memcpy(out, o.data(), o.size() * 4);
         checkFlagsAfter(env);
         return 0;
-    } catch (const Fail& f) {
-        return fail(f);
-    }
+    });
 }
 
 int mrts_evaluate_dev(mrts_env* env, int32_t maxplayer, float* d_out, void* stream) {
-    try {
-        if (!env || !d_out) throw Fail{-EINVAL, "null argument"};
+    return guarded(env, [&] {
+        if (!d_out) throw Fail{-EINVAL, "null argument"};
         if (maxplayer != 0 && maxplayer != 1) throw Fail{-EINVAL, "maxplayer must be 0 or 1"};
         HIPCHK(hipSetDevice(env->device));
         HIPCHK(launchEvaluate(env->hstatic, env->d_static, maxplayer, d_out, pickStream(env, stream)));
         return 0;
-    } catch (const Fail& f) {
-        return fail(f);
-    }
+    });
 }
 
 int mrts_evaluate(mrts_env* env, int32_t maxplayer, float* out) {
-    try {
-        if (!env || !out) throw Fail{-EINVAL, "null argument"};
+    return guarded(env, [&] {
+        if (!out) throw Fail{-EINVAL, "null argument"};
         if (!env->d_eval) HIPCHK(hipMalloc(&env->d_eval, (size_t)env->nGames * 4));
         int r = mrts_evaluate_dev(env, maxplayer, env->d_eval, env->stream);
         if (r) return r;
         HIPCHK(hipMemcpyAsync(out, env->d_eval, (size_t)env->nGames * 4, hipMemcpyDeviceToHost, env->stream));
         HIPCHK(hipStreamSynchronize(env->stream));
         return 0;
-    } catch (const Fail& f) {
-        return fail(f);
-    }
+    });
 }
 
 #ifdef MRTS_LANE_AUDIT

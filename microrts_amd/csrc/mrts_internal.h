@@ -131,6 +131,9 @@ struct KStatic {
     uint32_t bot_types;
 };
 enum : uint32_t { RN_COUNTS = 1, RN_CLOSER = 2, RN_RESOURCES = 4 };
+// what a k_env launch does (launchEnv's mode): one or more steps, a reset of every game, a mask write alone,
+// forward-model playouts, a trace replay
+enum { MODE_STEP = 0, MODE_RESET = 1, MODE_MASKS = 2, MODE_PLAYOUT = 3, MODE_TRACE = 4 };
 // Per-call buffers (kernel arguments by value)
 struct KDyn {
     const int32_t* actions;        // [n_slots][HW][7]

@@ -26,7 +26,7 @@ namespace {
 
 constexpr uint16_t EMPTY = 0xFFFF, WALL = 0xFFFE;
 enum { T_NONE = 0, T_MOVE = 1, T_HARVEST = 2, T_RETURN = 3, T_PRODUCE = 4, T_ATTACK = 5 };
-enum { MODE_STEP = 0, MODE_RESET = 1, MODE_MASKS = 2, MODE_PLAYOUT = 3, MODE_TRACE = 4 };
+// (k_env's MODE_STEP .. MODE_TRACE: mrts_internal.h, shared with the host)
 
 // Diagnostic build only (-DMRTS_PHASE_TIMING, tools/phase_timing.py): per-phase shader-clock cycles
 // summed over games; not compiled into libmrts.so.

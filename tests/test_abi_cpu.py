@@ -29,6 +29,21 @@ def test_library_loads_and_exports_every_symbol():
         assert ctypes.cast(getattr(L, name), ctypes.c_void_p).value
 
 
+@pytest.mark.parametrize("call", [
+    lambda L: L.mrts_step_dev(None, None, None, None, None, None, None, 0, None),
+    lambda L: L.mrts_get_state(None, 0, None, 0),
+    lambda L: L.mrts_reset(None, None, None),
+], ids=["mrts_step_dev", "mrts_get_state", "mrts_reset"])
+def test_null_handle_is_an_error_code(call):
+    """Every entry point that returns an error code answers a null handle with -EINVAL and "null handle", before it
+    touches the handle or the device (no GPU is needed to be refused)."""
+    L = _lib.load()
+    L.mrts_create(None, None)  # (another refusal first: the text below is this call's, not a leftover)
+    assert L.mrts_last_error().decode() == "null argument"
+    assert call(L) == -22
+    assert L.mrts_last_error().decode() == "null handle"
+
+
 def test_config_struct_layout():
     # mrts_config: 6 int32, pointer, pointer, int32, uint64, int32 (natural alignment)
     assert ctypes.sizeof(_lib.MrtsConfig) == 104

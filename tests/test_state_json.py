@@ -11,15 +11,10 @@ import numpy as np
 import pytest
 
 from tests import oracle_py
+from tests.state_json_invalid import BASE4X4_JSON, invalid_states
 
 M4 = "maps/4x4/base4x4.xml"
 M8 = "maps/8x8/basesWorkers8x8.xml"
-
-BASE4X4_JSON = ('{"time":0,"pgs":{"width":4,"height":4,"terrain":"0000000000000000","players":[{"ID":0, "resources":5},'
-                '{"ID":1, "resources":5}],"units":[{"type":"Resource", "ID":4, "player":-1, "x":0, "y":0, "resources":10, '
-                '"hitpoints":1},{"type":"Base", "ID":5, "player":0, "x":1, "y":1, "resources":0, "hitpoints":10},'
-                '{"type":"Base", "ID":6, "player":1, "x":3, "y":3, "resources":0, "hitpoints":10},{"type":"Worker", '
-                '"ID":7, "player":0, "x":1, "y":0, "resources":0, "hitpoints":1}]},"actions":[]}')
 
 
 def normalise(text):
@@ -133,28 +128,16 @@ def test_gpu_set_state_json_rejects_invalid():
     from microrts_amd import DeviceVecEnv
 
     env = DeviceVecEnv(2, 0, 2000, [M4] * 2)
-    good = json.loads(BASE4X4_JSON)
-    bad = []
-    b = json.loads(BASE4X4_JSON)
-    b["pgs"]["width"] = 5
-    bad.append(b)  # size differs
-    b = json.loads(BASE4X4_JSON)
-    b["pgs"]["units"][1]["x"] = 0
-    b["pgs"]["units"][1]["y"] = 0
-    bad.append(b)  # two units in a cell
-    b = json.loads(BASE4X4_JSON)
-    b["actions"] = [{"ID": 99, "time": 0, "action": {"type": 0, "parameter": 10}}]
-    bad.append(b)  # unknown ID
-    b = json.loads(BASE4X4_JSON)
-    b["pgs"]["units"][0]["type"] = "Dragon"
-    bad.append(b)
-    for x in bad:
-        with pytest.raises(RuntimeError):
-            env.set_state_json(0, json.dumps(x))
-    env.set_state_json(0, json.dumps(good))
+    bad = invalid_states()  # (shared with the CPU test of the same converter, tests/test_state_json_cpu.py)
+    assert [what for what, _, _ in bad] == ["size differs", "two units in a cell", "unknown ID", "unknown unit type", "no JSON"]
+    for what, text, code in bad[:4]:
+        with pytest.raises(RuntimeError, match=f"mrts error {code}:"):
+            env.set_state_json(0, text)
+    env.set_state_json(0, BASE4X4_JSON)
     assert json.loads(env.state_json(0))["pgs"]["units"][3]["type"] == "Worker"
-    with pytest.raises(RuntimeError):
-        env.set_state_json(0, "{broken")
+    for what, text, code in bad[4:]:
+        with pytest.raises(RuntimeError, match=f"mrts error {code}:"):
+            env.set_state_json(0, text)
     env.close()
 
 
