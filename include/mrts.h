@@ -438,6 +438,46 @@ int mrts_set_source_output(mrts_env* env, uint32_t* d_source);
  * d_out 16-byte aligned. */
 int mrts_onehot_features(const mrts_env* env);
 int mrts_onehot_dev(mrts_env* env, const int32_t* d_obs, uint8_t* d_out, void* stream);
+/* Packed observation rows: what a rollout keeps of an observation tensor int32 [C][H][W] (C = 6, or 8 when
+ * partially observable) for the update.  Planes 0-4 (hp, resources, owner, type, action) are zero except where a
+ * unit stands; planes 5..C-1 (terrain, the visibility planes) hold 0 / 1.  A packed row is
+ * 1 + 2 * cap + (C - 5) * ceil(H*W / 32) uint32 words (mrts_obs_packed_words), 1 <= cap <= H*W (cap = H*W can
+ * never cut a row):
+ *   word 0: bits 0-30 n, the true number of occupied cells (cells where any of planes 0-4 is non-zero); bit 31 the
+ *           lossy flag, set when n > cap, when a kept value was clamped, or when a value of planes 5.. is neither
+ *           0 nor 1;
+ *   then the first min(n, cap) occupied cells in ascending cell order, two words each:
+ *     word A: cell | owner << 16 | action << 18 | type << 21 (16, 2, 3 and 5 bits; bits 26-31 zero);
+ *     word B: (hp & 0xFFFF) | resources << 16 (hp an int16, resources a uint16);
+ *     a value outside its field is stored clamped to the field's range and sets the lossy flag — every field is
+ *     wider than its one-hot size, so the one-hot encoding of a clamped row stays exact;
+ *   words after the last kept cell are zero;
+ *   then one bitmap per plane 5..C-1, in plane order, ceil(H*W / 32) words each: bit c % 32 of word c / 32 set
+ *   <=> the plane's value at cell c is non-zero; unused high bits zero.
+ * A row is self-contained (terrain travels as a bitmap) and packing is a pure function of the tensor: rows of any
+ * handles of the same shape can be mixed and gathered.
+ * mrts_obs_pack_dev: packs d_obs [n_rows][C][H][W], any n_rows, into d_out [n_rows][words], every word written.
+ * mrts_obs_unpack_dev: writes every element of d_obs int32 [n_rows][C][H][W]; for a row without the lossy flag the
+ * tensor that was packed, byte for byte, for a lossy row its kept, clamped content.
+ * mrts_obs_onehot_packed_dev: writes every byte of d_out uint8 [n_rows][H][W][F] (F = mrts_onehot_features, d_out
+ * 16-byte aligned): for every row with n <= cap, clamped values included, the bytes mrts_onehot_dev gives on the
+ * tensor the row was packed from.
+ * d_packed holds n_packed rows.  Row r of a reading call reads packed row d_index[r] (int32 [n_rows], repeats
+ * allowed), or packed row r when d_index is NULL (then n_packed >= n_rows).  The readers neither read nor write out
+ * of bounds whatever the buffer holds: an index outside [0, n_packed) gives an all-zero output row and one bad read;
+ * a stored count above cap reads cap cells (a cut row); a stored cell >= H*W is skipped and is one bad read.
+ * mrts_obs_packed_status: *lossy_rows = the rows the pack calls flagged lossy, *bad_reads = the bad reads of the
+ * reading calls, both since the last status call; clears them.  Synchronises (as mrts_render_status).  The counters'
+ * device memory is allocated by the first of these calls, which therefore must not run inside a capture.
+ * -EINVAL: a null handle or pointer, n_rows < 0, cap outside 1..H*W, n_packed < 1, a misaligned buffer; -ENOTSUP: a
+ * map of more than 65536 cells. */
+int32_t mrts_obs_packed_words(const mrts_env* env, int32_t cap);
+int mrts_obs_pack_dev(mrts_env* env, int32_t n_rows, const int32_t* d_obs, int32_t cap, uint32_t* d_out, void* stream);
+int mrts_obs_unpack_dev(mrts_env* env, int32_t n_rows, const uint32_t* d_packed, int32_t n_packed, int32_t cap,
+                        const int32_t* d_index, int32_t* d_obs, void* stream);
+int mrts_obs_onehot_packed_dev(mrts_env* env, int32_t n_rows, const uint32_t* d_packed, int32_t n_packed, int32_t cap,
+                               const int32_t* d_index, uint8_t* d_out, void* stream);
+int mrts_obs_packed_status(mrts_env* env, int64_t* lossy_rows, int64_t* bad_reads);
 
 /* Batched forward model for search AIs: GameState.clone() + playouts + evaluation,
  * as NaiveMCTS / ModelledEvaluationMCTS use the engine.  Games of a forward-model handle are its slots

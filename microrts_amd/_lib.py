@@ -85,7 +85,7 @@ def device_code_sha256(path=None):
 EXPORTS = [
     "mrts_create", "mrts_dims", "mrts_reset", "mrts_step", "mrts_get_masks", "mrts_step_rows", "mrts_get_masks_i32",
     "mrts_get_masks_host", "mrts_get_masks_i32_host",
-    "mrts_reset_dev", "mrts_step_dev", "mrts_get_masks_dev", "mrts_step_rows_dev", "mrts_get_masks_i32_dev", "mrts_onehot_features", "mrts_onehot_dev", "mrts_policy_dev", "mrts_step_fused_dev", "mrts_rollout_fused_dev", "mrts_set_rollout_events", "mrts_rccl_unique_id", "mrts_exchange_init", "mrts_exchange_init_loopback", "mrts_rollout_fused_exchange_dev", "mrts_rollout_uniform_exchange_dev", "mrts_set_exchange_bytes", "mrts_set_records", "mrts_record_words", "mrts_rollout_fused_records_dev", "mrts_rollout_uniform_records_dev", "mrts_render_records_dev", "mrts_render_status", "mrts_render_records_onehot_dev", "mrts_set_step_responses", "mrts_capture_begin", "mrts_capture_end", "mrts_replay", "mrts_set_multi_step", "mrts_multi_step_capable", "mrts_set_obs16", "mrts_policy_uniform_dev", "mrts_step_uniform_dev", "mrts_rollout_uniform_dev", "mrts_policy_invalidate", "mrts_policy_head_sample_dev", "mrts_policy_head_score_dev", "mrts_policy_head_grad_dev", "mrts_policy_head_packed_words", "mrts_policy_head_pack_dev", "mrts_policy_head_pack_status", "mrts_policy_head_unpack_dev", "mrts_policy_head_score_packed_dev", "mrts_policy_head_grad_packed_dev", "mrts_set_obs_delta", "mrts_obs_invalidate", "mrts_set_source_output", "mrts_copy_games", "mrts_copy_games_dev", "mrts_playout", "mrts_playout_dev", "mrts_trace_step",
+    "mrts_reset_dev", "mrts_step_dev", "mrts_get_masks_dev", "mrts_step_rows_dev", "mrts_get_masks_i32_dev", "mrts_onehot_features", "mrts_onehot_dev", "mrts_obs_packed_words", "mrts_obs_pack_dev", "mrts_obs_unpack_dev", "mrts_obs_onehot_packed_dev", "mrts_obs_packed_status", "mrts_policy_dev", "mrts_step_fused_dev", "mrts_rollout_fused_dev", "mrts_set_rollout_events", "mrts_rccl_unique_id", "mrts_exchange_init", "mrts_exchange_init_loopback", "mrts_rollout_fused_exchange_dev", "mrts_rollout_uniform_exchange_dev", "mrts_set_exchange_bytes", "mrts_set_records", "mrts_record_words", "mrts_rollout_fused_records_dev", "mrts_rollout_uniform_records_dev", "mrts_render_records_dev", "mrts_render_status", "mrts_render_records_onehot_dev", "mrts_set_step_responses", "mrts_capture_begin", "mrts_capture_end", "mrts_replay", "mrts_set_multi_step", "mrts_multi_step_capable", "mrts_set_obs16", "mrts_policy_uniform_dev", "mrts_step_uniform_dev", "mrts_rollout_uniform_dev", "mrts_policy_invalidate", "mrts_policy_head_sample_dev", "mrts_policy_head_score_dev", "mrts_policy_head_grad_dev", "mrts_policy_head_packed_words", "mrts_policy_head_pack_dev", "mrts_policy_head_pack_status", "mrts_policy_head_unpack_dev", "mrts_policy_head_score_packed_dev", "mrts_policy_head_grad_packed_dev", "mrts_set_obs_delta", "mrts_obs_invalidate", "mrts_set_source_output", "mrts_copy_games", "mrts_copy_games_dev", "mrts_playout", "mrts_playout_dev", "mrts_trace_step",
     "mrts_evaluate", "mrts_evaluate_dev", "mrts_utt_json", "mrts_get_state_json",
     "mrts_set_state_json", "mrts_checkpoint_size", "mrts_checkpoint", "mrts_restore", "mrts_get_state", "mrts_error_flags", "mrts_env_steps", "mrts_stream",
     "mrts_destroy", "mrts_last_error",
@@ -157,6 +157,11 @@ def load(path=LIB_PATH):
     L.mrts_get_masks_i32_dev.argtypes = [P, I32, P, P]
     L.mrts_onehot_features.argtypes = [P]
     L.mrts_onehot_dev.argtypes = [P, P, P, P]
+    L.mrts_obs_packed_words.argtypes = [P, I32]
+    L.mrts_obs_pack_dev.argtypes = [P, I32, P, I32, P, P]
+    L.mrts_obs_unpack_dev.argtypes = [P, I32, P, I32, I32, P, P, P]
+    L.mrts_obs_onehot_packed_dev.argtypes = [P, I32, P, I32, I32, P, P, P]
+    L.mrts_obs_packed_status.argtypes = [P, ctypes.POINTER(ctypes.c_int64), ctypes.POINTER(ctypes.c_int64)]
     L.mrts_reset_dev.argtypes = [P, P, P, P, P, P, I32, P]
     L.mrts_step_dev.argtypes = [P, P, P, P, P, P, P, I32, P]
     L.mrts_get_masks_dev.argtypes = [P, I32, P, P]

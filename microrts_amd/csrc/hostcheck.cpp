@@ -5,7 +5,8 @@
 //     same dump after a second trip;
 //   * the three built-in tables under each conflict policy, and the table file, round-trip through JSON;
 //   * every proper prefix of the smallest map, of the table file and of the smallest map's state goes to its parser:
-//     each must end in a Fail or a clean parse.
+//     each must end in a Fail or a clean parse;
+//   * the packed observation rows' word count and every refusal of their argument checks.
 // Any other exception leaves main (std::terminate), a sanitizer report aborts: both fail the make target.
 #include <cstdio>
 #include <fstream>
@@ -135,6 +136,53 @@ int main(int argc, char** argv) {
         std::vector<int32_t> s((size_t)stateWords(smallShape.CAP, smallShape.HW), 0);
         jsonToBlock(smallShape, t, s);
     });
+    // packed observation rows: the word count and every refusal of the argument checks (no buffer is dereferenced)
+    {
+        static_assert(obsPackedWords(6, 256, 128) == 265 && obsPackedWords(8, 1024, 128) == 353 && obsPackedWords(6, 72, 72) == 148,
+                      "1 + 2 * cap + (C - 5) * ceil(H*W / 32)");
+        HandleConfig c;
+        c.H = 9, c.W = 8, c.HW = 72, c.C = 8;
+        alignas(16) static uint32_t buf[8];
+        const auto code = [](auto&& f) {
+            try {
+                f();
+                return 0;
+            } catch (const Fail& e) {
+                return e.code;
+            }
+        };
+        int refused = 0, passed = 0;
+        const auto want = [&](int rc, auto&& f, const char* what) {
+            const int got = code(f);
+            expect(got == rc, std::string("packed observation rows: ") + what);
+            (got ? refused : passed)++;
+        };
+        want(0, [&] { expect(obsPackShape(c, 5, 72).words == 1 + 144 + 9, "words of 9x8 x 8 planes"); }, "cap = H*W");
+        want(0, [&] { obsPackShape(c, 0, 1); }, "no rows, cap 1");
+        want(-EINVAL, [&] { obsPackShape(c, -1, 8); }, "n_rows < 0");
+        want(-EINVAL, [&] { obsPackShape(c, (int32_t)(((int64_t)1 << 31) / 72 + 1), 8); }, "n_rows * H*W >= 2^31");
+        want(-EINVAL, [&] { obsPackShape(c, 1, 0); }, "cap 0");
+        want(-EINVAL, [&] { obsPackShape(c, 1, 73); }, "cap H*W + 1");
+        HandleConfig big = c;
+        big.HW = OBS_MAX_CELLS + 1;
+        want(-ENOTSUP, [&] { obsPackShape(big, 1, 8); }, "more cells than a cell number holds");
+        ObsPackParams P = obsPackShape(c, 4, 8);
+        const int32_t* in = (const int32_t*)buf;
+        const uint8_t* bytes = (const uint8_t*)buf;
+        want(0, [&] { obsPackBuffers(P, in, buf); }, "buffers");
+        want(-EINVAL, [&] { obsPackBuffers(P, nullptr, buf); }, "null obs");
+        want(-EINVAL, [&] { obsPackBuffers(P, in, nullptr); }, "null out");
+        want(-EINVAL, [&] { obsPackBuffers(P, in, (uint32_t*)(bytes + 2)); }, "misaligned out");
+        want(0, [&] { obsPackedSource(P, buf, 4, nullptr, buf, 16); }, "source");
+        want(0, [&] { obsPackedSource(P, buf, 1, in, buf, 4); }, "one packed row through an index");
+        want(-EINVAL, [&] { obsPackedSource(P, nullptr, 4, nullptr, buf, 4); }, "null packed");
+        want(-EINVAL, [&] { obsPackedSource(P, buf, 4, nullptr, nullptr, 4); }, "null out");
+        want(-EINVAL, [&] { obsPackedSource(P, buf, 0, in, buf, 4); }, "no packed rows");
+        want(-EINVAL, [&] { obsPackedSource(P, buf, 3, nullptr, buf, 4); }, "fewer packed rows than rows, no index");
+        want(-EINVAL, [&] { obsPackedSource(P, buf, 4, nullptr, bytes + 4, 16); }, "one-hot out not 16-byte aligned");
+        want(-EINVAL, [&] { obsPackedSource(P, buf, 4, (const int32_t*)(bytes + 1), buf, 4); }, "misaligned index");
+        std::printf("packed observation rows: %d argument sets accepted, %d refused with an error code\n", passed, refused);
+    }
     if (g_bad) std::printf("%d check(s) FAILED\n", g_bad);
     else std::printf("clean\n");
     return g_bad ? 1 : 0;

@@ -1,5 +1,5 @@
 // mrts_aux.hip — gfx950 kernels beside the step: the one-hot and record renderers, the mask widening, the forward
-// model's game copies and the evaluation function.
+// model's game copies, the evaluation function and the packed observation rows.
 #include <hip/hip_runtime.h>
 #include <stdint.h>
 
@@ -41,6 +41,17 @@ __global__ __launch_bounds__(256) void k_onehot(OneHotParams Q) {
     for (int64_t k = t; k < n16; k += 256) ((uint4*)dst)[k] = ((const uint4*)buf)[k];
     for (int64_t k = 16 * n16 + t; k < nbytes; k += 256) dst[k] = buf[k];
 }
+// the one definition of the encoding's table: plane p's one-hot size and its first byte in a cell's F bytes (F returned)
+static int oneHotTable(int C, int ntypes, int32_t sizes[8], int32_t offs[8]) {
+    const int base[6] = {5, 5, 3, ntypes + 1, 6, 2};
+    int f = 0;
+    for (int p = 0; p < 8; p++) {
+        sizes[p] = p < 6 ? base[p] : 2;
+        offs[p] = f;
+        if (p < C) f += sizes[p];
+    }
+    return f;
+}
 hipError_t launchOneHot(const int32_t* obs, uint8_t* out, int n_slots, int HW, int C, int ntypes, hipStream_t stream) {
     OneHotParams Q;
     Q.obs = obs;
@@ -48,14 +59,7 @@ hipError_t launchOneHot(const int32_t* obs, uint8_t* out, int n_slots, int HW, i
     Q.n_cells = n_slots * HW;
     Q.HW = HW;
     Q.C = C;
-    const int base[6] = {5, 5, 3, ntypes + 1, 6, 2};
-    int f = 0;
-    for (int p = 0; p < 8; p++) {
-        Q.sizes[p] = p < 6 ? base[p] : 2;
-        Q.offs[p] = f;
-        if (p < C) f += Q.sizes[p];
-    }
-    Q.F = f;
+    const int f = Q.F = oneHotTable(C, ntypes, Q.sizes, Q.offs);
     if (C > 8 || f > 40 || ((uintptr_t)out & 15)) return hipErrorInvalidValue;
     hipLaunchKernelGGL(k_onehot, dim3((unsigned)((Q.n_cells + 255) / 256)), dim3(256), 0, stream, Q);
     return hipGetLastError();
@@ -316,14 +320,7 @@ hipError_t launchRenderRecordsOneHot(const KStatic& hs, const KStatic* ds, const
                                      int units, int64_t rank_stride, const int32_t* sel, const int64_t* step_off, int n_sel,
                                      uint8_t* out, int32_t* err, hipStream_t stream) {
     OneHotParams Q{};
-    const int base[6] = {5, 5, 3, hs.utt.ntypes + 1, 6, 2};
-    int f = 0;
-    for (int q = 0; q < 6; q++) {
-        Q.sizes[q] = base[q];
-        Q.offs[q] = f;
-        f += base[q];
-    }
-    Q.F = f;
+    const int f = Q.F = oneHotTable(6, hs.utt.ntypes, Q.sizes, Q.offs);
     if (hs.partial_obs || hs.HW > 256 || f > 40 || ((size_t)hs.HW * f) % 16 || ((uintptr_t)out & 15)) return hipErrorInvalidValue;
     if (n_sel <= 0) return hipSuccess;
     hipLaunchKernelGGL(k_render_records_onehot, dim3((unsigned)n_sel), dim3(256), 0, stream, ds, rec, units, rank_stride, sel,
@@ -419,6 +416,228 @@ hipError_t launchEvaluate(const KStatic& hs, const KStatic* ds, int maxplayer, f
     // the handle's block stride: a handle with a LightRush game has the bot memory after every state block
     const int words = hs.bot_off ? hs.bot_off + botWords(hs.CAP) : stateWords(hs.CAP, hs.HW);
     hipLaunchKernelGGL(k_evaluate, dim3((unsigned)hs.n_games), dim3(64), 0, stream, ds, hs.state, words, hs.CAP, maxplayer, out);
+    return hipGetLastError();
+}
+
+// ---------------------------------------------------------------- packed observation rows
+// include/mrts.h "Packed observation rows": what a rollout keeps of an observation [C][HW] — its occupied cells (any
+// of planes 0-4 non-zero) as two words each, and planes 5.. as bitmaps.
+constexpr int OBS_STG = 192;    // cells k_obs_pack stages in LDS between flushes (a chunk adds at most 64)
+constexpr int OBS_BMSEG = 128;  // bitmap words per plane it stages between flushes (64 chunks; even)
+constexpr int OBS_TILE = 256;   // cells of a reader's tile (one thread each)
+DEV int wordAlign(const void* p) { return (int)(((uintptr_t)p >> 2) & 3); }
+DEV int obsClamp(int v, int lo, int hi, bool& clamped) {
+    const int c = min(max(v, lo), hi);
+    clamped |= c != v;
+    return c;
+}
+// the staged words [w0, w0 + nw) of every bitmap to the row (brow: its first bitmap word)
+template <int C>
+DEV void obsFlushBitmaps(int32_t (*bm)[4 + OBS_BMSEG + 4], int32_t* brow, int MW, int w0, int nw, int lane) {
+    __syncthreads();
+#pragma unroll
+    for (int q = 0; q < C - 5; q++) {
+        int32_t* g = brow + (size_t)q * MW + w0;
+        const int ab = wordAlign(g);
+        headFlush(bm[q], g - ab, ab, nw, lane);
+    }
+    __syncthreads();
+}
+// One wave per row.  Per 64 cells every lane loads its cell's C plane values (unconditional loads, in flight
+// together); one ballot of "any of planes 0-4 non-zero" marks the occupied lanes, whose place in the row is the count
+// before the chunk plus the occupied lanes below; a ballot per plane 5.. is two bitmap words.  Cells and bitmaps are
+// composed in LDS and leave as dwordx4 (headFlush), count word and zero tail included; a row of more cells than
+// OBS_STG, or of more bitmap words than OBS_BMSEG, flushes in between.  Row starts are only 4-byte aligned.
+template <int C>
+__global__ __launch_bounds__(64) void k_obs_pack(ObsPackParams P) {
+    __shared__ __align__(16) int32_t stg[4 + 1 + 2 * OBS_STG + 3];
+    __shared__ __align__(16) int32_t bm[C - 5][4 + OBS_BMSEG + 4];
+    const int lane = (int)threadIdx.x, row = (int)blockIdx.x, HW = P.HW, MW = (HW + 31) / 32;
+    const int32_t* o = P.obs + (size_t)row * C * HW;
+    int32_t* orow = (int32_t*)P.packed_out + (size_t)row * (size_t)P.words;
+    int32_t* brow = orow + 1 + 2 * P.cap;
+    // staged: the row's words [r0, r0 + rn) at stg[a + (word - r0)], orow + r0 - a 16-byte aligned; bitmap words
+    // [w0, w0 + OBS_BMSEG) of plane 5 + q at bm[q][its own alignment + (word - w0)]
+    int total = 0, r0 = 0, rn = 1, a = wordAlign(orow), w0 = 0;
+    bool lossy = false;
+    for (int c0 = 0; c0 < HW; c0 += 64) {
+        const int c = c0 + lane;
+        const bool in = c < HW;
+        int v[C];
+#pragma unroll
+        for (int p = 0; p < C; p++) v[p] = o[(size_t)p * HW + (in ? c : 0)];
+        const bool occ = in && (v[0] | v[1] | v[2] | v[3] | v[4]) != 0;
+        const uint64_t m = ballot(occ);
+        const int bw = c0 >> 5;  // the chunk's first bitmap word
+        if (bw >= w0 + OBS_BMSEG) {
+            obsFlushBitmaps<C>(bm, brow, MW, w0, OBS_BMSEG, lane);
+            w0 += OBS_BMSEG;
+        }
+#pragma unroll
+        for (int p = 5; p < C; p++) {
+            const uint64_t b = ballot(in && v[p] != 0);
+            lossy |= in && (uint32_t)v[p] > 1u;
+            if (lane == 0) {
+                int32_t* s = bm[p - 5] + wordAlign(brow + (size_t)(p - 5) * MW + w0) + (bw - w0);
+                s[0] = (int32_t)(uint32_t)b;
+                if (bw + 1 < MW) s[1] = (int32_t)(uint32_t)(b >> 32);
+            }
+        }
+        if (m == 0) continue;
+        const int nc = __builtin_popcountll(m), keep = max(0, min(nc, P.cap - total));
+        total += nc;
+        if (keep == 0) continue;
+        if (rn + 2 * keep > 1 + 2 * OBS_STG) {  // word 0 waits for the count
+            __syncthreads();
+            if (r0 == 0) headFlush(stg, orow - a, a + 1, rn - 1, lane);
+            else headFlush(stg, orow + r0 - a, a, rn, lane);
+            __syncthreads();
+            r0 += rn;
+            rn = 0;
+            a = wordAlign(orow + r0);
+        }
+        const int pos = lanes_below(m);
+        if (occ && pos < keep) {
+            int32_t* s = stg + a + rn + 2 * pos;
+            bool cl = false;
+            const uint32_t hp = (uint32_t)obsClamp(v[0], -32768, 32767, cl) & 0xFFFFu;
+            const uint32_t res = (uint32_t)obsClamp(v[1], 0, 65535, cl), ow = (uint32_t)obsClamp(v[2], 0, 3, cl);
+            const uint32_t ty = (uint32_t)obsClamp(v[3], 0, 31, cl), ac = (uint32_t)obsClamp(v[4], 0, 7, cl);
+            s[0] = (int32_t)((uint32_t)c | (ow << 16) | (ac << 18) | (ty << 21));
+            s[1] = (int32_t)(hp | (res << 16));
+            lossy |= cl;
+        }
+        rn += 2 * keep;
+    }
+    const bool flag = ballot(lossy) != 0 || total > P.cap;
+    if (lane == 0) {
+        const int32_t w = (int32_t)((uint32_t)total | (flag ? 0x80000000u : 0u));
+        if (r0 == 0) stg[a] = w;
+        else orow[0] = w;
+        if (flag) atomicAdd(P.counters, 1ull);
+    }
+    __syncthreads();
+    headFlush(stg, orow + r0 - a, a, rn, lane);
+    const int t0 = r0 + rn, a2 = wordAlign(orow + t0);
+    headFlush(nullptr, orow + t0 - a2, a2, 1 + 2 * P.cap - t0, lane);
+    obsFlushBitmaps<C>(bm, brow, MW, w0, MW - w0, lane);
+}
+
+// The readers, one 256-thread block per (row, tile of OBS_TILE cells).  Output row r reads packed row index[r] (r
+// without an index); an index outside the packed rows gives a zero output row and one bad read.  A stored count
+// above cap reads cap cells; a stored cell outside the map is skipped and is one bad read (counted by the row's
+// first tile).  Every tile looks at every kept cell and takes those inside it, so nothing depends on their order.
+struct ObsRow {
+    const uint32_t* w;  // the packed row, null: an index outside the packed rows
+    uint32_t n;         // its kept cells
+};
+DEV ObsRow obsPackedRow(const ObsPackParams& P, int row, bool first) {
+    const int64_t pr = P.index ? (int64_t)P.index[row] : (int64_t)row;
+    ObsRow R = {nullptr, 0u};
+    if (pr >= 0 && pr < (int64_t)P.n_packed) {
+        R.w = P.packed + (size_t)pr * (size_t)P.words;
+        R.n = min(R.w[0] & 0x7FFFFFFFu, (uint32_t)P.cap);
+    } else if (first && threadIdx.x == 0) {
+        atomicAdd(P.counters + 1, 1ull);
+    }
+    return R;
+}
+// The tile's kept cells into its per-cell words (cwA: word A >> 16, cwB: word B; zero = an empty cell), and the
+// thread's own cell's bits of planes 5.. (bit q: plane 5 + q).  The first round's cell words and the bitmap words
+// are loaded before the count is looked at — they lie inside the row whatever the count says (entry t < cap) — so
+// a row costs one memory round after its index.
+DEV uint32_t obsScatter(const ObsPackParams& P, ObsRow R, int t0, int ncell, uint32_t* cwA, uint32_t* cwB, bool first) {
+    const int t = (int)threadIdx.x, MW = (P.HW + 31) / 32, c = t0 + min(t, ncell - 1);
+    uint32_t i = (uint32_t)t, A = 0u, B = 0u, bw[3] = {0u, 0u, 0u};
+    if (i < (uint32_t)P.cap) A = R.w[1 + 2 * (size_t)i], B = R.w[2 + 2 * (size_t)i];
+#pragma unroll
+    for (int q = 0; q < 3; q++)
+        if (q < P.C - 5) bw[q] = R.w[1 + 2 * (size_t)P.cap + (size_t)q * MW + (c >> 5)];
+    cwA[t] = 0u;
+    cwB[t] = 0u;
+    __syncthreads();
+    while (i < R.n) {
+        const uint32_t cell = A & 0xFFFFu, k = cell - (uint32_t)t0;  // (a cell below the tile wraps past ncell)
+        if (cell >= (uint32_t)P.HW) {
+            if (first) atomicAdd(P.counters + 1, 1ull);
+        } else if (k < (uint32_t)ncell) {
+            cwA[k] = A >> 16;
+            cwB[k] = B;
+        }
+        i += OBS_TILE;
+        if (i < R.n) A = R.w[1 + 2 * (size_t)i], B = R.w[2 + 2 * (size_t)i];
+    }
+    __syncthreads();
+    return ((bw[0] >> (c & 31)) & 1u) | (((bw[1] >> (c & 31)) & 1u) << 1) | (((bw[2] >> (c & 31)) & 1u) << 2);
+}
+// int32 planes [n_rows][C][HW]: each plane's OBS_TILE words composed in LDS, then aligned 16-byte stores (headFlush)
+__global__ __launch_bounds__(OBS_TILE) void k_obs_unpack(ObsPackParams P) {
+    __shared__ uint32_t cwA[OBS_TILE], cwB[OBS_TILE];
+    __shared__ __align__(16) int32_t sp[8][4 + OBS_TILE + 4];
+    const int t = (int)threadIdx.x, row = (int)blockIdx.x, t0 = (int)blockIdx.y * OBS_TILE, HW = P.HW, C = P.C;
+    const int ncell = min(OBS_TILE, HW - t0);
+    const ObsRow R = obsPackedRow(P, row, blockIdx.y == 0);
+    int32_t* orow = P.obs_out + (size_t)row * C * HW + t0;
+    if (R.w) {
+        const uint32_t bits = obsScatter(P, R, t0, ncell, cwA, cwB, blockIdx.y == 0);
+        if (t < ncell) {
+            const uint32_t x = cwA[t], B = cwB[t];
+            const int v[5] = {(int)(int16_t)(uint16_t)(B & 0xFFFFu), (int)(B >> 16), (int)(x & 3u), (int)((x >> 5) & 31u),
+                              (int)((x >> 2) & 7u)};
+#pragma unroll
+            for (int p = 0; p < 5; p++) sp[p][wordAlign(orow + (size_t)p * HW) + t] = v[p];
+            for (int p = 5; p < C; p++) sp[p][wordAlign(orow + (size_t)p * HW) + t] = (int)((bits >> (p - 5)) & 1u);
+        }
+        __syncthreads();
+    }
+    for (int p = 0; p < C; p++) {
+        int32_t* g = orow + (size_t)p * HW;
+        const int ab = wordAlign(g);
+        headFlush(R.w ? sp[p] : nullptr, g - ab, ab, ncell, t, OBS_TILE);
+    }
+}
+// the one-hot encoding [n_rows][HW][F] (k_onehot's bytes on the tensor the row was packed from): each cell's F
+// bytes composed in zeroed LDS by the cell's thread, then aligned 16-byte stores (headFlushBytes)
+__global__ __launch_bounds__(OBS_TILE) void k_obs_onehot_packed(ObsPackParams P) {
+    __shared__ uint32_t cwA[OBS_TILE], cwB[OBS_TILE];
+    __shared__ __align__(16) uint8_t buf[16 + OBS_TILE * 40 + 16];
+    const int t = (int)threadIdx.x, row = (int)blockIdx.x, t0 = (int)blockIdx.y * OBS_TILE, HW = P.HW, C = P.C, F = P.F;
+    const int ncell = min(OBS_TILE, HW - t0), nb = ncell * F;
+    const ObsRow R = obsPackedRow(P, row, blockIdx.y == 0);
+    uint8_t* g = P.onehot_out + ((size_t)row * HW + t0) * F;
+    const int ab = (int)((uintptr_t)g & 15);
+    if (R.w) {
+        for (int k = t; k < ((ab + nb + 15) >> 4); k += OBS_TILE) ((int4*)buf)[k] = make_int4(0, 0, 0, 0);
+        const uint32_t bits = obsScatter(P, R, t0, ncell, cwA, cwB, blockIdx.y == 0);  // (its barriers also order the zeroing)
+        if (t < ncell) {
+            const uint32_t x = cwA[t], B = cwB[t];
+            const int v[5] = {(int)(int16_t)(uint16_t)(B & 0xFFFFu), (int)(B >> 16), (int)(x & 3u), (int)((x >> 5) & 31u),
+                              (int)((x >> 2) & 7u)};
+            uint8_t* cellb = buf + ab + t * F;
+#pragma unroll
+            for (int p = 0; p < 5; p++) cellb[P.offs[p] + min(max(v[p], 0), P.sizes[p] - 1)] = 1;
+            for (int p = 5; p < C; p++) cellb[P.offs[p] + ((bits >> (p - 5)) & 1u)] = 1;
+        }
+        __syncthreads();
+    }
+    headFlushBytes(R.w ? buf : nullptr, g - ab, ab, nb, t, OBS_TILE);
+}
+hipError_t launchObsPacked(int mode, ObsPackParams P, int ntypes, hipStream_t stream) {
+    P.F = oneHotTable(P.C, ntypes, P.sizes, P.offs);
+    if ((P.C != 6 && P.C != 8) || P.F > 40 || P.HW > OBS_MAX_CELLS || P.cap < 1 || P.cap > P.HW ||
+        P.words != obsPackedWords(P.C, P.HW, P.cap) || !P.counters)
+        return hipErrorInvalidValue;
+    if (P.n_rows <= 0) return hipSuccess;
+    const dim3 tiles((unsigned)P.n_rows, (unsigned)((P.HW + OBS_TILE - 1) / OBS_TILE));
+    if (mode == OBS_PACK) {
+        if (P.C == 6) hipLaunchKernelGGL(k_obs_pack<6>, dim3((unsigned)P.n_rows), dim3(64), 0, stream, P);
+        else hipLaunchKernelGGL(k_obs_pack<8>, dim3((unsigned)P.n_rows), dim3(64), 0, stream, P);
+    } else if (mode == OBS_UNPACK) {
+        hipLaunchKernelGGL(k_obs_unpack, tiles, dim3(OBS_TILE), 0, stream, P);
+    } else {
+        if ((uintptr_t)P.onehot_out & 15) return hipErrorInvalidValue;
+        hipLaunchKernelGGL(k_obs_onehot_packed, tiles, dim3(OBS_TILE), 0, stream, P);
+    }
     return hipGetLastError();
 }
 }  // namespace mrts

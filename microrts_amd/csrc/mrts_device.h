@@ -352,6 +352,38 @@ DEV void paintDiskRows(uint32_t* rows, int H, int W, int x, int y, int sr, uint3
         }
     }
 }
+// nw words of a chunk to global memory as dwordx4 where whole vectors lie inside it: LDS word t <-> gp[t], the
+// chunk at t in [a, a + nw) with gp 16-byte aligned (a = the chunk's word offset in its vector).  lds null: zeros.
+// nl: the lanes that call it (lane in [0, nl)).
+DEV void headFlush(const int32_t* lds, int32_t* gp, int a, int nw, int lane, int nl = 64) {
+    const int nv = (a + nw + 3) >> 2;
+    for (int v = lane; v < nv; v += nl) {
+        const int t = 4 * v;
+        const int4 x = lds ? ((const int4*)lds)[v] : make_int4(0, 0, 0, 0);
+        if (t >= a && t + 4 <= a + nw) {
+            ((int4*)gp)[v] = x;
+        } else {
+            const int xs[4] = {x.x, x.y, x.z, x.w};
+#pragma unroll
+            for (int k = 0; k < 4; k++)
+                if (t + k >= a && t + k < a + nw) gp[t + k] = xs[k];
+        }
+    }
+}
+// nb bytes of a chunk to global memory as dwordx4 where whole vectors lie inside it: LDS byte t <-> gp[t], the chunk
+// at t in [a, a + nb) with gp 16-byte aligned.  lds null: zeros.
+DEV void headFlushBytes(const uint8_t* lds, uint8_t* gp, int a, int nb, int lane, int nl = 64) {
+    const int nv = (a + nb + 15) >> 4;
+    for (int v = lane; v < nv; v += nl) {
+        const int t = 16 * v;
+        if (t >= a && t + 16 <= a + nb) {
+            ((int4*)gp)[v] = lds ? ((const int4*)lds)[v] : make_int4(0, 0, 0, 0);
+        } else {
+            for (int k = 0; k < 16; k++)
+                if (t + k >= a && t + k < a + nb) gp[t + k] = lds ? lds[t + k] : (uint8_t)0;
+        }
+    }
+}
 }  // namespace
 
 #ifdef MRTS_LANE_AUDIT

@@ -64,6 +64,7 @@ struct mrts_env : HandleConfig {
     uint32_t* d_prioTab = nullptr;  // multi-step launches: per-SIMD issue-rank table (KDyn.prio_tab)
     int32_t* d_renderErr = nullptr; // the record renders' overflow flag (mrts_render_status)
     unsigned long long* d_packOverflow = nullptr;  // rows mrts_policy_head_pack_dev cut at cap (mrts_policy_head_pack_status)
+    unsigned long long* d_obsPackCnt = nullptr;  // packed observation rows: lossy rows, bad reads (mrts_obs_packed_status)
     int32_t* d_bal = nullptr;       // multi-step launches: balanced game placement (KDyn.bal)
     bool exPending[2] = {false, false};  // exDone[b] was recorded by an earlier (eager) exchange call
     hipStream_t exLastStream = nullptr;  // the stream of the last eager exchange call (already waits for them)
@@ -1342,6 +1343,80 @@ int mrts_policy_head_grad_packed_dev(mrts_env* env, int32_t n_rows, const float*
     });
 }
 
+// ---- packed observation rows (include/mrts.h; the argument checks are mrts_hostdata.cpp's)
+namespace {
+// the counters of mrts_obs_packed_status, allocated at the first call outside a capture (an allocation and a memset
+// cannot be captured): a first call inside one is refused
+void obsPackCounters(mrts_env* env, hipStream_t s) {
+    if (env->d_obsPackCnt) return;
+    hipStreamCaptureStatus cst = hipStreamCaptureStatusNone;
+    HIPCHK(hipStreamIsCapturing(s, &cst));
+    if (cst != hipStreamCaptureStatusNone)
+        throw Fail{-EINVAL, "packed observation rows: make the first call (mrts_obs_packed_status will do) outside a capture"};
+    HIPCHK(hipMalloc(&env->d_obsPackCnt, 16));
+    HIPCHK(hipMemset(env->d_obsPackCnt, 0, 16));
+}
+}  // namespace
+
+int32_t mrts_obs_packed_words(const mrts_env* env, int32_t cap) {
+    return guarded(env, [&] { return obsPackShape(*env, 0, cap).words; });
+}
+
+int mrts_obs_pack_dev(mrts_env* env, int32_t n_rows, const int32_t* d_obs, int32_t cap, uint32_t* d_out, void* stream) {
+    return guarded(env, [&] {
+        ObsPackParams P = obsPackShape(*env, n_rows, cap);
+        obsPackBuffers(P, d_obs, d_out);
+        HIPCHK(hipSetDevice(env->device));
+        obsPackCounters(env, pickStream(env, stream));
+        P.counters = env->d_obsPackCnt;
+        HIPCHK(launchObsPacked(OBS_PACK, P, env->utt.ntypes, pickStream(env, stream)));
+        return 0;
+    });
+}
+
+int mrts_obs_unpack_dev(mrts_env* env, int32_t n_rows, const uint32_t* d_packed, int32_t n_packed, int32_t cap,
+                        const int32_t* d_index, int32_t* d_obs, void* stream) {
+    return guarded(env, [&] {
+        ObsPackParams P = obsPackShape(*env, n_rows, cap);
+        obsPackedSource(P, d_packed, n_packed, d_index, d_obs, 4);
+        HIPCHK(hipSetDevice(env->device));
+        obsPackCounters(env, pickStream(env, stream));
+        P.counters = env->d_obsPackCnt;
+        P.obs_out = d_obs;
+        HIPCHK(launchObsPacked(OBS_UNPACK, P, env->utt.ntypes, pickStream(env, stream)));
+        return 0;
+    });
+}
+
+int mrts_obs_onehot_packed_dev(mrts_env* env, int32_t n_rows, const uint32_t* d_packed, int32_t n_packed, int32_t cap,
+                               const int32_t* d_index, uint8_t* d_out, void* stream) {
+    return guarded(env, [&] {
+        ObsPackParams P = obsPackShape(*env, n_rows, cap);
+        obsPackedSource(P, d_packed, n_packed, d_index, d_out, 16);
+        HIPCHK(hipSetDevice(env->device));
+        obsPackCounters(env, pickStream(env, stream));
+        P.counters = env->d_obsPackCnt;
+        P.onehot_out = d_out;
+        HIPCHK(launchObsPacked(OBS_ONEHOT, P, env->utt.ntypes, pickStream(env, stream)));
+        return 0;
+    });
+}
+
+int mrts_obs_packed_status(mrts_env* env, int64_t* lossy_rows, int64_t* bad_reads) {
+    return guarded(env, [&] {
+        if (!lossy_rows || !bad_reads) throw Fail{-EINVAL, "null argument"};
+        HIPCHK(hipSetDevice(env->device));
+        obsPackCounters(env, nullptr);
+        HIPCHK(hipDeviceSynchronize());
+        unsigned long long v[2] = {0, 0};
+        HIPCHK(hipMemcpy(v, env->d_obsPackCnt, 16, hipMemcpyDeviceToHost));
+        if (v[0] | v[1]) HIPCHK(hipMemset(env->d_obsPackCnt, 0, 16));
+        *lossy_rows = (int64_t)v[0];
+        *bad_reads = (int64_t)v[1];
+        return 0;
+    });
+}
+
 static void fillResponses(mrts_env* env, mrts_responses* out) {
     const size_t S = (size_t)env->nSlots;
     HIPCHK(hipMemcpyAsync(env->h_obs, env->d_obs, S * env->C * env->HW * 4, hipMemcpyDeviceToHost, env->stream));
@@ -1518,6 +1593,7 @@ void mrts_destroy(mrts_env* env) {
     (void)hipFree(env->d_prioTab);
     (void)hipFree(env->d_renderErr);
     (void)hipFree(env->d_packOverflow);
+    (void)hipFree(env->d_obsPackCnt);
     (void)hipFree(env->d_bal);
     (void)hipFree(env->d_state);
     (void)hipFree(env->d_polPrev);

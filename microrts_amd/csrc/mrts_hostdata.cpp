@@ -787,6 +787,38 @@ void checkCkpt(const HandleConfig& c, const void* buf, int64_t size) {
     if (size != ckptSize(c)) throw Fail{-EINVAL, "checkpoint size mismatch"};
 }
 
+// ------------------------------------------------------------------ packed observation rows
+ObsPackParams obsPackShape(const HandleConfig& c, int32_t n_rows, int32_t cap) {
+    if (c.HW > OBS_MAX_CELLS || (c.C != 6 && c.C != 8))
+        throw Fail{-ENOTSUP, "packed observation rows: maps of at most 65536 cells, 6 or 8 planes"};
+    if (n_rows < 0 || (int64_t)n_rows * c.HW >= ((int64_t)1 << 31)) throw Fail{-EINVAL, "n_rows: 0 <= n_rows * H*W < 2^31"};
+    if (cap < 1 || cap > c.HW) throw Fail{-EINVAL, "cap: 1 <= cap <= H*W"};
+    ObsPackParams P;
+    std::memset(&P, 0, sizeof(P));
+    P.HW = c.HW;
+    P.C = c.C;
+    P.cap = cap;
+    P.words = obsPackedWords(c.C, c.HW, cap);
+    P.n_rows = n_rows;
+    return P;
+}
+void obsPackBuffers(ObsPackParams& P, const int32_t* d_obs, uint32_t* d_out) {
+    if (!d_obs || !d_out) throw Fail{-EINVAL, "null argument"};
+    if (((uintptr_t)d_obs & 3) || ((uintptr_t)d_out & 3)) throw Fail{-EINVAL, "misaligned buffer"};
+    P.obs = d_obs;
+    P.packed_out = d_out;
+}
+void obsPackedSource(ObsPackParams& P, const uint32_t* d_packed, int32_t n_packed, const int32_t* d_index, const void* d_out,
+                     int out_align) {
+    if (!d_packed || !d_out) throw Fail{-EINVAL, "null argument"};
+    if (n_packed < 1 || (!d_index && n_packed < P.n_rows)) throw Fail{-EINVAL, "n_packed: at least 1, and n_rows without an index"};
+    if (((uintptr_t)d_packed & 3) || ((uintptr_t)d_index & 3) || ((uintptr_t)d_out & (uintptr_t)(out_align - 1)))
+        throw Fail{-EINVAL, "misaligned buffer"};
+    P.packed = d_packed;
+    P.n_packed = n_packed;
+    P.index = d_index;
+}
+
 }  // namespace mrts
 
 // ------------------------------------------------------------------ internal probes

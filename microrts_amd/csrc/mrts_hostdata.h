@@ -128,4 +128,13 @@ inline int64_t ckptSize(const HandleConfig& c) { return (int64_t)sizeof(CkptHead
 // the checks of mrts_restore on a checkpoint of `size` bytes at buf; throws Fail
 void checkCkpt(const HandleConfig& c, const void* buf, int64_t size);
 
+// ------------------------------------------------------------------ packed observation rows
+// The argument checks of mrts_obs_pack_dev / _unpack_dev / _onehot_packed_dev (include/mrts.h), without a device:
+// the shape fields of the kernels' parameters for n_rows rows at `cap`, then the buffers; each throws Fail.
+ObsPackParams obsPackShape(const HandleConfig& c, int32_t n_rows, int32_t cap);
+void obsPackBuffers(ObsPackParams& P, const int32_t* d_obs, uint32_t* d_out);
+// out_align: 4 (the int32 planes) or 16 (the one-hot bytes)
+void obsPackedSource(ObsPackParams& P, const uint32_t* d_packed, int32_t n_packed, const int32_t* d_index, const void* d_out,
+                     int out_align);
+
 }  // namespace mrts

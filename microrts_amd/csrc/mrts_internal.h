@@ -294,4 +294,23 @@ struct HeadPackedParams {
     unsigned long long* overflow;  // pack: rows with more than cap candidates (mrts_policy_head_pack_status)
 };
 
+// The packed observation row (include/mrts.h, "Packed observation rows"): word 0 = occupied cells | lossy << 31,
+// then cap cells of two words (cell | owner << 16 | action << 18 | type << 21; hp as int16 | resources << 16),
+// then one bitmap of ceil(hw / 32) words per plane 5..c-1.  A cell number is 16 bits: hw <= OBS_MAX_CELLS.
+constexpr int OBS_MAX_CELLS = 65536;
+constexpr int obsPackedWords(int c, int hw, int cap) { return 1 + 2 * cap + (c - 5) * ((hw + 31) / 32); }
+enum : int32_t { OBS_PACK = 0, OBS_UNPACK = 1, OBS_ONEHOT = 2 };
+struct ObsPackParams {
+    int32_t HW, C, cap, words;     // words = obsPackedWords(C, HW, cap)
+    int32_t n_rows, n_packed;      // n_packed: rows of `packed` (an index outside them reads nothing)
+    const int32_t* obs;            // pack: [n_rows][C][HW]
+    uint32_t* packed_out;          // pack: [n_rows][words], every word written
+    const uint32_t* packed;        // unpack / one-hot: [n_packed][words]
+    const int32_t* index;          // unpack / one-hot, optional: row r reads packed row index[r]
+    int32_t* obs_out;              // unpack: [n_rows][C][HW], every element written
+    uint8_t* onehot_out;           // one-hot: [n_rows][HW][F], every byte written
+    unsigned long long* counters;  // [0] rows pack flagged lossy, [1] bad reads (mrts_obs_packed_status)
+    int32_t F, sizes[8], offs[8];  // the one-hot table (oneHotTable in mrts_aux.hip)
+};
+
 }  // namespace mrts

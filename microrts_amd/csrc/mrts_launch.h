@@ -1,5 +1,6 @@
 // mrts_launch.h — the one declaration of everything mrts_host.cpp calls in the .hip units (mrts_kernels.hip: the
-// step kernel; mrts_policy.hip: the random policies and the masked head; mrts_aux.hip: renderers, copies, evaluation).
+// step kernel; mrts_policy.hip: the random policies and the masked head; mrts_aux.hip: renderers, packed observation
+// rows, copies, evaluation).
 // The host and every unit include it, so a definition that drifts from its declaration fails to compile.
 #pragma once
 #include <hip/hip_runtime.h>
@@ -58,4 +59,6 @@ hipError_t launchRenderRecords(const KStatic& hs, const KStatic* ds, const uint3
 hipError_t launchRenderRecordsOneHot(const KStatic& hs, const KStatic* ds, const uint32_t* rec, int64_t rec_words, int n_ranks,
                                      int units, int64_t rank_stride, const int32_t* sel, const int64_t* step_off, int n_sel,
                                      uint8_t* out, int32_t* err, hipStream_t stream);
+// mode: OBS_PACK / OBS_UNPACK / OBS_ONEHOT (the one-hot table is filled here from P.C and ntypes)
+hipError_t launchObsPacked(int mode, ObsPackParams P, int ntypes, hipStream_t stream);
 }  // namespace mrts

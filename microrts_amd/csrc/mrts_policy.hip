@@ -404,24 +404,6 @@ DEV void headCell(HeadCell& X, const HeadParams& Q, int lane) {
     headField<MODE, 4, 16>(X, lane, l + 3, set + 3, j[3], 4 * q, 6, X.w6, a6);
 }
 
-// nw words of a chunk to global memory as dwordx4 where whole vectors lie inside it: LDS word t <-> gp[t], the
-// chunk at t in [a, a + nw) with gp 16-byte aligned (a = the chunk's word offset in its vector).  lds null: zeros.
-DEV void headFlush(const int32_t* lds, int32_t* gp, int a, int nw, int lane) {
-    const int nv = (a + nw + 3) >> 2;
-    for (int v = lane; v < nv; v += 64) {
-        const int t = 4 * v;
-        const int4 x = lds ? ((const int4*)lds)[v] : make_int4(0, 0, 0, 0);
-        if (t >= a && t + 4 <= a + nw) {
-            ((int4*)gp)[v] = x;
-        } else {
-            const int xs[4] = {x.x, x.y, x.z, x.w};
-#pragma unroll
-            for (int k = 0; k < 4; k++)
-                if (t + k >= a && t + k < a + nw) gp[t + k] = xs[k];
-        }
-    }
-}
-
 // One wave per row.  Per 64 cells: the candidate bits (source bits, or mask byte 0) as one ballot; SAMPLE / GRAD
 // compose the chunk's action / gradient rows in zeroed LDS and store them with dwordx4, a chunk without a
 // candidate as plain zero stores.  The row's log-probability and entropy are per-lane partial sums added up by one
@@ -604,21 +586,6 @@ __global__ __launch_bounds__(64) void k_head_pack(HeadPackedParams P) {
     headFlush(stg, orow + r0 - a, a, rn, lane);
     const int t0 = r0 + rn, a2 = (int)(((uintptr_t)(orow + t0) >> 2) & 3);
     headFlush(nullptr, orow + t0 - a2, a2, P.words - t0, lane);
-}
-
-// nb bytes of a chunk to global memory as dwordx4 where whole vectors lie inside it: LDS byte t <-> gp[t], the chunk
-// at t in [a, a + nb) with gp 16-byte aligned.  lds null: zeros.
-DEV void headFlushBytes(const uint8_t* lds, uint8_t* gp, int a, int nb, int lane) {
-    const int nv = (a + nb + 15) >> 4;
-    for (int v = lane; v < nv; v += 64) {
-        const int t = 16 * v;
-        if (t >= a && t + 16 <= a + nb) {
-            ((int4*)gp)[v] = lds ? ((const int4*)lds)[v] : make_int4(0, 0, 0, 0);
-        } else {
-            for (int k = 0; k < 16; k++)
-                if (t + k >= a && t + k < a + nb) gp[t + k] = lds ? lds[t + k] : (uint8_t)0;
-        }
-    }
 }
 
 // The canonical dense form of packed rows, one wave per row: per 64 cells the chunk's mask records (0 / 1 bytes)

@@ -830,6 +830,74 @@ class DeviceVecEnv:
                                                    self._p(masks_out), self._p(actions_out), self._s(stream)))
         return masks_out, actions_out
 
+    def obs_packed_words(self, cap=None):
+        """uint32 words of a packed observation row (obs_pack.py; include/mrts.h "Packed observation rows") of at
+        most `cap` occupied cells: 1 + 2 * cap + (C - 5) * ceil(H*W / 32).  cap: 1 .. H*W, default min(H*W, 128);
+        H*W can never cut a row."""
+        from . import obs_pack
+
+        return obs_pack.packed_words(self, cap)
+
+    def obs_packed_buffer(self, n_steps, cap=None):
+        """A rollout's observations, packed: uint32 zeros [n_steps][slots][obs_packed_words(cap)] — pack_obs(buf[t])
+        fills step t, onehot_packed(buf, index=mb) gives a minibatch's network input."""
+        T = self.torch
+        return T.zeros((n_steps, self._h.S, self.obs_packed_words(cap)), dtype=T.int32, device=self.device).view(T.uint32)
+
+    def pack_obs(self, out, obs=None, cap=None, stream=None):
+        """Packs observations into `out` (uint32 [n][words], such as buf[t]; every word written): one launch
+        (mrts_obs_pack_dev).  obs: default env.obs, or any int32 [n][C][H][W] with n = out's rows.  cap defaults to
+        what out's words stand for.  A row of more than cap occupied cells keeps its first cap, its true count and
+        the lossy flag, and is counted (obs_pack_status)."""
+        from . import obs_pack
+
+        h = self._h
+        src = self.obs if obs is None else obs
+        n, cap = obs_pack.check_pack_args(self, out, src, cap)
+        _lib.check(h.L.mrts_obs_pack_dev(h.h, n, self._p(src), cap, self._p(out), self._s(stream)))
+        return out
+
+    def unpack_obs(self, packed, index=None, out=None, stream=None):
+        """The int32 planes [rows][C][H][W] of packed observation rows (mrts_obs_unpack_dev): for a row without the
+        lossy flag the tensor that was packed.  packed: uint32 [N][words] or any leading shape (a [T][slots][words]
+        rollout buffer), flattened; rows: index's length (int32 on the device, gathers packed rows, repeats allowed),
+        else every packed row.  An index outside [0, N) gives a zero row and is counted (obs_pack_status)."""
+        from . import obs_pack
+
+        h, T = self._h, self.torch
+        rows, n_packed, cap = obs_pack.check_read_args(self, packed, index)
+        if out is None:
+            out = T.empty((rows, h.C, h.H, h.W), dtype=T.int32, device=self.device)
+        obs_pack.check_tensor("out", out, T.int32, [(rows, h.C, h.H, h.W)], self.device)
+        _lib.check(h.L.mrts_obs_unpack_dev(h.h, rows, self._p(packed), n_packed, cap, self._p(index), self._p(out),
+                                           self._s(stream)))
+        return out
+
+    def onehot_packed(self, packed, index=None, out=None, stream=None):
+        """onehot_obs straight from packed observation rows (mrts_obs_onehot_packed_dev): uint8 [rows][H][W][F], for
+        every row that was not cut at its cap the bytes onehot_obs gives on the tensor that was packed.  packed, index
+        and rows as unpack_obs: onehot_packed(buf, index=mb) is an update's minibatch, with no dense copy of the
+        buffer."""
+        from . import obs_pack
+
+        h, T = self._h, self.torch
+        rows, n_packed, cap = obs_pack.check_read_args(self, packed, index)
+        F = h.L.mrts_onehot_features(h.h)
+        if out is None:
+            out = T.empty((rows, h.H, h.W, F), dtype=T.uint8, device=self.device)
+        obs_pack.check_tensor("out", out, T.uint8, [(rows, h.H, h.W, F)], self.device)
+        _lib.check(h.L.mrts_obs_onehot_packed_dev(h.h, rows, self._p(packed), n_packed, cap, self._p(index), self._p(out),
+                                                  self._s(stream)))
+        return out
+
+    def obs_pack_status(self):
+        """(lossy_rows, bad_reads) since the last call of this (mrts_obs_packed_status): the rows pack_obs flagged
+        lossy (cut at cap, a clamped value, a plane 5.. value other than 0 / 1) and the bad reads of unpack_obs /
+        onehot_packed (an index outside the packed rows, a stored cell outside the map); clears both.  Synchronises."""
+        a, b = ctypes.c_int64(0), ctypes.c_int64(0)
+        _lib.check(self._h.L.mrts_obs_packed_status(self._h.h, ctypes.byref(a), ctypes.byref(b)))
+        return a.value, b.value
+
     def synchronize(self):
         self.torch.cuda.current_stream(self.device).synchronize()
 

@@ -91,6 +91,11 @@ WHY = {
                      "rounds' headCell calls (segMax / segSum / ballots inside) sit in those uniform loops, a DPP row "
                      "without a candidate running them with every bit cleared.  k_head_pack's ballots (candidates, mask "
                      "bits) are in uniform flow too: its loops test ballots, the cap and kernel arguments",
+    "k_obs_pack": "packed observation rows: no readlane or DPP — its cross-lane work is ballots (occupied cells, one per "
+                  "plane 5.., the lossy flags) and mbcnt of a ballot, all at the chunk loop's top level or after it; the "
+                  "loop's `continue`s and flushes test ballots, counts of ballots and kernel arguments (uniform), and each "
+                  "ballot's operand is a select defined on every lane (false beyond the map).  The readers "
+                  "(k_obs_unpack, k_obs_onehot_packed) have no cross-lane read",
     "k_lane_audit_probe": "the audit build's negative control (reads lane 40 from a branch only lanes 0-31 take)",
     "lrClosest": "LightRush: wave_min after the per-lane `for (o = lid() ...)` loop has reconverged; `best` starts at "
                  "INF on every lane; every caller passes wave-uniform arguments from uniform flow",
