@@ -1,15 +1,14 @@
 """Scenario helpers for the combat-unit tests: maps that put Light, Heavy and Ranged units, attacks of
 range > 1 and games that end by elimination in front of the output kernels within a few hundred steps
 (the random-policy rollouts from basesWorkers* starts never reach them: DESIGN.md, "What the random
-rollouts never reach").  Built on tests.test_kats.write_map; every map is written by the test that
+rollouts never reach").  Built on tests.defs.write_map; every map is written by the test that
 uses it.  Also the census the adequacy tests assert on (oracle only, no GPU)."""
 import numpy as np
 
 from tests import oracle_py
-from tests.test_kats import HEAVY, LIGHT, RANGED, RESOURCE, WORKER, write_map
+from tests.defs import HEAVY, LIGHT, RANGED, RESOURCE, SEED, WORKER, write_map
 
-SEED = 0x5EEDC0DE  # the policy seed of every rollout in the suite
-GAME_SEED = 3      # tests.test_gpu_parity._rollout's default game seed
+GAME_SEED = 3  # tests.gpu_checks.rollout's default game seed
 
 MELEE16 = "maps/16x16/melee16x16Mixed12.xml"
 MELEE8 = "maps/8x8/melee8x8Mixed6.xml"

@@ -11,16 +11,15 @@ import os
 
 import numpy as np
 
-from tests import oracle_py
-from tests.test_kats import HP, NAMES
+from tests import dumps, oracle_py
+from tests.defs import COST, HP, NAMES, SEED  # noqa: F401  (SEED: re-exported)
+from tests.dumps import live_units
 from tests.trace_fixtures import GROUPS, ROOT, SIZES, TR  # noqa: F401  (SIZES: re-exported)
 
-SEED = 0x5EEDC0DE  # the policy seed of every rollout in the suite
 GAME_SEED = 3
 TYPE_NAMES = [NAMES[t] for t in sorted(NAMES)]
 MAX_HP = [HP[t] for t in sorted(HP)]
 RESOURCE, WORKER = TYPE_NAMES.index("Resource"), TYPE_NAMES.index("Worker")
-COST = {"Base": 10, "Barracks": 5, "Worker": 1, "Light": 2, "Heavy": 2, "Ranged": 2}  # UnitTypeTable VERSION_ORIGINAL
 
 
 def dump_to_json(template_json, dump, type_names=TYPE_NAMES):
@@ -28,17 +27,14 @@ def dump_to_json(template_json, dump, type_names=TYPE_NAMES):
     hp, res), na, na x (unit, type, parameter, x, y, unit type, time)) as GameState.toJSON text.  Terrain
     and size come from template_json, the state_json of a freshly reset game on the same map; unit IDs
     are list positions.  Only ATTACK_LOCATION (type 5) carries x / y (UnitAction.toJSON)."""
-    d = [int(v) for v in dump]
+    time, res, units, assign = dumps.parse(dump)
     out = json.loads(template_json)
-    out["time"] = d[0]
-    out["pgs"]["players"] = [{"ID": 0, "resources": d[2]}, {"ID": 1, "resources": d[3]}]
-    nu = d[4]
-    out["pgs"]["units"] = [{"type": type_names[t], "ID": i, "player": p, "x": x, "y": y, "resources": res, "hitpoints": hp}
-                           for i, (t, p, x, y, hp, res) in enumerate(d[5 + 6 * k:11 + 6 * k] for k in range(nu))]
-    base = 5 + 6 * nu
+    out["time"] = time
+    out["pgs"]["players"] = [{"ID": 0, "resources": res[0]}, {"ID": 1, "resources": res[1]}]
+    out["pgs"]["units"] = [{"type": type_names[t], "ID": i, "player": p, "x": x, "y": y, "resources": r, "hitpoints": hp}
+                           for i, (t, p, x, y, hp, r) in enumerate(units.tolist())]
     acts = []
-    for k in range(d[base]):
-        unit, t, par, x, y, ut, when = d[base + 1 + 7 * k:base + 8 + 7 * k]
+    for unit, t, par, x, y, ut, when in assign.tolist():
         a = {"type": t}
         if t == 5:
             a["x"], a["y"] = x, y
@@ -129,7 +125,7 @@ def crowd(state_json, seed, per_window=None):
             taken[y, x] = True
     owner = {u["ID"]: u["player"] for u in pgs["units"]}
     for p in pgs["players"]:
-        due = sum(COST[a["action"]["unitType"]] for a in d["actions"] if a["action"]["type"] == 4 and owner[a["ID"]] == p["ID"])
+        due = sum(COST[TYPE_NAMES.index(a["action"]["unitType"])] for a in d["actions"] if a["action"]["type"] == 4 and owner[a["ID"]] == p["ID"])
         p["resources"] = due + int(rng.integers(0, 15))
     return json.dumps(d, separators=(",", ":"))
 
@@ -157,7 +153,7 @@ def case(size):
     for g, (mp, _fx, _k, dump) in enumerate(pick):
         j = dump_to_json(tm[mp], dump)
         crowded.append(g % 2 == 1)
-        trace_units.append(int(dump[4]))
+        trace_units.append(dumps.n_units(dump))
         states.append(crowd(j, 1000 * size[0] + 10 * size[1] + g) if crowded[-1] else j)
         maps += [mp, mp]
     edge_row = max(last_open_row(json.loads(tm[mp])["pgs"]["terrain"], size[1], size[0]) for mp in set(maps))
@@ -181,11 +177,6 @@ def java_rows(acts, reverse):
     S, HW, _ = acts.shape
     rows = np.concatenate([np.broadcast_to(np.arange(HW, dtype=np.int32)[None, :, None], (S, HW, 1)), acts], axis=2)
     return np.ascontiguousarray(rows[:, ::-1] if reverse else rows, np.int32)
-
-
-def live_units(dump):
-    nu = int(dump[4])
-    return np.asarray(dump[5:5 + 6 * nu]).reshape(-1, 6)
 
 
 def oracle_run(c, partial_obs=False):

@@ -10,18 +10,18 @@ import json
 
 import numpy as np
 
-from tests import oracle_py
+from tests import dumps, oracle_py
 from tests.combat_maps import BARRACKS16, MELEE16
-from tests.state_cases import GAME_SEED, SEED  # noqa: F401  (re-exported)
+from tests.defs import DX, DY, SEED  # noqa: F401  (re-exported)
+from tests.defs import MOVE as T_MOVE, PRODUCE as T_PRODUCE
+from tests.state_cases import GAME_SEED  # noqa: F401  (re-exported)
 
 MAP16 = "maps/16x16/basesWorkers16x16.xml"
 GAMES = 64
-T_MOVE, T_PRODUCE = 1, 4
 # Lower bounds of an assignment's duration in every unit-type table version (rts/units/UnitTypeTable.java:
 # the fastest move is Light's 8 cycles, the fastest production Worker's 50): an assignment younger than
 # that is unfinished whatever its unit
 MIN_MOVE, MIN_PRODUCE = 8, 50
-DX, DY = (0, 1, 0, -1), (-1, 0, 1, 0)  # UnitAction.DIRECTION_OFFSET_X/Y: up, right, down, left
 
 CASES = {
     # ranged and melee kills of units that hold pending MOVEs.  Under the random policy the armies first meet after
@@ -81,15 +81,10 @@ def call_edges(calls):
 
 def _state(dump):
     """dump -> (time, {(x, y): (type, player)}, [(x, y, action type, parameter, issue time)])"""
-    d = [int(v) for v in dump]
-    nu = d[4]
-    units = [d[5 + 6 * k:11 + 6 * k] for k in range(nu)]
-    base = 5 + 6 * nu
-    acts = []
-    for k in range(d[base]):
-        u, t, par, _x, _y, _ut, when = d[base + 1 + 7 * k:base + 8 + 7 * k]
-        acts.append((units[u][2], units[u][3], t, par, when))
-    return d[0], {(u[2], u[3]): (u[0], u[1]) for u in units}, acts
+    time, _, units, assign = dumps.parse(dump)
+    units = units.tolist()
+    acts = [(units[u][2], units[u][3], t, par, when) for u, t, par, _x, _y, _ut, when in assign.tolist()]
+    return time, {(u[2], u[3]): (u[0], u[1]) for u in units}, acts
 
 
 def _young(t, when, now):

@@ -2,20 +2,14 @@
 declares; the Python mirror validates its arguments (no GPU compute is called here)."""
 import ctypes
 import os
-import re
 
 import pytest
 
 from microrts_amd import _lib
 from microrts_amd.vec_client import UnitTypeTable, _check_rfs, _bot_kind
+from tests.headers import header_symbols
 
 ROOT = os.path.dirname(os.path.dirname(os.path.abspath(__file__)))
-
-
-def header_symbols():
-    txt = open(os.path.join(ROOT, "include", "mrts.h")).read()
-    txt = re.sub(r"/\*.*?\*/", "", txt, flags=re.S)
-    return sorted(set(re.findall(r"\b(mrts_[a-z0-9_]+)\s*\(", txt)))
 
 
 def test_header_matches_python_exports():

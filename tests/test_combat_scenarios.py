@@ -7,7 +7,7 @@ census of the suite's older rollouts, which reach none of this, is in DESIGN.md.
 import pytest
 
 from tests import combat_maps as C
-from tests.test_kats import HEAVY, LIGHT, RANGED
+from tests.defs import HEAVY, LIGHT, RANGED
 
 
 @pytest.mark.parametrize("sc", C.ROLLOUTS, ids=[s["id"] for s in C.ROLLOUTS])

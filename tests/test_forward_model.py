@@ -11,22 +11,21 @@ oracle bit for bit (state dumps, float32 evaluations) through the C ABI."""
 import numpy as np
 import pytest
 
-from tests import oracle_py
+from tests import dumps, oracle_py
+from tests.defs import COST, HP, SEED
+from tests.gpu_checks import PASSIVE, RB
+from tests.gpu_checks import fm_compare as _compare, fm_mixed as _mixed
+from tests.gpu_support import torch_gpu
 
-RB, PASSIVE = oracle_py.BOT_RANDOM_BIASED, oracle_py.BOT_PASSIVE
 M8 = "maps/8x8/basesWorkers8x8.xml"
 M16 = "maps/16x16/basesWorkers16x16.xml"
 M4 = "maps/4x4/base4x4.xml"
-# UnitTypeTable VERSION_ORIGINAL (rts/units/UnitTypeTable.java:111-259): type id -> (cost, hp)
-UTT1 = {0: (1, 1), 1: (10, 10), 2: (5, 4), 3: (1, 1), 4: (2, 4), 5: (2, 4), 6: (2, 1)}
 
 
 def eval_from_dump(d, maxplayer):
     """numpy restatement of SimpleSqrtEvaluationFunction3 over a canonical state dump."""
     f32, f64 = np.float32, np.float64
-    res = [int(d[2]), int(d[3])]
-    nu = int(d[4])
-    units = np.asarray(d[5:5 + 6 * nu]).reshape(nu, 6)
+    _, res, units, _ = dumps.parse(d)
 
     def base(p):
         score = f32(res[p]) * f32(20)
@@ -36,7 +35,7 @@ def eval_from_dump(d, maxplayer):
                 continue
             any_unit = True
             score = f32(score + f32(r) * f32(10))
-            cost, mhp = UTT1[int(t)]
+            cost, mhp = COST[int(t)], HP[int(t)]  # UnitTypeTable VERSION_ORIGINAL
             bonus = f64(f32(40.0) * f32(cost)) * np.sqrt(f64(int(hp) // mhp))
             score = f32(f64(score) + bonus)
         return score if any_unit else f32(0)
@@ -60,7 +59,7 @@ def test_clone_reproduces_source():
     fm = oracle_py.OracleForwardModel(4, M8, RB, RB, seed=11)
     fm.playout(0, 37)  # mid-game, with in-flight assignments
     d0 = fm.dump(0)
-    assert d0[5 + 6 * d0[4]] > 0, "want assignments in the cloned state"
+    assert dumps.n_assign(d0) > 0, "want assignments in the cloned state"
     fm.copy(1, 0)
     assert np.array_equal(fm.dump(1), d0)
     # same state + same seeds -> same continuation; the clone is independent of its source
@@ -93,49 +92,24 @@ def test_playout_loop_exits():
     # horizon 0 on an incomplete state: the do-while issues once and stops before the cycle
     fm.playout(0, 0)
     d = fm.dump(0)
-    assert d[0] == 0 and d[5 + 6 * d[4]] > 0
+    assert d[0] == 0 and dumps.n_assign(d) > 0
     # then the next call cycles first (the state is complete)
     fm.playout(0, 1)
     assert fm.dump(0)[0] == 1
     # a long horizon ends at gameover (base4x4 RandomBiased games finish)
     fm.playout(1, 20000)
     d = fm.dump(1)
-    owners = set(int(p) for p in np.asarray(d[5:5 + 6 * d[4]]).reshape(-1, 6)[:, 1]) - {-1}
+    owners = set(int(p) for p in dumps.live_units(d)[:, 1]) - {-1}
     assert len(owners) <= 1 and d[0] < 20000
 
 
 # ------------------------------------------------------------------ GPU: HIP forward model vs oracle
 
 
-def _torch():
-    import torch
-
-    assert torch.cuda.is_available()
-    return torch
-
-
-def _mixed(n):
-    ai1 = [RB, RB, PASSIVE, RB] * (n // 4)
-    ai2 = [RB, PASSIVE, RB, RB] * (n // 4)
-    name = {RB: "RandomBiasedAI", PASSIVE: "PassiveAI"}
-    return ai1, ai2, [name[k] for k in ai1], [name[k] for k in ai2]
-
-
-def _compare(gpu, ref, n, tag, evals=True):
-    for g in range(n):
-        assert np.array_equal(gpu.dump_state(g), ref.dump(g)), f"{tag}: state of game {g}"
-    if evals:
-        for mp in (0, 1):
-            v = gpu.evaluate(mp).cpu().numpy()
-            for g in range(n):
-                assert v[g] == ref.evaluate(g, mp), f"{tag}: evaluation of game {g} for player {mp}"
-    assert not gpu.error_flags().any()
-
-
 @pytest.mark.gpu
 @pytest.mark.parametrize("mp", [M8, M16])
 def test_gpu_playouts_match_oracle(mp):
-    _torch()
+    torch_gpu()
     from microrts_amd import ForwardModel
 
     n = 16
@@ -153,7 +127,7 @@ def test_gpu_playouts_match_oracle(mp):
 
 @pytest.mark.gpu
 def test_gpu_clone_within_forward_model():
-    torch = _torch()
+    torch = torch_gpu()
     from microrts_amd import ForwardModel
 
     n = 16
@@ -183,7 +157,7 @@ def test_gpu_clone_within_forward_model():
 def test_gpu_clone_from_vec_env_then_playout():
     """MCTS use: clone the live self-play games of a DeviceVecEnv (stepped with the Philox policy in
     lockstep with the oracle VecClient), then run playouts from those roots."""
-    torch = _torch()
+    torch = torch_gpu()
     from microrts_amd import DeviceVecEnv, ForwardModel
 
     S = 8
@@ -191,10 +165,9 @@ def test_gpu_clone_from_vec_env_then_playout():
     vref = oracle_py.OracleVecClient(S, 0, 2000, [M8] * S, seed=17)
     env.reset()
     vref.reset()
-    seed = 0x5EEDC0DE
     for step in range(60):
         m = vref.get_masks(0)
-        acts = np.stack([oracle_py.policy(m[s], seed, s, step, 0) for s in range(S)])
+        acts = np.stack([oracle_py.policy(m[s], SEED, s, step, 0) for s in range(S)])
         env.actions.copy_(torch.as_tensor(acts))
         env.step()
         vref.step(acts)
@@ -216,7 +189,7 @@ def test_gpu_clone_from_vec_env_then_playout():
 
 @pytest.mark.gpu
 def test_gpu_playout_to_gameover_and_argument_checks():
-    _torch()
+    torch_gpu()
     from microrts_amd import DeviceVecEnv, ForwardModel
 
     n = 8
@@ -251,7 +224,7 @@ def test_gpu_playout_to_gameover_and_argument_checks():
 def test_gpu_full_size_playouts_deterministic():
     """4096 games of 16x16 with NaiveMCTS's default lookahead (MAXSIMULATIONTIME = 1024): clones of
     one root replay identically when their streams are identical, a sample matches the oracle."""
-    torch = _torch()
+    torch = torch_gpu()
     from microrts_amd import ForwardModel
 
     n = 4096

@@ -30,12 +30,12 @@ import numpy as np
 import pytest
 
 from tests import oracle_py
-from tests.test_full_size_every_game import _threads
-from tests.test_gpu_parity import _encode_obs_np
+from tests.defs import SEED
+from tests.gpu_checks import encode_obs_np, oracle_threads
+from tests.gpu_support import torch_gpu
 
 pytestmark = pytest.mark.gpu
 
-SEED = 0x5EEDC0DE
 WORLD, RANK = 8, 3
 BURN = 1000
 CALLS = (20, 200, 1040)
@@ -55,9 +55,7 @@ def _checked_steps(n):
 
 
 def _gpu_run(cfg):
-    import torch
-
-    assert torch.cuda.is_available(), "GPU tests need an MI355X"
+    torch = torch_gpu()
     from microrts_amd import DeviceVecEnv
 
     mp, G, po, mu, seed, units = SHAPES[cfg]
@@ -158,7 +156,7 @@ def _shard(cfg, g0, g1, points):
                 js, twin, got = oh
                 mine = np.nonzero((js == j) & (twin >= 2 * g0) & (twin < 2 * g1))[0]
                 if len(mine):
-                    want = _encode_obs_np(ref.obs[twin[mine] - 2 * g0])
+                    want = encode_obs_np(ref.obs[twin[mine] - 2 * g0])
                     for i, w in zip(mine, want):
                         if not np.array_equal(got[i], w):
                             bad["one-hot sample"] = bad.get("one-hot sample", 0) + 1
@@ -184,7 +182,7 @@ def _loopback_full_size(cfg):
     points = _gpu_run(cfg)
     print(f"{cfg}: GPU rollout + renders {time.time() - t0:.1f} s; oracle replicas next", flush=True)
     G = SHAPES[cfg][1]
-    nt = _threads()
+    nt = oracle_threads()
     step = (G + nt - 1) // nt
     bad, ex, nsamp = {}, [], 0
     with cf.ThreadPoolExecutor(nt) as pool:  # the oracle steps in native code with the GIL released

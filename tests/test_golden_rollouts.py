@@ -8,6 +8,7 @@ import os
 import numpy as np
 import pytest
 
+from tests.gpu_support import torch_gpu
 from tests import oracle_py
 from tests.golden import rollouts as R
 
@@ -42,9 +43,7 @@ def test_oracle_reproduces_bot_only_fixture():
 @pytest.mark.gpu
 @pytest.mark.parametrize("name", NAMES)
 def test_gpu_replays_fixture(name):
-    import torch
-
-    assert torch.cuda.is_available()
+    torch = torch_gpu()
     from microrts_amd import DeviceVecEnv
 
     fx = _load(name)
@@ -81,9 +80,7 @@ def test_gpu_replays_fixture(name):
 
 @pytest.mark.gpu
 def test_gpu_replays_bot_only_fixture():
-    import torch
-
-    assert torch.cuda.is_available()
+    torch_gpu()
     from microrts_amd import DeviceVecEnv
 
     fx = _load("c1_bot_only_4x4")

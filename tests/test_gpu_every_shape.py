@@ -20,7 +20,7 @@ than 64 units.  max_steps lies below the stepped horizon, so every game also res
   They are compared with what defines them, the oracle's step_rows over the same list: B and the oracle
   take the states once more and step REVERSED_STEPS times on reversed rows;
 * the one-hot encoder on A's observation half-way to the reset and on its last one, against the numpy
-  restatement of tests.test_gpu_parity.
+  restatement of tests.gpu_checks.
 """
 import json
 
@@ -29,8 +29,8 @@ import pytest
 
 from tests import oracle_py, policy_head_ref
 from tests import state_cases as SC
-from tests.test_gpu_parity import _encode_obs_np, _torch
-from tests.test_state_json import dump_xy_free
+from tests.gpu_checks import encode_obs_np
+from tests.gpu_support import assert_matches_oracle, same, torch_gpu
 
 pytestmark = pytest.mark.gpu
 
@@ -38,37 +38,25 @@ SEED = SC.SEED
 REVERSED_STEPS = 4
 
 
-def _same(torch, name, got, want, tag):
-    """got (device tensor) == want (numpy array or device tensor), compared on the device."""
-    w = want if isinstance(want, torch.Tensor) else torch.as_tensor(want, device=got.device)
-    if got.shape == w.shape and got.dtype == w.dtype and torch.equal(got, w):
-        return
-    g, h = got.cpu().numpy(), w.cpu().numpy()
-    assert g.shape == h.shape and g.dtype == h.dtype, f"{tag}: {name} {g.dtype}{g.shape} vs {h.dtype}{h.shape}"
-    bad = np.argwhere(g != h)
-    raise AssertionError(f"{tag}: {name} differs at {len(bad)} places, first {bad[0].tolist()}: "
-                         f"gpu {g[tuple(bad[0])]} ref {h[tuple(bad[0])]}")
-
-
 def _inject(handle, states, stride):
     for g, j in enumerate(states):
         handle.set_state_json(stride * g, j)
 
 
-def _check_injected(torch, A, ref, tag):
+def _check_injected(A, ref, tag):
     """After the injection, before any step: A's masks (both players' views in self-play) and source bits."""
     A.get_masks()
     m = ref.get_masks(0)
-    _same(torch, "masks", A.masks, m, f"{tag} injected")
-    _same(torch, "source bits", A.source, policy_head_ref.source_bits(m.reshape(ref.S, -1, ref.K)), f"{tag} injected")
+    same(A.masks, m, "masks", f"{tag} injected")
+    same(A.source, policy_head_ref.source_bits(m.reshape(ref.S, -1, ref.K)), "source bits", f"{tag} injected")
     return m
 
 
-def _check_onehot(torch, A, po, tag):
+def _check_onehot(A, po, tag):
     got = A.onehot_obs()
-    want = _encode_obs_np(A.obs.cpu().numpy())
+    want = encode_obs_np(A.obs.cpu().numpy())
     assert got.shape == want.shape and got.shape[-1] == (33 if po else 29)
-    _same(torch, "one-hot observation", got, want, tag)
+    same(got, want, "one-hot observation", tag)
 
 
 def _make(c, po, bots, **kw):
@@ -90,9 +78,10 @@ def _oracle(c, po, bots):
 
 
 def _run(c, po, bots=False):
-    torch = _torch()
+    torch = torch_gpu()
     tag = f"{c['size'][1]}x{c['size'][0]}{' po' if po else ''}{' bots' if bots else ''}"
     stride = 1 if bots else 2
+    every = "all" if bots else "even"  # the slots whose state is compared: one per game
     players = c.get("players") if bots else None
     A = _make(c, po, bots)
     twins = [] if bots else [_make(c, po, bots, mask_delta=False, obs_delta=False, source_bits=False), _make(c, po, bots)]
@@ -106,7 +95,7 @@ def _run(c, po, bots=False):
         _inject(e, c["states"], stride)
     ref.reset(players)
     _inject(ref, c["states"], stride)
-    _check_injected(torch, A, ref, tag)
+    _check_injected(A, ref, tag)
     for e in twins:
         e.get_masks()
     if twins:
@@ -122,7 +111,7 @@ def _run(c, po, bots=False):
         for s in range(min(S, 8)):
             assert np.array_equal(acts[s], oracle_py.policy(m[s], SEED, s, step, 0)), f"{at}: policy rows of slot {s}"
         if twins:
-            _same(torch, "C's fused policy rows", C.actions, A.actions, at)
+            same(C.actions, A.actions, "C's fused policy rows", at)
             if step % 2:
                 B.step_rows(torch.cat([pos, A.actions], dim=2).contiguous())
             else:
@@ -131,40 +120,29 @@ def _run(c, po, bots=False):
         A.step()
         ref.step(acts, players)  # raises what Java would throw
         dones += int(ref.done.sum())
-        _same(torch, "obs", A.obs, ref.obs, at)
-        _same(torch, "reward", A.reward, ref.reward, at)
-        _same(torch, "done", A.done, ref.done, at)
-        _same(torch, "masks", A.masks, ref.get_masks(0), at)
+        assert_matches_oracle(A, ref, at, states=every if step % 5 == 4 else None, xy_free=True)
         for name, e in zip(("B", "C"), twins):
             for what in ("obs", "masks", "reward", "done"):
-                _same(torch, f"{name}.{what} vs A", getattr(e, what), getattr(A, what), at)
-        if step % 5 == 4:
-            for s in range(0, S, stride):
-                assert np.array_equal(dump_xy_free(A.dump_state(s)), dump_xy_free(ref.dump(s))), f"{at}: state of slot {s}"
+                same(getattr(e, what), getattr(A, what), f"{name}.{what} vs A", at)
         if step == c["max_steps"] // 2:  # the crowd is still on the map
-            _check_onehot(torch, A, po, at)
+            _check_onehot(A, po, at)
     assert dones >= S, f"{tag}: not every game reset inside a step ({dones} dones, {S} slots)"
-    _check_onehot(torch, A, po, tag)
+    _check_onehot(A, po, tag)
     if twins:
         A.random_policy(SEED, c["steps"])
-        _same(torch, "C's fused policy rows", C.actions, A.actions, f"{tag} after the last step")
+        same(C.actions, A.actions, "C's fused policy rows", f"{tag} after the last step")
         # reversed Java rows, against the oracle's step_rows from the same states
         _inject(B, c["states"], stride)
         _inject(ref, c["states"], stride)
         B.get_masks()
-        _same(torch, "masks", B.masks, ref.get_masks(0), f"{tag} injected again")
+        same(B.masks, ref.get_masks(0), "masks", f"{tag} injected again")
         for k in range(REVERSED_STEPS):
             at = f"{tag} reversed rows step {k}"
             B.random_policy(SEED, 1000 + k)
             rows = torch.cat([pos, B.actions], dim=2).flip(1).contiguous()
             B.step_rows(rows)
             ref.step_rows(rows.cpu().numpy())
-            _same(torch, "obs", B.obs, ref.obs, at)
-            _same(torch, "reward", B.reward, ref.reward, at)
-            _same(torch, "done", B.done, ref.done, at)
-            _same(torch, "masks", B.masks, ref.get_masks(0), at)
-        for s in range(0, S, stride):
-            assert np.array_equal(dump_xy_free(B.dump_state(s)), dump_xy_free(ref.dump(s))), f"{tag} reversed rows: slot {s}"
+            assert_matches_oracle(B, ref, at, states=every if k == REVERSED_STEPS - 1 else None, xy_free=True)
     for name, e in zip("ABC", [A] + twins):
         assert not e.error_flags().any(), f"{tag}: error flags of {name}: {e.error_flags()}"
         e.close()
@@ -192,7 +170,7 @@ def test_outputs_against_bots(size):
 def test_a_shifted_unit_is_noticed():
     """The comparison is not vacuous: on 128x96, one crowd unit moved by one cell in the oracle's copy
     alone makes the mask comparison fail before any step."""
-    torch = _torch()
+    torch_gpu()
     c = SC.case((96, 128))
     g = c["crowded"].index(True)
     d = json.loads(c["states"][g])
@@ -215,8 +193,8 @@ def test_a_shifted_unit_is_noticed():
     _inject(A, c["states"], 2)
     _inject(ref, shifted, 2)
     with pytest.raises(AssertionError, match="masks differs"):
-        _check_injected(torch, A, ref, "shifted")
+        _check_injected(A, ref, "shifted")
     _inject(ref, c["states"], 2)
-    _check_injected(torch, A, ref, "unshifted")
+    _check_injected(A, ref, "unshifted")
     A.close()
     ref.close()

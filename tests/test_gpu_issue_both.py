@@ -14,24 +14,16 @@ import sys
 import numpy as np
 import pytest
 
-from tests import oracle_py
+from tests import dumps, oracle_py
+from tests.defs import BASE, DOWN, DX, DY, LEFT, RIGHT, SEED, UP, WORKER, write_map
+from tests.defs import MOVE as T_MOVE, PRODUCE as T_PRODUCE
+from tests.gpu_checks import FUSED_MAP, flag_rollout
+from tests.gpu_support import assert_matches_oracle, assert_same_outputs, torch_gpu
 
 pytestmark = pytest.mark.gpu
 
 ROOT = os.path.dirname(os.path.dirname(os.path.abspath(__file__)))
-SEED = 0x5EEDC0DE
-T_NONE, T_MOVE, T_HARVEST, T_RETURN, T_PRODUCE, T_ATTACK = range(6)
-UP, RIGHT, DOWN, LEFT = range(4)
-DX, DY = (0, 1, 0, -1), (-1, 0, 1, 0)
-WORKER = 3  # UnitTypeTable v1: Resource, Base, Barracks, Worker, Light, Heavy, Ranged
 E_PRODUCE_TYPE = 1 << 2
-
-
-def _torch():
-    import torch
-
-    assert torch.cuda.is_available(), "GPU tests need an MI355X"
-    return torch
 
 
 # The scenarios' map (the reference's XML layout, PhysicalGameState.java:700-726), within the top-left 8x8
@@ -43,22 +35,13 @@ def _torch():
 #   3                        B1
 #   4      A1    Q     T
 #   6         R     U     B0
-UNITS = {"A0": ("Base", 0, 1, 1), "A1": ("Base", 0, 1, 4), "P": ("Worker", 0, 3, 2), "Q": ("Worker", 0, 3, 4),
-         "R": ("Worker", 0, 2, 6), "B0": ("Base", 1, 6, 6), "B1": ("Base", 1, 7, 3), "S": ("Worker", 1, 5, 2),
-         "T": ("Worker", 1, 5, 4), "U": ("Worker", 1, 4, 6)}
+UNITS = {"A0": (BASE, 0, 1, 1), "A1": (BASE, 0, 1, 4), "P": (WORKER, 0, 3, 2), "Q": (WORKER, 0, 3, 4),
+         "R": (WORKER, 0, 2, 6), "B0": (BASE, 1, 6, 6), "B1": (BASE, 1, 7, 3), "S": (WORKER, 1, 5, 2),
+         "T": (WORKER, 1, 5, 4), "U": (WORKER, 1, 4, 6)}
 
 
 def _write_map(tmp_path, size):
-    units = "".join(f'    <rts.units.Unit type="{t}" ID="{10 + i}" player="{p}" x="{x}" y="{y}" resources="0" '
-                    f'hitpoints="{10 if t == "Base" else 1}" >\n    </rts.units.Unit>\n'
-                    for i, (t, p, x, y) in enumerate(UNITS.values()))
-    text = (f'<rts.PhysicalGameState width="{size}" height="{size}">\n  <terrain>{"0" * (size * size)}</terrain>\n'
-            '  <players>\n    <rts.Player ID="0" resources="1">\n    </rts.Player>\n'
-            '    <rts.Player ID="1" resources="5">\n    </rts.Player>\n  </players>\n  <units>\n'
-            f'{units}  </units>\n</rts.PhysicalGameState>\n')
-    path = tmp_path / f"issue_both{size}x{size}.xml"
-    path.write_text(text)
-    return str(path)
+    return write_map(tmp_path / f"issue_both{size}x{size}.xml", size, size, list(UNITS.values()), res=(1, 5))
 
 
 def _row(kind, d=0, ut=0):
@@ -72,7 +55,7 @@ def _row(kind, d=0, ut=0):
 
 MOVE = lambda d: _row(T_MOVE, d)  # noqa: E731
 PROD = lambda d, ut=WORKER: _row(T_PRODUCE, d, ut)  # noqa: E731
-NONE = _row(T_NONE)
+NONE = _row(0)
 
 # scenario -> the scripted steps: {unit: row}; units left out get a NONE row
 SCENARIOS = {
@@ -95,19 +78,6 @@ SCENARIOS = {
 }
 
 
-def _parse_dump(d):
-    """ref_cpu dumpState: time, players + resources, units (type, player, x, y, hp, resources), assignments in
-    insertion order (unit index, type, parameter, x, y, unit type, time)."""
-    npl = int(d[1])
-    o = 2 + npl
-    nu = int(d[o])
-    units = np.asarray(d[o + 1:o + 1 + 6 * nu]).reshape(nu, 6)
-    o += 1 + 6 * nu
-    na = int(d[o])
-    asg = np.asarray(d[o + 1:o + 1 + 7 * na]).reshape(na, 7)
-    return units, asg
-
-
 def _scripted_actions(S, size, step_rows):
     acts = np.zeros((S, size * size, 7), np.int32)
     for name, row in step_rows.items():
@@ -117,26 +87,17 @@ def _scripted_actions(S, size, step_rows):
 
 
 def _assert_same(env, ref, tag):
-    env.synchronize()
-    assert np.array_equal(env.obs.cpu().numpy(), ref.obs), f"{tag}: observations"
-    assert np.array_equal(env.reward.cpu().numpy(), ref.reward), f"{tag}: rewards"
-    assert np.array_equal(env.done.cpu().numpy(), ref.done), f"{tag}: dones"
-    assert np.array_equal(env.masks.cpu().numpy(), ref.get_masks(0)), f"{tag}: masks"
-    for s in range(0, ref.S, 2):
-        a, b = env.dump_state(s), ref.dump(s)
-        assert np.array_equal(a, b), f"{tag}: state of slot {s}\n gpu {a.tolist()}\n ref {b.tolist()}"
+    assert_matches_oracle(env, ref, tag, states="even")
 
 
 def _assignment_of(ref, name):
     """(type, parameter, insertion index) of the unit's assignment in the oracle's game 0, or None"""
-    units, asg = _parse_dump(ref.dump(0))
+    d = ref.dump(0)
     _, p, x, y = UNITS[name]
-    idx = [i for i, u in enumerate(units) if (u[1], u[2], u[3]) == (p, x, y)]
+    idx = [i for i, u in enumerate(dumps.live_units(d)) if (u[1], u[2], u[3]) == (p, x, y)]
     assert len(idx) == 1, f"{name} is not where the map put it"
-    for k, a in enumerate(asg):
-        if a[0] == idx[0]:
-            return int(a[1]), int(a[2]), k
-    return None
+    held = dumps.assignment_of(d, idx[0])
+    return held and (int(held[0][1]), int(held[0][2]), held[1])
 
 
 def _oracle_scripted_step(ref, acts, step_rows, size):
@@ -193,7 +154,7 @@ def test_directed_steps(tmp_path, scenario, size):
     issueSafe's legality test on — then 20 masked-random steps, on 4 games; every step against the oracle.
     The oracle's own state asserts what the scenario is for (who was accepted, who was filled), so the
     comparison cannot pass on a scenario that does not happen."""
-    torch = _torch()
+    torch = torch_gpu()
     from microrts_amd import DeviceVecEnv
 
     S = 8
@@ -228,7 +189,7 @@ def _clash(dump, rows0, rows1, W):
     """Does this game-step keep the merged pass from being taken on positions: two candidate rows (idle units'
     MOVE / PRODUCE rows, either player) with one target cell, or one targeting a cell an assignment in flight
     has reserved?  From the oracle's state before the step and the step's rows."""
-    units, asg = _parse_dump(dump)
+    _, _, units, asg = dumps.parse(dump)
     busy = {int(a[0]) for a in asg}
     taken = set()
     for a in asg:
@@ -248,7 +209,6 @@ def _clash(dump, rows0, rows1, W):
     return False
 
 
-FUSED_MAP = "maps/16x16/basesWorkers16x16.xml"
 FUSED_LAUNCHES = (1, 3, 40, 57, 2, 97, 64, 136)  # 400 steps
 FUSED_SEED = 5
 
@@ -259,7 +219,7 @@ def test_fused_multi_step_rollout():
     step and against the oracle at every launch boundary (outputs, next rows, every game's state).  The
     oracle's side asserts that the rollout holds at least 20 game-steps with a target clash among the candidate
     rows or with a reservation in flight, so both the merged pass and the per-player passes ran."""
-    torch = _torch()
+    torch_gpu()
     from microrts_amd import DeviceVecEnv
 
     S = 64
@@ -288,50 +248,16 @@ def test_fused_multi_step_rollout():
             ref.step(acts)
         k += n
         tag = f"after the launch to step {k}"
-        A.synchronize()
-        B.synchronize()
-        for name in ("obs", "reward", "done", "masks", "actions", "source"):
-            assert torch.equal(getattr(A, name), getattr(B, name)), f"{name} {tag}: multi-step vs one launch per step"
-        assert np.array_equal(A._h.env_steps(), B._h.env_steps()), f"env steps {tag}"
+        assert_same_outputs(A, B, f"{tag}: one launch per step vs multi-step")
         m = ref.get_masks(0)
         nxt = np.stack([oracle_py.policy(m[s], SEED, s, k, 0) for s in range(S)])
-        assert np.array_equal(B.obs.cpu().numpy(), ref.obs), f"{tag}: observations"
-        assert np.array_equal(B.reward.cpu().numpy(), ref.reward), f"{tag}: rewards"
-        assert np.array_equal(B.done.cpu().numpy(), ref.done), f"{tag}: dones"
-        assert np.array_equal(B.masks.cpu().numpy(), m), f"{tag}: masks"
-        assert np.array_equal(B.actions.cpu().numpy(), nxt), f"{tag}: next action rows"
-        for s in range(0, S, 2):
-            d = ref.dump(s)
-            assert np.array_equal(B.dump_state(s), d), f"{tag}: state of slot {s}"
-            assert np.array_equal(A.dump_state(s), d), f"{tag}: state of slot {s} (one launch per step)"
+        assert_matches_oracle(B, ref, tag, next_rows=nxt, states="even")
+        assert_matches_oracle(A, ref, f"{tag} (one launch per step)", masks=None, rewards=None, states="even")
     assert clashes >= 20 and clean >= 20, (clashes, clean)
     assert not A.error_flags().any() and not B.error_flags().any()
     A.close()
     B.close()
     ref.close()
-
-
-def _flag_rollout(out):
-    """A 16x16 fused rollout of 200 steps; everything it leaves, to `out` (.npz)"""
-    _torch()
-    from microrts_amd import DeviceVecEnv
-
-    S = 32
-    env = DeviceVecEnv(S, 0, 2000, [FUSED_MAP] * S, seed=9)
-    env.reset()
-    env.random_policy(SEED, 0)
-    res, k = {}, 0
-    for n in (1, 19, 80, 100):
-        env.rollout_fused(SEED, k + 1, n)
-        k += n
-        env.synchronize()
-        for name in ("obs", "masks", "actions", "reward", "done"):
-            res[f"{name}_{k}"] = getattr(env, name).cpu().numpy()
-        for s in range(0, S, 2):
-            res[f"state_{k}_{s}"] = env.dump_state(s)
-    res["flags"] = env.error_flags()
-    env.close()
-    np.savez(out, **res)
 
 
 def test_flag_off_equals_flag_on(tmp_path):
@@ -347,10 +273,10 @@ def test_flag_off_equals_flag_on(tmp_path):
         pytest.skip("this session's own library is the variant")
     off, on = str(tmp_path / "off.npz"), str(tmp_path / "on.npz")
     env = dict(os.environ, MRTS_LIB_PATH=x1)
-    r = subprocess.run([sys.executable, "-c", f"from tests.test_gpu_issue_both import _flag_rollout; _flag_rollout({off!r})"],
+    r = subprocess.run([sys.executable, "-c", f"from tests.gpu_checks import flag_rollout; flag_rollout({off!r})"],
                        cwd=ROOT, env=env, capture_output=True, text=True, timeout=120)
     assert r.returncode == 0, r.stderr
-    _flag_rollout(on)
+    flag_rollout(on)
     a, b = np.load(off), np.load(on)
     assert sorted(a.files) == sorted(b.files)
     for name in a.files:

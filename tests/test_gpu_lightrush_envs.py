@@ -7,6 +7,9 @@ import struct
 import numpy as np
 import pytest
 
+from tests import dumps
+from tests.gpu_support import torch_gpu
+
 pytestmark = pytest.mark.gpu
 
 ROOT = os.path.dirname(os.path.dirname(os.path.abspath(__file__)))
@@ -15,21 +18,10 @@ M16 = os.path.join(ROOT, "maps/16x16/basesWorkers16x16.xml")
 
 
 def _env(*a, **k):
-    import torch
-
-    assert torch.cuda.is_available(), "GPU tests need an MI355X"
+    torch_gpu()
     from microrts_amd import DeviceVecEnv
 
     return DeviceVecEnv(*a, **k)
-
-
-def _parse(d):
-    """dump_state -> (time, resources, units [n][6], assignments [(unit, type, parameter, tx, ty, unit type, time)])"""
-    nu = int(d[4])
-    units = d[5:5 + 6 * nu].reshape(-1, 6)
-    na = int(d[5 + 6 * nu])
-    asg = d[6 + 6 * nu:6 + 6 * nu + 7 * na].reshape(-1, 7)
-    return int(d[0]), (int(d[2]), int(d[3])), units, asg
 
 
 @pytest.mark.parametrize("side", [0, 1])
@@ -58,8 +50,8 @@ def test_agent_vs_lightrush_equals_the_bot_only_path(side):
         lr = 1 - side
         history, ends = [], []
         for k in range(steps + 1):
-            ta, ra, ua, aa = _parse(agent.dump_state(0))
-            tb, rb, ub, ab = _parse(bots.dump_state(0))
+            ta, ra, ua, aa = dumps.parse(agent.dump_state(0))
+            tb, rb, ub, ab = dumps.parse(bots.dump_state(0))
             tag = f"step {k}"
             assert (ta, ra) == (tb, rb), f"{tag}: time / resources {(ta, ra)} vs {(tb, rb)}"
             assert np.array_equal(ua, ub), f"{tag}: units differ"
@@ -180,7 +172,7 @@ def test_lightrush_game_leaves_the_other_games_of_its_handle_alone():
             if k % 10 == 9:
                 for s in range(3):
                     assert np.array_equal(a.dump_state(s), b.dump_state(s)), f"{tag}: state of slot {s}"
-        t, _, units, asg = _parse(a.dump_state(3))
+        t, _, units, asg = dumps.parse(a.dump_state(3))
         assert t == steps and len(asg) > 0  # the LightRush environment ran beside them
         assert not a.error_flags().any() and not b.error_flags().any()
     finally:
@@ -207,7 +199,7 @@ def test_evaluate_and_copy_read_the_longer_blocks():
         env.synchronize()
         fm.copy_from([[g, g] for g in range(n)], src=env)
         for g in range(n):
-            a, b = _parse(env.dump_state(g)), _parse(fm.dump_state(g))
+            a, b = dumps.parse(env.dump_state(g)), dumps.parse(fm.dump_state(g))
             assert a[:2] == b[:2] and np.array_equal(a[2], b[2]) and np.array_equal(a[3], b[3]), f"copy of game {g}"
         seen = []
         for maxplayer in (0, 1):

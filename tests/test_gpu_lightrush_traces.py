@@ -21,6 +21,7 @@ import os
 import numpy as np
 import pytest
 
+from tests.gpu_support import torch_gpu
 from tests.trace_fixtures import GROUPS, IDX, ROOT, SIZES, TR, check_vs_trace, parse
 
 pytestmark = pytest.mark.gpu
@@ -55,9 +56,7 @@ def _survivor_reward(units):
 def _run(group, ai1, ai2, stop_at_mismatch=False):
     """Play the group's maps bot against bot and compare with the traces.  Returns the number of entries compared
     (or, with stop_at_mismatch, the (game, entry index) of the first entry that differs, None if none does)."""
-    import torch
-
-    assert torch.cuda.is_available(), "GPU tests need an MI355X"
+    torch_gpu()
     from microrts_amd import DeviceVecEnv
 
     n = len(group)

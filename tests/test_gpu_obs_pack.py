@@ -13,6 +13,7 @@ import numpy as np
 import pytest
 
 from tests import obs_pack_ref as OR
+from tests.gpu_support import ptr, torch_gpu
 
 pytestmark = pytest.mark.gpu
 
@@ -29,29 +30,18 @@ CASES = {
 }
 
 
-def _torch():
-    import torch
-
-    assert torch.cuda.is_available(), "GPU tests need an MI355X"
-    return torch
-
-
-def _p(t):
-    return ctypes.c_void_p(t.data_ptr()) if t is not None else None
-
-
 def _np32(t):
-    return t.cpu().view(_torch().int32).numpy().view(np.uint32)
+    return t.cpu().view(torch_gpu().int32).numpy().view(np.uint32)
 
 
 def _u32(a, device):
     """a numpy uint32 array as a uint32 tensor on the device"""
-    torch = _torch()
+    torch = torch_gpu()
     return torch.from_numpy(np.ascontiguousarray(a).view(np.int32)).to(device).view(torch.uint32)
 
 
 def _filled(shape, device, word=0xDEADBEEF):
-    torch = _torch()
+    torch = torch_gpu()
     return torch.full(shape, word - (1 << 32) if word >> 31 else word, dtype=torch.int32, device=device).view(torch.uint32)
 
 
@@ -68,7 +58,7 @@ class Case:
     """one shape: a rollout whose every step is kept packed (cap = H*W), as int32 planes and one-hot"""
 
     def __init__(self, name):
-        torch = _torch()
+        torch = torch_gpu()
         from microrts_amd import DeviceVecEnv
 
         path, po, steps = CASES[name]
@@ -91,7 +81,7 @@ class Case:
 
     def dense_onehot(self, obs):
         """onehot_obs (the dense kernel) of any number of rows, S at a time"""
-        torch = _torch()
+        torch = torch_gpu()
         n = obs.shape[0]
         pad = torch.cat([obs, obs.new_zeros(((-n) % S,) + tuple(obs.shape[1:]))]).contiguous()
         return torch.cat([self.env.onehot_obs(obs=pad[i:i + S]) for i in range(0, pad.shape[0], S)])[:n]
@@ -124,7 +114,7 @@ def test_packed_words_equal_the_numpy_packer(case):
 
 
 def test_readers_give_back_what_the_network_saw(case):
-    torch = _torch()
+    torch = torch_gpu()
     env = case.env
     assert torch.equal(env.unpack_obs(case.buf).reshape(case.obs.shape), case.obs)
     assert torch.equal(env.onehot_packed(case.buf).reshape(case.hot.shape), case.hot)
@@ -143,7 +133,7 @@ def test_readers_give_back_what_the_network_saw(case):
 
 
 def test_default_cap_holds_a_16x16_rollout():
-    torch = _torch()
+    torch = torch_gpu()
     from microrts_amd import DeviceVecEnv
 
     env = DeviceVecEnv(S, 0, 2000, [CASES["16x16"][0]] * S, seed=3)
@@ -163,7 +153,7 @@ def test_default_cap_holds_a_16x16_rollout():
 
 
 def test_synthetic_rows_through_all_three_kernels(case):
-    torch = _torch()
+    torch = torch_gpu()
     env, H, W, C, HW = case.env, case.H, case.W, case.C, case.HW
     syn, names, info = OR.synthetic_rows(H, W, C, seed=HW)
     n = len(names)
@@ -202,7 +192,7 @@ def test_reader_bounds(case):
     """The readers' bounds handling (k_obs_unpack / k_obs_onehot_packed: obsPackedRow refuses an index outside the
     packed rows before any read of it, obsScatter skips a stored cell >= H*W before any LDS write, the stored count is
     clamped to cap): zero rows, the row without the bad cell, and the two counted."""
-    torch = _torch()
+    torch = torch_gpu()
     env, H, W, C, HW = case.env, case.H, case.W, case.C, case.HW
     assert HW < 1 << 16  # the cell number H*W fits the 16-bit field
     syn, names, _ = OR.synthetic_rows(H, W, C, seed=HW)
@@ -242,7 +232,7 @@ def test_reader_bounds(case):
 
 def test_refusals():
     """every ValueError of the Python layer and every -EINVAL of the C calls"""
-    torch = _torch()
+    torch = torch_gpu()
     from microrts_amd import _lib
 
     case = _case("8x8")
@@ -256,9 +246,9 @@ def test_refusals():
     a, b = ctypes.c_int64(0), ctypes.c_int64(0)
 
     def calls(hh, n=S, cap=8, packed=pk, obs=ob, out=hot, n_packed=S):
-        return [L.mrts_obs_pack_dev(hh, n, _p(obs), cap, _p(packed), None),
-                L.mrts_obs_unpack_dev(hh, n, _p(packed), n_packed, cap, None, _p(obs), None),
-                L.mrts_obs_onehot_packed_dev(hh, n, _p(packed), n_packed, cap, None, _p(out), None)]
+        return [L.mrts_obs_pack_dev(hh, n, ptr(obs), cap, ptr(packed), None),
+                L.mrts_obs_unpack_dev(hh, n, ptr(packed), n_packed, cap, None, ptr(obs), None),
+                L.mrts_obs_onehot_packed_dev(hh, n, ptr(packed), n_packed, cap, None, ptr(out), None)]
 
     assert calls(h) == [0, 0, 0]
     assert calls(None) == [-22] * 3 and L.mrts_last_error().decode() == "null handle"
@@ -269,10 +259,10 @@ def test_refusals():
         assert calls(h, cap=cap) == [-22] * 3 and "cap" in L.mrts_last_error().decode()
     assert calls(h, packed=None) == [-22] * 3 and calls(h, obs=None)[:2] == [-22] * 2 and calls(h, out=None)[2] == -22
     assert calls(h, n_packed=0)[1:] == [-22] * 2 and calls(h, n_packed=S - 1)[1:] == [-22] * 2
-    assert L.mrts_obs_onehot_packed_dev(h, S, _p(pk), S, 8, None, ctypes.c_void_p(hot.data_ptr() + 1), None) == -22
+    assert L.mrts_obs_onehot_packed_dev(h, S, ptr(pk), S, 8, None, ctypes.c_void_p(hot.data_ptr() + 1), None) == -22
     assert "misaligned" in L.mrts_last_error().decode()
-    assert L.mrts_obs_pack_dev(h, S, _p(ob), 8, ctypes.c_void_p(pk.data_ptr() + 2), None) == -22
-    assert L.mrts_obs_unpack_dev(h, S, _p(pk), S, 8, None, ctypes.c_void_p(ob.data_ptr() + 2), None) == -22
+    assert L.mrts_obs_pack_dev(h, S, ptr(ob), 8, ctypes.c_void_p(pk.data_ptr() + 2), None) == -22
+    assert L.mrts_obs_unpack_dev(h, S, ptr(pk), S, 8, None, ctypes.c_void_p(ob.data_ptr() + 2), None) == -22
     assert L.mrts_obs_packed_status(h, None, ctypes.byref(b)) == -22 and L.mrts_obs_packed_status(h, ctypes.byref(a), None) == -22
     assert L.mrts_obs_packed_status(h, ctypes.byref(a), ctypes.byref(b)) == 0 and (a.value, b.value) == (0, 0)
     # the Python layer names the argument

@@ -7,136 +7,58 @@ canonical state dump (units in list order + assignments in LinkedHashMap order).
 import numpy as np
 import pytest
 
-from tests import oracle_py
+from tests import dumps, oracle_py
+from tests.defs import SEED
+from tests.gpu_checks import onehot_encoder, rollout
+from tests.gpu_support import assert_matches_oracle, assert_same_outputs, torch_gpu
 
 pytestmark = pytest.mark.gpu
-
-SEED = 0x5EEDC0DE
-
-
-def _torch():
-    import torch
-
-    assert torch.cuda.is_available(), "GPU tests need an MI355X"
-    return torch
-
-
-def _compare_step(env, ref, step, dump_every, tag=""):
-    env.synchronize()
-    obs, rew, done = ref.obs, ref.reward, ref.done
-    g_obs = env.obs.cpu().numpy()
-    if not np.array_equal(g_obs, obs):
-        bad = np.argwhere(g_obs != obs)[0]
-        raise AssertionError(f"{tag} obs mismatch step {step} at {bad}: gpu {g_obs[tuple(bad)]} ref {obs[tuple(bad)]}")
-    assert np.array_equal(env.reward.cpu().numpy(), rew), f"{tag} reward mismatch step {step}"
-    assert np.array_equal(env.done.cpu().numpy(), done), f"{tag} done mismatch step {step}"
-    if dump_every and step % dump_every == 0:
-        for s in range(ref.S):
-            a, b = env.dump_state(s), ref.dump(s)
-            if not np.array_equal(a, b):
-                n = min(len(a), len(b))
-                i = int(np.argmax(a[:n] != b[:n])) if (a[:n] != b[:n]).any() else n
-                raise AssertionError(f"{tag} state mismatch slot {s} step {step} at word {i} (len {len(a)} vs {len(b)}):"
-                                     f"\n gpu {a[max(0, i - 14):i + 14]}\n ref {b[max(0, i - 14):i + 14]}\n gpu {a.tolist()}"
-                                     f"\n ref {b.tolist()}")
-
-
-def _rollout(maps, n_sp, n_bot=0, steps=200, max_steps=2000, utt=1, crs=1, policy="masked", dump_every=10, seed=3,
-             players=None, partial_obs=False, bots=None, rfs=None, utt_json=None, max_units=0):
-    torch = _torch()
-    from microrts_amd import DeviceVecEnv, UnitTypeTable
-
-    table = UnitTypeTable.fromJSON(utt_json) if utt_json else UnitTypeTable(utt, crs)
-    ntypes = len(table.TYPES)
-    env = DeviceVecEnv(n_sp, n_bot, max_steps, maps, utt=table, seed=seed, partial_obs=partial_obs,
-                       ai2s=bots, rfs=rfs, max_units=max_units)
-    kinds = [1 if b == "RandomBiasedAI" else 0 for b in bots] if bots else None
-    ref = oracle_py.OracleVecClient(n_sp, n_bot, max_steps, maps, utt_version=utt, crs=crs, seed=seed,
-                                    partial_obs=partial_obs, bot_kinds=kinds,
-                                    rewards=[oracle_py.REWARD_IDS[r] for r in rfs] if rfs else None, utt_json=utt_json)
-    S = ref.S
-    if players is not None:
-        env.players.copy_(torch.as_tensor(players, dtype=torch.int32))
-    env.reset()
-    ref.reset(players)
-    _compare_step(env, ref, 0, 1, "reset")
-    rng = np.random.default_rng(seed)
-    HW = ref.H * ref.W
-    for step in range(steps):
-        m_ref = ref.get_masks(0)
-        env.synchronize()
-        g_m = env.masks.cpu().numpy()
-        if not np.array_equal(g_m, m_ref):
-            bad = np.argwhere(g_m != m_ref)[0]
-            raise AssertionError(f"mask mismatch step {step} at {bad}: gpu {g_m[tuple(bad)]} ref {m_ref[tuple(bad)]}")
-        if policy == "masked":
-            env.random_policy(SEED, step)
-            env.synchronize()
-            acts = env.actions.cpu().numpy()
-            if step < 20 or step % 10 == 0:  # the GPU policy kernel is bit-identical to the oracle's Philox policy
-                for s in range(min(S, 8)):
-                    assert np.array_equal(acts[s], oracle_py.policy(m_ref[s], SEED, s, step, 0, ntypes))
-        else:  # unmasked uniform components (exercises every illegal → NONE path)
-            acts = np.stack([rng.integers(0, 6, (S, HW)), rng.integers(0, 4, (S, HW)), rng.integers(0, 4, (S, HW)),
-                             rng.integers(0, 4, (S, HW)), rng.integers(0, 4, (S, HW)), rng.integers(0, ntypes, (S, HW)),
-                             rng.integers(0, ref.K - 23 - ntypes, (S, HW))], axis=-1).astype(np.int32)
-            env.actions.copy_(torch.as_tensor(acts))
-        env.step()
-        ref.step(acts, players)
-        _compare_step(env, ref, step + 1, dump_every)
-        if rfs:
-            _rollout.nonzero |= (ref.reward != 0).reshape(ref.S, -1).any(axis=0)
-    flags = env.error_flags()
-    env.close()
-    ref.close()
-    return flags
-
 
 @pytest.mark.parametrize("mp", ["maps/4x4/base4x4.xml", "maps/8x8/basesWorkers8x8.xml", "maps/16x16/basesWorkers16x16.xml",
                                 "maps/BWDistantResources32x32.xml"])
 def test_selfplay_masked_policy(mp):
-    _rollout([mp] * 16, 16, steps=300 if "32x32" not in mp else 150)
+    rollout([mp] * 16, 16, steps=300 if "32x32" not in mp else 150)
 
 
 @pytest.mark.parametrize("mp", ["maps/8x8/basesWorkers8x8.xml", "maps/16x16/basesWorkers16x16.xml"])
 def test_selfplay_unmasked_uniform(mp):
-    _rollout([mp] * 16, 16, steps=300, policy="uniform")
+    rollout([mp] * 16, 16, steps=300, policy="uniform")
 
 
 def test_autoreset_and_short_episodes():
-    _rollout(["maps/4x4/base4x4.xml"] * 16, 16, steps=200, max_steps=37)
+    rollout(["maps/4x4/base4x4.xml"] * 16, 16, steps=200, max_steps=37)
 
 
 def test_mixed_maps_same_size():
     maps = ["maps/8x8/basesWorkers8x8.xml", "maps/8x8/basesWorkers8x8.xml", "maps/8x8/bases8x8.xml", "maps/8x8/bases8x8.xml",
             "maps/8x8/TwoBasesWorkers8x8.xml", "maps/8x8/TwoBasesWorkers8x8.xml", "maps/8x8/basesWorkersBarracks8x8.xml",
             "maps/8x8/basesWorkersBarracks8x8.xml"]
-    _rollout(maps, 8, steps=250)
+    rollout(maps, 8, steps=250)
 
 
 @pytest.mark.parametrize("utt,crs", [(2, 1), (3, 1), (1, 2), (1, 3), (3, 2)])
 def test_utt_versions_and_conflict_policies(utt, crs):
-    _rollout(["maps/8x8/basesWorkers8x8.xml"] * 16, 16, steps=250, utt=utt, crs=crs, policy="uniform")
+    rollout(["maps/8x8/basesWorkers8x8.xml"] * 16, 16, steps=250, utt=utt, crs=crs, policy="uniform")
 
 
 def test_bot_envs_passive():
     players = [0, 1, 0, 1, 1, 0]
-    _rollout(["maps/8x8/basesWorkers8x8.xml"] * 6, 0, n_bot=6, steps=200, players=players, policy="uniform")
+    rollout(["maps/8x8/basesWorkers8x8.xml"] * 6, 0, n_bot=6, steps=200, players=players, policy="uniform")
 
 
 def test_selfplay_plus_bots():
-    _rollout(["maps/8x8/basesWorkers8x8.xml"] * 6, 4, n_bot=2, steps=200, players=[0, 0, 0, 0, 1, 0])
+    rollout(["maps/8x8/basesWorkers8x8.xml"] * 6, 4, n_bot=2, steps=200, players=[0, 0, 0, 0, 1, 0])
 
 
 @pytest.mark.parametrize("mp,policy", [("maps/BWDistantResources32x32.xml", "masked"), ("maps/8x8/basesWorkers8x8.xml", "uniform"),
                                        ("maps/16x16/basesWorkers16x16.xml", "uniform")])
 def test_partial_observability(mp, policy):
     """BASELINE config c5 semantics: PartiallyObservableGameState views (8 planes)."""
-    _rollout([mp] * 16, 16, steps=200, policy=policy, partial_obs=True)
+    rollout([mp] * 16, 16, steps=200, policy=policy, partial_obs=True)
 
 
 def test_partial_observability_bots_and_resets():
-    _rollout(["maps/8x8/basesWorkers8x8.xml"] * 6, 2, n_bot=4, steps=200, max_steps=45, players=[0, 0, 1, 0, 1, 1],
+    rollout(["maps/8x8/basesWorkers8x8.xml"] * 6, 2, n_bot=4, steps=200, max_steps=45, players=[0, 0, 1, 0, 1, 1],
              partial_obs=True, policy="uniform")
 
 
@@ -144,14 +66,14 @@ def test_partial_observability_bots_and_resets():
 def test_agent_vs_random_biased(po):
     """JNIGridnetClient with a RandomBiasedAI opponent (a2 + a17): java.util.Random sampling on the GPU."""
     players = [0, 1, 0, 1, 0, 1, 1, 0]
-    _rollout(["maps/8x8/basesWorkers8x8.xml"] * 8, 0, n_bot=8, steps=300, players=players, partial_obs=po,
+    rollout(["maps/8x8/basesWorkers8x8.xml"] * 8, 0, n_bot=8, steps=300, players=players, partial_obs=po,
              bots=["RandomBiasedAI"] * 8, policy="masked")
 
 
 @pytest.mark.parametrize("mp", ["maps/4x4/base4x4.xml", "maps/16x16/basesWorkers16x16.xml"])
 def test_bot_only_client(mp):
     """Config c1 (JNIBotClient: RandomBiasedAI vs RandomBiasedAI / PassiveAI) on the GPU vs the oracle."""
-    torch = _torch()
+    torch = torch_gpu()
     from microrts_amd import DeviceVecEnv
 
     n = 8
@@ -176,7 +98,7 @@ def test_bot_only_client(mp):
 
 
 def test_host_api_matches_oracle():
-    _torch()
+    torch_gpu()
     from microrts_amd import JNIGridnetVecClient
 
     maps = ["maps/16x16/basesWorkers16x16.xml"] * 8
@@ -199,7 +121,7 @@ def test_host_api_matches_oracle():
 
 def test_full_size_properties():
     """BASELINE config c3 size (4096 games, 16x16): size-independent invariants + oracle spot checks."""
-    torch = _torch()
+    torch = torch_gpu()
     from microrts_amd import DeviceVecEnv
 
     E = 4096
@@ -236,7 +158,7 @@ def test_full_size_c5_fused():
     """BASELINE config c5 as bench.py runs it (2048 games, 32x32 partially observable, max_units 256,
     the fused random policy with forwarded rows, delta masks, persistent PO views): picked games are
     replayed by the oracle from the actions each launch consumed — observations and masks equal."""
-    _torch()
+    torch_gpu()
     from microrts_amd import DeviceVecEnv
 
     E = 2048
@@ -262,7 +184,7 @@ def test_full_size_c5_fused():
 def test_full_size_c2_uniform():
     """BASELINE config c2 as bench.py runs it (1024 games, 8x8, unmasked uniform rows, no masks, the
     native policy + step loop): picked games replayed by the oracle with the oracle's uniform rows."""
-    _torch()
+    torch_gpu()
     from microrts_amd import DeviceVecEnv
 
     E = 1024
@@ -294,7 +216,7 @@ def test_delta_masks_and_source_policy_match_full(mp, po, n_bot):
     """Delta mask and observation writes (only dirty rows / 4-cell chunks rewritten) leave the buffers
     byte-identical to full writes after every step (auto-resets at 150 steps included), and the
     source-bit policy kernel picks exactly the actions of the full-read policy kernel."""
-    torch = _torch()
+    torch = torch_gpu()
     from microrts_amd import DeviceVecEnv
 
     n_sp = 16
@@ -363,7 +285,7 @@ def test_java_rows_layout(mp, n_sp, n_bot, po, crs, mode):
     """mrts_step_rows (Java int[][][] rows: any order, duplicate rows, off-map positions) vs the oracle
     running PlayerAction.fromVectorAction over the same row lists; rows in ascending cell order must
     also equal the grid path."""
-    torch = _torch()
+    torch = torch_gpu()
     from microrts_amd import DeviceVecEnv, JNIGridnetVecClient, UnitTypeTable
 
     maps = [mp] * (n_sp + n_bot)
@@ -391,7 +313,8 @@ def test_java_rows_layout(mp, n_sp, n_bot, po, crs, mode):
         rows = _java_rows(rng, acts, mode)
         env.step_rows(torch.as_tensor(rows, device=env.device))
         ref.step_rows(rows)
-        _compare_step(env, ref, step + 1, 5, f"rows[{mode}]")
+        assert_matches_oracle(env, ref, f"rows[{mode}] step {step + 1}", masks=None,
+                              states="all" if (step + 1) % 5 == 0 else None)
         if grid is not None:
             grid.step(torch.as_tensor(acts, device=grid.device))
             grid.synchronize()
@@ -423,7 +346,7 @@ def test_java_rows_layout(mp, n_sp, n_bot, po, crs, mode):
 def test_more_than_64_units(rows):
     """EightBasesWorkers16x16 starts with 64 units and grows past one wave's worth: exercises the
     multi-block (nu > 64) decode / issue / ready-list paths, grid and Java-row layouts."""
-    torch = _torch()
+    torch = torch_gpu()
     from microrts_amd import DeviceVecEnv
 
     mp = "maps/16x16/EightBasesWorkers16x16.xml"
@@ -446,8 +369,8 @@ def test_more_than_64_units(rows):
         else:
             env.step(torch.as_tensor(acts, device=env.device))
             ref.step(acts)
-        _compare_step(env, ref, step + 1, 10, "many-units")
-        most = max(most, int(ref.dump(0)[4]))
+        assert_matches_oracle(env, ref, f"many-units step {step + 1}", masks=None, states="all" if (step + 1) % 10 == 0 else None)
+        most = max(most, dumps.n_units(ref.dump(0)))
     assert most > 64, f"test did not reach > 64 units (max {most})"
     assert not env.error_flags().any()
     env.close()
@@ -471,27 +394,27 @@ def test_all_reward_functions(mp, n_sp, n_bot, po, policy, crs):
     bit-exact (the Closer* ones are fp64 sqrt differences) after every step, self-play + RandomBiasedAI
     opponents, full and partial observability."""
     bots = ["RandomBiasedAI"] * n_bot if n_bot else None
-    _rollout.nonzero = np.zeros(len(ALL_RFS), bool)
-    assert not _rollout([mp] * (n_sp + n_bot), n_sp, n_bot, steps=400, max_steps=300, crs=crs, policy=policy,
+    rollout.nonzero = np.zeros(len(ALL_RFS), bool)
+    assert not rollout([mp] * (n_sp + n_bot), n_sp, n_bot, steps=400, max_steps=300, crs=crs, policy=policy,
                         partial_obs=po, bots=bots, rfs=ALL_RFS, dump_every=25).any()
     # non-vacuous: under the masked policy the gather / worker / attack / distance functions fire (WinLoss
     # and the building / combat-unit ones can stay 0 in 400 random steps); unmasked actions are mostly
     # illegal, so only the distance functions are certain to
     must = [1, 2, 4, 6, 7] if policy == "masked" else [6, 7]
-    assert _rollout.nonzero[must].all(), _rollout.nonzero
+    assert rollout.nonzero[must].all(), rollout.nonzero
 
 
 def test_first_reward_function_drives_reset():
     """done[0] of the FIRST reward function triggers the auto-reset (JNIGridnetVecClient.java:247):
     with ResourceGather first, a game resets only when its resources are gone, not at gameover."""
     rfs = ["ResourceGatherRewardFunction", "WinLossRewardFunction", "AttackRewardFunction"]
-    _rollout.nonzero = np.zeros(len(rfs), bool)
-    assert not _rollout(["maps/4x4/base4x4.xml"] * 8, 8, 0, steps=600, max_steps=5000, rfs=rfs, dump_every=50).any()
+    rollout.nonzero = np.zeros(len(rfs), bool)
+    assert not rollout(["maps/4x4/base4x4.xml"] * 8, 8, 0, steps=600, max_steps=5000, rfs=rfs, dump_every=50).any()
 
 
 def test_bot_only_reward_functions():
     """Config c1 clients with all eight reward functions (JNIBotClient.java:108-135)."""
-    torch = _torch()
+    torch = torch_gpu()
     from microrts_amd import DeviceVecEnv
 
     n, mp = 4, "maps/8x8/basesWorkers8x8.xml"
@@ -509,40 +432,11 @@ def test_bot_only_reward_functions():
     env.close()
 
 
-def _encode_obs_np(obs, ntypes=7):
-    """numpy restatement of MicroRTS-Py's GridnetVecEnv `_encode_obs` (gym_microrts, external to the
-    reference — parity unpinned): per env, planes clipped to [0, n-1] and one-hot encoded, channels
-    last, plane sizes [5, 5, 3, ntypes + 1, 6, 2] (+ [2] per extra partial-observability plane)."""
-    S, C, H, W = obs.shape
-    sizes = [5, 5, 3, ntypes + 1, 6, 2] + [2] * (C - 6)
-    offs = np.concatenate([[0], np.cumsum(sizes)[:-1]])
-    out = np.zeros((S, H * W, sum(sizes)), np.uint8)
-    flat = obs.reshape(S, C, H * W)
-    for p in range(C):
-        v = np.clip(flat[:, p], 0, sizes[p] - 1)
-        np.put_along_axis(out, (v + offs[p])[..., None], 1, axis=2)
-    return out.reshape(S, H, W, -1)
-
-
 @pytest.mark.parametrize("mp,po", [("maps/16x16/basesWorkers16x16.xml", False), ("maps/10x10/basesWorkers10x10.xml", True),
                                    ("maps/4x4/base4x4.xml", False)])
 def test_onehot_encoder(mp, po):
     """mrts_onehot_dev = MicroRTS-Py's observation encoding of the step's int32 observation."""
-    torch = _torch()
-    from microrts_amd import DeviceVecEnv
-
-    env = DeviceVecEnv(6, 0, 2000, [mp] * 6, seed=3, partial_obs=po)
-    env.reset()
-    for step in range(60):
-        env.random_policy(SEED, step)
-        env.step()
-        if step % 10 == 9:
-            got = env.onehot_obs()
-            env.synchronize()
-            ref = _encode_obs_np(env.obs.cpu().numpy())
-            assert got.shape == ref.shape and got.shape[-1] == (33 if po else 29)
-            assert np.array_equal(got.cpu().numpy(), ref), f"step {step}"
-    env.close()
+    onehot_encoder(mp, po)
 
 
 # ------------------------------------------------------------------ JSON unit-type tables
@@ -560,10 +454,10 @@ def test_utt_from_json_fixture(mp, n_sp, n_bot, po, policy):
     """The reference's utts/TestUnitTypeTable.json (Base hp 50, Barracks hp 25, harvestTime taken
     from produceTime by UnitType.updateFromJSON) with every reward function."""
     S = n_sp + n_bot
-    _rollout.nonzero = np.zeros(len(ALL_RFS), bool)
-    assert not _rollout([mp] * S, n_sp, n_bot, steps=300, policy=policy, partial_obs=po, bots=["RandomBiasedAI"] * n_bot,
+    rollout.nonzero = np.zeros(len(ALL_RFS), bool)
+    assert not rollout([mp] * S, n_sp, n_bot, steps=300, policy=policy, partial_obs=po, bots=["RandomBiasedAI"] * n_bot,
                         rfs=ALL_RFS, utt_json=_fixture_utt(), dump_every=25).any()
-    assert _rollout.nonzero[[6, 7]].all()
+    assert rollout.nonzero[[6, 7]].all()
 
 
 def test_utt_from_json_eight_types():
@@ -579,16 +473,16 @@ def test_utt_from_json_eight_types():
                            "producedBy": ["Worker"]})
     js = json.dumps(t)
     mp = "maps/8x8/basesWorkers8x8.xml"
-    _rollout.nonzero = np.zeros(len(ALL_RFS), bool)
-    assert not _rollout([mp] * 8, 6, 2, steps=300, policy="masked", bots=["RandomBiasedAI"] * 2, rfs=ALL_RFS,
+    rollout.nonzero = np.zeros(len(ALL_RFS), bool)
+    assert not rollout([mp] * 8, 6, 2, steps=300, policy="masked", bots=["RandomBiasedAI"] * 2, rfs=ALL_RFS,
                         utt_json=js, dump_every=25, seed=12).any()
-    assert _rollout.nonzero[[1, 2, 4, 6, 7]].all()
+    assert rollout.nonzero[[1, 2, 4, 6, 7]].all()
 
 
 @pytest.mark.parametrize("mp,po,mu", [("maps/BWDistantResources32x32.xml", True, 96), ("maps/16x16/basesWorkers16x16.xml", False, 40)])
 def test_max_units_bound(mp, po, mu):
     """mrts_config.max_units: a smaller unit-slot capacity plays identically (generic kernel: bot envs)."""
-    assert not _rollout([mp] * 8, 6, 2, steps=200, partial_obs=po, bots=["RandomBiasedAI"] * 2, max_units=mu,
+    assert not rollout([mp] * 8, 6, 2, steps=200, partial_obs=po, bots=["RandomBiasedAI"] * 2, max_units=mu,
                         dump_every=20).any()
 
 
@@ -597,11 +491,11 @@ def test_max_units_bound(mp, po, mu):
                                              ("maps/8x8/basesWorkers8x8.xml", False, 0, "uniform")])
 def test_specialised_shapes(mp, po, mu, policy):
     """The compile-time specialisations of the step kernel: c5 (32x32 PO, 320 slots) and c2 (8x8)."""
-    assert not _rollout([mp] * 16, 16, steps=250, partial_obs=po, max_units=mu, policy=policy, dump_every=25).any()
+    assert not rollout([mp] * 16, 16, steps=250, partial_obs=po, max_units=mu, policy=policy, dump_every=25).any()
 
 
 def test_max_units_below_map_units_rejected():
-    _torch()
+    torch_gpu()
     from microrts_amd import DeviceVecEnv
 
     with pytest.raises(RuntimeError):
@@ -618,7 +512,7 @@ def test_max_units_below_map_units_rejected():
 def test_fused_policy_matches_separate_kernels(mp, n_sp, n_bot, po, delta):
     """mrts_step_fused_dev = mrts_step_dev followed by mrts_policy_dev(next step), bit for bit, including
     after a reset and a standalone mask write in between."""
-    torch = _torch()
+    torch = torch_gpu()
     from microrts_amd import DeviceVecEnv
 
     S = n_sp + n_bot
@@ -654,7 +548,7 @@ def test_fused_forwarding_respects_action_writes(mp):
     when the caller overwrites the action tensor in between (uniform random rows, every 7th step), or
     runs a plain step or a mask write on the handle, the next fused step must read the tensor.  Twin A
     always reads the tensor (step + standalone policy kernel)."""
-    torch = _torch()
+    torch = torch_gpu()
     from microrts_amd import DeviceVecEnv
 
     n_sp = 16
@@ -692,7 +586,7 @@ def test_fused_forwarding_respects_action_writes(mp):
 def test_native_rollout_matches_fused_steps(mp, n_sp):
     """mrts_rollout_fused_dev(n) = n mrts_step_fused_dev calls (the bench's timed launch form), bit for
     bit: observations, rewards, dones, masks, next actions and every game's state."""
-    torch = _torch()
+    torch_gpu()
     from microrts_amd import DeviceVecEnv
 
     mk = lambda: DeviceVecEnv(n_sp, 0, 300, [mp] * n_sp, seed=3)  # noqa: E731
@@ -706,16 +600,9 @@ def test_native_rollout_matches_fused_steps(mp, n_sp):
             A.step_fused(SEED, k + i + 1)
         B.rollout_fused(SEED, k + 1, n)
         k += n
-        A.synchronize()
-        B.synchronize()
-        for name in ("obs", "reward", "done", "masks", "actions"):
-            assert np.array_equal(getattr(A, name).cpu().numpy(), getattr(B, name).cpu().numpy()), f"{name} after {k}"
-        for s in range(0, n_sp, 2):
-            assert np.array_equal(A.dump_state(s), B.dump_state(s)), f"state slot {s} after {k}"
-    assert np.array_equal(A._h.env_steps(), B._h.env_steps())
+        assert_same_outputs(A, B, f"after {k}")
     A.close()
     B.close()
-    del torch
 
 
 @pytest.mark.parametrize("mp,n_sp,max_steps,po", [("maps/16x16/basesWorkers16x16.xml", 48, 300, False),
@@ -732,7 +619,7 @@ def test_multi_step_rollout_matches_single_launches(mp, n_sp, max_steps, po):
     the multi-block decode, mask and non-forwarded row paths inside the loop), then single fused
     steps, a plain step and a mask write after the multi-step launches (handle bookkeeping); the 32x32
     partially observable views (persistent-buffer delta renders whose record is re-read per step)."""
-    torch = _torch()
+    torch = torch_gpu()
     from microrts_amd import DeviceVecEnv
 
     mk = lambda: DeviceVecEnv(n_sp, 0, max_steps, [mp] * n_sp, seed=5, partial_obs=po,  # noqa: E731
@@ -778,7 +665,7 @@ def test_multi_step_uniform_po_matches_single_launches():
     """The c5 helper-wave instance under the uniform rollout (mrts_rollout_uniform_dev: no masks, so
     the game wave hands the helper no mask records): multi-step launches = one launch per step, bit for
     bit — observations, rewards, dones, the drawn rows and every game's state."""
-    torch = _torch()
+    torch = torch_gpu()
     from microrts_amd import DeviceVecEnv
 
     mp, n_sp = "maps/BWDistantResources32x32.xml", 32
@@ -833,7 +720,7 @@ def test_po_helper_wave_over_64_units(tmp_path):
     waits at a second barrier, and the packed form takes over again after the auto-reset.  The crowded map
     starts at 60 units and the games produce past 64 (oracle: steps ~249-298 of 300): multi-step = one
     launch per step, bit for bit, across both transitions."""
-    torch = _torch()
+    torch = torch_gpu()
     from microrts_amd import DeviceVecEnv
 
     mp = _crowded_32x32(tmp_path, 22)
@@ -845,7 +732,7 @@ def test_po_helper_wave_over_64_units(tmp_path):
     for e in (A, B):
         e.reset()
         e.random_policy(SEED, 0)
-    assert int(B.dump_state(0)[4]) <= 64
+    assert dumps.n_units(B.dump_state(0)) <= 64
     names = ("obs", "reward", "done", "masks", "actions", "source")
     k, high = 0, 0
     for n in (1, 3, 40, 60, 60, 60, 60, 80, 60):
@@ -858,7 +745,7 @@ def test_po_helper_wave_over_64_units(tmp_path):
             assert torch.equal(getattr(A, name), getattr(B, name)), f"{name} after {k}"
         for s in range(0, n_sp, 2):
             d = B.dump_state(s)
-            high = max(high, int(d[4]))
+            high = max(high, dumps.n_units(d))
             assert np.array_equal(A.dump_state(s), d), f"state slot {s} after {k}"
     assert high > 64, f"no game grew past 64 units (most {high})"
     assert not A.error_flags().any() and not B.error_flags().any()
@@ -880,7 +767,7 @@ def test_po_obs_delta_matches_full(mp, n_sp, n_bot, rows, max_units):
     every step: self-play and agent-vs-RandomBiasedAI games (the agent's side flips every 7 steps),
     auto-resets (max_steps 120), a caller's in-place edit of env.obs, a checkpoint restore and a
     GameState.fromJSON injection."""
-    torch = _torch()
+    torch = torch_gpu()
     from microrts_amd import DeviceVecEnv
 
     S = n_sp + n_bot
@@ -935,7 +822,7 @@ def test_po_obs_delta_matches_full(mp, n_sp, n_bot, rows, max_units):
 def test_uniform_policy_matches_oracle():
     """mrts_policy_uniform_dev (BASELINE config c2's unmasked uniform rows) = the oracle's restatement,
     for every slot, several steps, with a non-zero slot_id_base."""
-    _torch()
+    torch_gpu()
     from microrts_amd import DeviceVecEnv
 
     env = DeviceVecEnv(12, 0, 300, ["maps/8x8/basesWorkers8x8.xml"] * 12, seed=2, slot_id_base=40)
@@ -953,7 +840,7 @@ def test_uniform_rollout_matches_oracle(mp):
     """The c2 workload: rollout_uniform (uniform rows + a step without masks, native loop) against the
     oracle VecClient stepped with the oracle's uniform rows — observations, rewards and dones every
     step, the canonical state every 20 steps, and across auto-resets (max_steps 150)."""
-    _torch()
+    torch_gpu()
     from microrts_amd import DeviceVecEnv
 
     n = 16
@@ -962,12 +849,12 @@ def test_uniform_rollout_matches_oracle(mp):
     S, H, W, C, K = env.dims
     env.reset()
     ref.reset(None)
-    _compare_step(env, ref, 0, 1, "reset")
+    assert_matches_oracle(env, ref, "reset", masks=None)
     for step in range(260):
         env.rollout_uniform(SEED, step, 1)
         acts = np.stack([oracle_py.policy_uniform(H, W, K, SEED, s, step) for s in range(S)])
         ref.step(acts, None)
-        _compare_step(env, ref, step + 1, 20, "uniform")
+        assert_matches_oracle(env, ref, f"uniform step {step + 1}", masks=None, states="all" if (step + 1) % 20 == 0 else None)
     assert not env.error_flags().any()
     env.close()
     ref.close()
@@ -983,7 +870,7 @@ def test_uniform_fused_matches_split(mp, n_sp, n_bot, po, masks):
     observations, rewards, dones (and masks) after every step, every slot's canonical state every 25
     steps — specialised 16x16 / 8x8 kernels, the generic kernel with agent-vs-RandomBiasedAI games and
     partially observable views, across auto-resets (max_steps 120)."""
-    torch = _torch()
+    torch = torch_gpu()
     from microrts_amd import DeviceVecEnv
 
     maps = [mp] * (n_sp + n_bot)
@@ -1031,7 +918,7 @@ def test_obs16_copy_matches_obs(mp, n_sp, n_bot):
     """mrts_set_obs16: every observation write also leaves the planes as int16 in the given buffer —
     after reset, plain steps, fused steps and multi-step rollouts (auto-resets included), on the
     specialised and generic kernels; switching the buffer and turning it off work too."""
-    torch = _torch()
+    torch = torch_gpu()
     from microrts_amd import DeviceVecEnv
 
     bots = ["RandomBiasedAI"] * n_bot if n_bot else None
@@ -1068,7 +955,7 @@ def test_obs16_copy_matches_obs(mp, n_sp, n_bot):
 def test_host_mask_views_match_copies():
     """getMasks(copy=False): views of the library-owned pinned arrays (mrts_get_masks_host /
     mrts_get_masks_i32_host) hold the same masks as the copying form, and the next call refills them."""
-    _torch()
+    torch_gpu()
     from microrts_amd import JNIGridnetVecClient, UnitTypeTable
 
     mp = "maps/8x8/basesWorkers8x8.xml"
@@ -1095,4 +982,4 @@ def test_full_obs_without_byte_image(tmp_path):
     assert 'resources="25"' in src
     big = tmp_path / "bigpile16x16.xml"
     big.write_text(src.replace('resources="25"', 'resources="300"', 1))
-    _rollout([str(big)] * 8, 8, steps=120)
+    rollout([str(big)] * 8, 8, steps=120)

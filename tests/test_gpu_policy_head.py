@@ -8,19 +8,20 @@ candidate, a slot with every bit of every cell set, empty / single-bit / scatter
 Tolerances are measured, not guessed: the same quantities computed by the reference in float32 on the CPU deviate
 from the float64 reference by some largest amount over a test's inputs, and the kernels (which sum in another
 order) get 4x that; the tests print both figures (MEASURED below records a run)."""
-import ctypes
 import math
 
 import numpy as np
 import pytest
 
 from tests import policy_head_ref as R
+from tests.defs import SEED
+from tests.gpu_support import assert_same_outputs, ptr, torch_gpu
 
 pytestmark = pytest.mark.gpu
 
 MAPS = {"4x4": "maps/4x4/basesWorkers4x4.xml", "9x8": "maps/NoWhereToRun9x8.xml", "16x16": "maps/16x16/basesWorkers16x16.xml"}
 S = 6
-SEED, HSEED, HSTEP = 0x5EEDC0DE, 0x0123456789ABCDEF, 17
+HSEED, HSTEP = 0x0123456789ABCDEF, 17
 # x the fp32 CPU reference's largest deviation from the float64 reference over a test's inputs (_bound).
 # MEASURED on an MI355X (fp32 CPU reference's deviation -> bound; the kernels' deviation):
 #   log-probability / entropy  4x4: 1.2e-5 -> 4.9e-5; 5.6e-6    9x8: 5.5e-5 -> 2.2e-4; 2.2e-5    16x16: 1.7e-4 -> 6.7e-4; 8.0e-5
@@ -30,27 +31,16 @@ SEED, HSEED, HSTEP = 0x5EEDC0DE, 0x0123456789ABCDEF, 17
 TOL_FACTOR = 4.0
 
 
-def _torch():
-    import torch
-
-    assert torch.cuda.is_available(), "GPU tests need an MI355X"
-    return torch
-
-
-def _p(t):
-    return ctypes.c_void_p(t.data_ptr()) if t is not None else None
-
-
 def _sample(env, logits, masks, source, seed, step):
     """the C entry on any masks / source bits: (actions, logprob, entropy)"""
-    torch = _torch()
+    torch = torch_gpu()
     from microrts_amd import _lib
 
     n = env._h.S
     out = torch.full((n, logits.shape[1], 7), -7, dtype=torch.int32, device=env.device)
     lp, ent = (torch.full((n,), math.nan, dtype=torch.float32, device=env.device) for _ in range(2))
-    _lib.check(env._h.L.mrts_policy_head_sample_dev(env._h.h, _p(logits), _p(masks), _p(source), seed, step, _p(out), _p(lp),
-                                                    _p(ent), env._s(None)))
+    _lib.check(env._h.L.mrts_policy_head_sample_dev(env._h.h, ptr(logits), ptr(masks), ptr(source), seed, step, ptr(out), ptr(lp),
+                                                    ptr(ent), env._s(None)))
     return out, lp, ent
 
 
@@ -58,7 +48,7 @@ class Case:
     """one shape: an env stepped 50 times, its masks / source bits, synthetic masks, logits, the float64 reference"""
 
     def __init__(self, shape):
-        torch = _torch()
+        torch = torch_gpu()
         from microrts_amd import DeviceVecEnv
 
         self.env = env = DeviceVecEnv(S, 0, 2000, [MAPS[shape]] * S, seed=3)
@@ -108,7 +98,7 @@ def _bound(name, torch, pairs):
 
 @pytest.mark.parametrize("kind", ["env", "syn"])
 def test_legality_zero_rows_and_both_candidate_forms(case, kind):
-    torch = _torch()
+    torch = torch_gpu()
     env, m = case.env, case.masks[kind]
     a, lp, ent = _sample(env, case.logits, m, case.source[kind], HSEED, HSTEP)
     a2, lp2, ent2 = _sample(env, case.logits, m, None, HSEED, HSTEP)
@@ -148,7 +138,7 @@ def test_draws_equal_the_float64_reference(case, kind):
 
 def test_stream_identity():
     """slot 0 of a handle with slot_id_base 3 draws what slot 3 of a base-0 handle draws; step and seed matter"""
-    torch = _torch()
+    torch = torch_gpu()
     from microrts_amd import DeviceVecEnv
 
     c = _case("9x8")
@@ -167,7 +157,7 @@ def test_stream_identity():
 
 def test_frequencies():
     """one candidate cell, type bits 1 2 4 with logits log 1, log 2, log 5, over 4096 steps: counts within 5 sigma"""
-    torch = _torch()
+    torch = torch_gpu()
     c = _case("4x4")
     env = c.env
     masks = torch.zeros((S, c.HW, c.K), dtype=torch.uint8, device=env.device)
@@ -181,7 +171,7 @@ def test_frequencies():
     outs = torch.zeros((n, S, c.HW, 7), dtype=torch.int32, device=env.device)
     L = env._h.L
     for t in range(n):
-        assert L.mrts_policy_head_sample_dev(env._h.h, _p(logits), _p(masks), _p(src), 99, t, _p(outs[t]), None, None,
+        assert L.mrts_policy_head_sample_dev(env._h.h, ptr(logits), ptr(masks), ptr(src), 99, t, ptr(outs[t]), None, None,
                                              env._s(None)) == 0
     got = outs[:, 0, 5, 0].cpu().numpy()
     assert outs.sum().item() == got.sum()
@@ -193,18 +183,18 @@ def test_frequencies():
 
 
 def _score(env, logits, masks, actions):
-    torch = _torch()
+    torch = torch_gpu()
     from microrts_amd import _lib
 
     n = logits.shape[0]
     lp, ent = (torch.full((n,), math.nan, dtype=torch.float32, device=env.device) for _ in range(2))
-    _lib.check(env._h.L.mrts_policy_head_score_dev(env._h.h, n, _p(logits), _p(masks), _p(actions), _p(lp), _p(ent), env._s(None)))
+    _lib.check(env._h.L.mrts_policy_head_score_dev(env._h.h, n, ptr(logits), ptr(masks), ptr(actions), ptr(lp), ptr(ent), env._s(None)))
     return lp, ent
 
 
 def _rows(c, n, seed):
     """n rows of logits / synthetic masks / on-mask actions (drawn by the reference from numpy uniforms)"""
-    torch = _torch()
+    torch = torch_gpu()
     g = torch.Generator().manual_seed(seed)
     logits = 3 * torch.randn((n, c.HW, c.K - 1), generator=g)
     masks = torch.from_numpy(R.synthetic_masks(n, c.HW, c.K, c.nt, seed=seed))
@@ -214,7 +204,7 @@ def _rows(c, n, seed):
 
 
 def test_logprob_and_entropy(case):
-    torch = _torch()
+    torch = torch_gpu()
     env, dev = case.env, case.env.device
     runs = []  # (kernel logprob, kernel entropy, float32 reference, float64 reference)
     for kind in ("env", "syn"):
@@ -238,7 +228,7 @@ def test_logprob_and_entropy(case):
 
 
 def test_exact_logprob_cases(case):
-    torch = _torch()
+    torch = torch_gpu()
     env, dev = case.env, case.env.device
     masks = torch.zeros((3, case.HW, case.K), dtype=torch.uint8)
     masks[0, :, 1:] = 1  # row 0: no candidate
@@ -256,17 +246,17 @@ def test_exact_logprob_cases(case):
 
 
 def _grad(env, logits, masks, acts, g_lp, g_ent):
-    torch = _torch()
+    torch = torch_gpu()
     from microrts_amd import _lib
 
     out = torch.full_like(logits, math.nan)  # garbage: every element must be overwritten
-    _lib.check(env._h.L.mrts_policy_head_grad_dev(env._h.h, logits.shape[0], _p(logits), _p(masks), _p(acts), _p(g_lp), _p(g_ent),
-                                                  _p(out), env._s(None)))
+    _lib.check(env._h.L.mrts_policy_head_grad_dev(env._h.h, logits.shape[0], ptr(logits), ptr(masks), ptr(acts), ptr(g_lp), ptr(g_ent),
+                                                  ptr(out), env._s(None)))
     return out
 
 
 def test_masked_logits_are_never_read(case):
-    torch = _torch()
+    torch = torch_gpu()
     env, dev = case.env, case.env.device
     for kind in ("env", "syn"):
         m = case.masks[kind]
@@ -290,7 +280,7 @@ def test_masked_logits_are_never_read(case):
 
 
 def test_gradient(case):
-    torch = _torch()
+    torch = torch_gpu()
     from microrts_amd import evaluate_actions
 
     env, dev = case.env, case.env.device
@@ -332,18 +322,8 @@ def test_gradient(case):
     assert worst <= tol
 
 
-def _same(torch, A, B, tag):
-    A.synchronize()
-    B.synchronize()
-    for name in ("obs", "masks", "actions", "source", "reward", "done"):
-        assert torch.equal(getattr(A, name), getattr(B, name)), f"{tag}: {name}"
-    assert not A.error_flags().any() and not B.error_flags().any(), tag
-    for s in range(0, A._h.S, 2):
-        assert np.array_equal(A.dump_state(s), B.dump_state(s)), f"{tag}: state of slot {s}"
-
-
 def test_determinism_and_bookkeeping():
-    torch = _torch()
+    torch = torch_gpu()
     from microrts_amd import DeviceVecEnv, _lib
 
     c = _case("16x16")
@@ -368,32 +348,32 @@ def test_determinism_and_bookkeeping():
         e.random_policy(SEED, 0)
         for k in range(1, 6):
             e.step_fused(SEED, k)
-    _same(torch, A, B, "fused warm-up")
+    assert_same_outputs(A, B, "fused warm-up")
     head(5)
     for e in (A, B):
         e.step_fused(SEED, 6)
-    _same(torch, A, B, "step_fused after sample_actions")
+    assert_same_outputs(A, B, "step_fused after sample_actions")
     head(6)
     for e in (A, B):
         e.random_policy(SEED, 7)
-    _same(torch, A, B, "random_policy after sample_actions")
+    assert_same_outputs(A, B, "random_policy after sample_actions")
     for e in (A, B):
         e.step()
         e.random_policy(SEED, 8)
     head(8)
     for e in (A, B):
         e.step()
-    _same(torch, A, B, "step after sample_actions")
+    assert_same_outputs(A, B, "step after sample_actions")
     head(9)
     for e in (A, B):
         e.rollout_fused(SEED, 10, 6)
-    _same(torch, A, B, "rollout_fused after sample_actions")
+    assert_same_outputs(A, B, "rollout_fused after sample_actions")
     A.close()
     B.close()
 
 
 def test_refusals():
-    torch = _torch()
+    torch = torch_gpu()
     from microrts_amd import ForwardModel, JNIGridnetVecClient, _lib
 
     m = MAPS["4x4"]
@@ -405,20 +385,20 @@ def test_refusals():
     ac = torch.zeros((2, 16, 7), dtype=torch.int32, device=dev)
     L = _lib.load()
     for h in (bots._h, fm._h):
-        calls = [L.mrts_policy_head_sample_dev(h.h, _p(lg), _p(mk), None, 1, 0, _p(ac), None, None, None),
-                 L.mrts_policy_head_score_dev(h.h, 2, _p(lg), _p(mk), _p(ac), None, None, None),
-                 L.mrts_policy_head_grad_dev(h.h, 2, _p(lg), _p(mk), _p(ac), None, None, _p(lg.clone()), None)]
+        calls = [L.mrts_policy_head_sample_dev(h.h, ptr(lg), ptr(mk), None, 1, 0, ptr(ac), None, None, None),
+                 L.mrts_policy_head_score_dev(h.h, 2, ptr(lg), ptr(mk), ptr(ac), None, None, None),
+                 L.mrts_policy_head_grad_dev(h.h, 2, ptr(lg), ptr(mk), ptr(ac), None, None, ptr(lg.clone()), None)]
         for rc in calls:
             assert rc == -95 and "bot-only or forward-model" in L.mrts_last_error().decode()  # -ENOTSUP
     bots.close()
     fm.close()
     env = _case("4x4").env
     h = env._h
-    assert L.mrts_policy_head_score_dev(h.h, -1, _p(lg), _p(mk), _p(ac), None, None, None) == -22  # -EINVAL
-    assert L.mrts_policy_head_score_dev(h.h, (1 << 31) // 16, _p(lg), _p(mk), _p(ac), None, None, None) == -22
-    assert L.mrts_policy_head_score_dev(h.h, 2, None, _p(mk), _p(ac), None, None, None) == -22
-    assert L.mrts_policy_head_grad_dev(h.h, 2, _p(lg), _p(mk), _p(ac), None, None, None, None) == -22
-    assert L.mrts_policy_head_sample_dev(h.h, _p(lg), None, None, 1, 0, _p(ac), None, None, None) == -22
+    assert L.mrts_policy_head_score_dev(h.h, -1, ptr(lg), ptr(mk), ptr(ac), None, None, None) == -22  # -EINVAL
+    assert L.mrts_policy_head_score_dev(h.h, (1 << 31) // 16, ptr(lg), ptr(mk), ptr(ac), None, None, None) == -22
+    assert L.mrts_policy_head_score_dev(h.h, 2, None, ptr(mk), ptr(ac), None, None, None) == -22
+    assert L.mrts_policy_head_grad_dev(h.h, 2, ptr(lg), ptr(mk), ptr(ac), None, None, None, None) == -22
+    assert L.mrts_policy_head_sample_dev(h.h, ptr(lg), None, None, 1, 0, ptr(ac), None, None, None) == -22
     with pytest.raises(ValueError, match="logits"):
         env.sample_actions(torch.zeros((S, 16, 78), dtype=torch.float64, device=dev), 1, 0)
     with pytest.raises(ValueError, match="out"):

@@ -13,6 +13,7 @@ import numpy as np
 import pytest
 
 from tests import policy_head_packed_ref as PR
+from tests.gpu_support import ptr, torch_gpu
 
 pytestmark = pytest.mark.gpu
 
@@ -21,36 +22,25 @@ S, T, STEPS = 16, 4, 50
 HSEED = 0x0123456789ABCDEF
 
 
-def _torch():
-    import torch
-
-    assert torch.cuda.is_available(), "GPU tests need an MI355X"
-    return torch
-
-
-def _p(t):
-    return ctypes.c_void_p(t.data_ptr()) if t is not None else None
-
-
 def _bits(t):
-    return t.contiguous().view(_torch().int32)
+    return t.contiguous().view(torch_gpu().int32)
 
 
 def _u32(shape, value, device):
     """a uint32 tensor filled with one word"""
-    torch = _torch()
+    torch = torch_gpu()
     return torch.full(shape, value - (1 << 32) if value >> 31 else value, dtype=torch.int32, device=device).view(torch.uint32)
 
 
 def _np32(t):
-    return t.cpu().view(_torch().int32).numpy().view(np.uint32)
+    return t.cpu().view(torch_gpu().int32).numpy().view(np.uint32)
 
 
 class Case:
     """one shape: a rollout under sample_actions whose last T steps are kept dense and packed, and the synthetic rows"""
 
     def __init__(self, shape):
-        torch = _torch()
+        torch = torch_gpu()
         from microrts_amd import DeviceVecEnv
 
         self.env = env = DeviceVecEnv(S, 0, 2000, [MAPS[shape]] * S, seed=3)
@@ -102,7 +92,7 @@ class Case:
         return lp.detach(), ent.detach(), lg.grad
 
     def weights(self, n):
-        torch = _torch()
+        torch = torch_gpu()
         g = torch.Generator().manual_seed(n)
         return tuple((torch.rand(n, generator=g) + 0.5).to(self.env.device) for _ in range(2))
 
@@ -129,7 +119,7 @@ def _same(torch, got, want, tag, rows=None):
 
 def test_format_matches_the_header(case):
     """1. the bytes pack_step writes are the bytes of the numpy packer written from include/mrts.h"""
-    torch = _torch()
+    torch = torch_gpu()
     env = case.env
     m, a, s = (t.cpu().numpy() for t in (case.masks, case.actions, case.source))
     total = 0
@@ -153,7 +143,7 @@ def test_format_matches_the_header(case):
 
 def test_round_trip_is_the_canonical_dense_form(case):
     """2. unpack(pack(x)): the env's masks and sampled rows unchanged, junk at non-candidate cells zeroed"""
-    torch = _torch()
+    torch = torch_gpu()
     env = case.env
     m, a = env.unpack(case.buf)
     assert torch.equal(m.reshape(T, S, case.HW, case.K), case.masks), "the env's masks are canonical"
@@ -175,7 +165,7 @@ def test_round_trip_is_the_canonical_dense_form(case):
 
 def test_bit_equality_with_the_dense_kernels(case):
     """3. the main test: logprob, entropy and gradient equal the dense kernels' byte for byte"""
-    torch = _torch()
+    torch = torch_gpu()
     env = case.env
     # the rollout's last step, packed with the source bits (by the rollout) and without them
     g1, g2 = case.weights(S)
@@ -205,7 +195,7 @@ def test_bit_equality_with_the_dense_kernels(case):
 
 def test_gather_through_an_index(case):
     """4. index with repeats and a permutation == the dense call on masks[index], actions[index]"""
-    torch = _torch()
+    torch = torch_gpu()
     env, N = case.env, T * S
     g = torch.Generator().manual_seed(5)
     idx = torch.cat([torch.randperm(N, generator=g), torch.tensor([3, 3, N - 1, 0, 3])]).to(torch.int32)
@@ -229,7 +219,7 @@ def test_gather_through_an_index(case):
 
 def test_overflowing_rows_are_nan_and_counted(case):
     """5. cap below a row's count: that row NaN (logprob, entropy, gradient row), the others as dense, the counter"""
-    torch = _torch()
+    torch = torch_gpu()
     env, cap = case.env, 3
     n = case.syn_masks.shape[0]
     count = (case.syn_masks[:, :, 0] != 0).sum(1)
@@ -251,7 +241,7 @@ def test_overflowing_rows_are_nan_and_counted(case):
 
 def test_determinism_and_the_first_epoch_ratio(case):
     """6. two pack and score runs give equal bytes; sample_actions' own logprob == the packed score of its rows"""
-    torch = _torch()
+    torch = torch_gpu()
     env = case.env
     g1, g2 = case.weights(S)
     out = [torch.empty_like(case.buf[0]) for _ in range(2)]
@@ -266,7 +256,7 @@ def test_determinism_and_the_first_epoch_ratio(case):
 
 def test_refusals():
     """7. bot-only and forward-model handles, cap outside [1, H*W], missing pointers"""
-    torch = _torch()
+    torch = torch_gpu()
     from microrts_amd import ForwardModel, JNIGridnetVecClient, _lib
 
     m = "maps/4x4/basesWorkers4x4.xml"
@@ -281,10 +271,10 @@ def test_refusals():
     v = ctypes.c_int64(0)
 
     def calls(h, cap, n=2):
-        return [L.mrts_policy_head_pack_dev(h.h, n, _p(mk), None, _p(ac), cap, _p(pk), None),
-                L.mrts_policy_head_unpack_dev(h.h, n, _p(pk), 2, cap, None, _p(mk.clone()), _p(ac.clone()), None),
-                L.mrts_policy_head_score_packed_dev(h.h, n, _p(lg), _p(pk), 2, cap, None, None, None, None),
-                L.mrts_policy_head_grad_packed_dev(h.h, n, _p(lg), _p(pk), 2, cap, None, None, None, _p(lg.clone()), None)]
+        return [L.mrts_policy_head_pack_dev(h.h, n, ptr(mk), None, ptr(ac), cap, ptr(pk), None),
+                L.mrts_policy_head_unpack_dev(h.h, n, ptr(pk), 2, cap, None, ptr(mk.clone()), ptr(ac.clone()), None),
+                L.mrts_policy_head_score_packed_dev(h.h, n, ptr(lg), ptr(pk), 2, cap, None, None, None, None),
+                L.mrts_policy_head_grad_packed_dev(h.h, n, ptr(lg), ptr(pk), 2, cap, None, None, None, ptr(lg.clone()), None)]
 
     for h in (bots._h, fm._h):
         for rc in calls(h, 4):
@@ -300,11 +290,11 @@ def test_refusals():
         assert calls(h, cap) == [-22] * 4 and "cap" in L.mrts_last_error().decode()
     assert calls(h, 4, n=-1) == [-22] * 4
     # three rows of two packed rows without an index; no packed rows
-    assert L.mrts_policy_head_score_packed_dev(h.h, 3, _p(lg), _p(pk), 2, 4, None, None, None, None) == -22
-    assert L.mrts_policy_head_score_packed_dev(h.h, 2, _p(lg), _p(pk), 0, 4, None, None, None, None) == -22
-    assert L.mrts_policy_head_pack_dev(h.h, 2, _p(mk), None, _p(ac), 4, None, None) == -22
-    assert L.mrts_policy_head_score_packed_dev(h.h, 2, _p(lg), None, 2, 4, None, None, None, None) == -22
-    assert L.mrts_policy_head_grad_packed_dev(h.h, 2, _p(lg), _p(pk), 2, 4, None, None, None, None, None) == -22
+    assert L.mrts_policy_head_score_packed_dev(h.h, 3, ptr(lg), ptr(pk), 2, 4, None, None, None, None) == -22
+    assert L.mrts_policy_head_score_packed_dev(h.h, 2, ptr(lg), ptr(pk), 0, 4, None, None, None, None) == -22
+    assert L.mrts_policy_head_pack_dev(h.h, 2, ptr(mk), None, ptr(ac), 4, None, None) == -22
+    assert L.mrts_policy_head_score_packed_dev(h.h, 2, ptr(lg), None, 2, 4, None, None, None, None) == -22
+    assert L.mrts_policy_head_grad_packed_dev(h.h, 2, ptr(lg), ptr(pk), 2, 4, None, None, None, None, None) == -22
     assert L.mrts_policy_head_pack_status(h.h, None) == -22 and L.mrts_policy_head_pack_status(h.h, ctypes.byref(v)) == 0
     for bad in (0, 65):
         with pytest.raises(ValueError, match="cap"):

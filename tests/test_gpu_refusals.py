@@ -8,6 +8,7 @@ import os
 import numpy as np
 import pytest
 
+from tests.gpu_support import torch_gpu
 from tests import oracle_py, refusal_cases
 
 GOLDEN = os.path.join(refusal_cases.ROOT, "tests", "golden", "refusals_parent.json")
@@ -15,9 +16,7 @@ GOLDEN = os.path.join(refusal_cases.ROOT, "tests", "golden", "refusals_parent.js
 
 @pytest.mark.gpu
 def test_gpu_refusals_are_the_parents():
-    import torch
-
-    assert torch.cuda.is_available()
+    torch = torch_gpu()
     want = json.load(open(GOLDEN))
     L, lib_mod, env, fm = refusal_cases.handles()
     got = refusal_cases.answers(L, lib_mod, env, fm)

@@ -19,9 +19,7 @@ import pytest
 
 from tests import oracle_py
 from tests import steady_carry_cases as C
-from tests.test_gpu_every_shape import _same
-from tests.test_gpu_steady_instance import _assert_same, _torch
-from tests.test_state_json import dump_xy_free
+from tests.gpu_support import assert_matches_oracle, assert_same_outputs, torch_gpu
 
 pytestmark = pytest.mark.gpu
 
@@ -45,7 +43,7 @@ def _env(c, general):
     return e
 
 
-def _against_oracle(torch, E, c, n, tag):
+def _against_oracle(E, c, n, tag):
     """Handle E after its first n steps against the oracle's n steps from the same start."""
     S = 2 * C.GAMES
     ref = oracle_py.OracleVecClient(S, 0, c["max_steps"], [c["map"]] * S, seed=C.GAME_SEED)
@@ -56,42 +54,33 @@ def _against_oracle(torch, E, c, n, tag):
     for step in range(n):
         m = ref.get_masks(0)
         ref.step(np.stack([oracle_py.policy(m[s], SEED, s, step, 0) for s in range(S)]))
-    E.synchronize()
     m = ref.get_masks(0)
-    _same(torch, "obs", E.obs, ref.obs, tag)
-    _same(torch, "reward", E.reward, ref.reward, tag)
-    _same(torch, "done", E.done, ref.done, tag)
-    _same(torch, "masks", E.masks, m, tag)
-    acts = E.actions.cpu().numpy()
-    for s in range(8):
-        assert np.array_equal(acts[s], oracle_py.policy(m[s], SEED, s, n, 0)), f"{tag}: next action rows of slot {s}"
-    for s in range(0, S, 2):
-        assert np.array_equal(dump_xy_free(E.dump_state(s)), dump_xy_free(ref.dump(s))), f"{tag}: state of slot {s}"
-        assert int(E._h.env_steps()[s]) == ref.env_steps(s), f"{tag}: env steps of slot {s}"
+    nxt = np.stack([oracle_py.policy(m[s], SEED, s, n, 0) for s in range(8)])
+    assert_matches_oracle(E, ref, tag, next_rows=nxt, states="even", xy_free=True, env_steps=True)
     ref.close()
 
 
 @pytest.mark.parametrize("name", list(C.CASES))
 def test_carried_state_equals_rederived(name):
-    torch = _torch()
+    torch_gpu()
     c = C.CASES[name]
     A, B = _env(c, False), _env(c, True)
-    _assert_same(torch, A, B, f"{name}: before the first call")
+    assert_same_outputs(A, B, f"{name}: before the first call")
     n_or = c["oracle_steps"]
     k = 0
     for n in c["calls"]:
         A.rollout_fused(SEED, k + 1, n)
         B.rollout_fused(SEED, k + 1, n)
         k += n
-        _assert_same(torch, A, B, f"{name}: after the call to step {k}")
+        assert_same_outputs(A, B, f"{name}: after the call to step {k}")
         if k == n_or:  # the steady handle itself, where its first call ends at the oracle's horizon
-            _against_oracle(torch, A, c, n_or, f"{name}: steady vs oracle after {n_or} steps")
+            _against_oracle(A, c, n_or, f"{name}: steady vs oracle after {n_or} steps")
     if n_or and n_or not in np.cumsum(c["calls"]):
         # the case's calls do not end there (one call of 90 keeps the resets strictly inside the launch): a third
         # handle, same seed, runs the steady instance for the oracle's horizon alone
         O = _env(c, False)
         O.rollout_fused(SEED, 1, n_or)
-        _against_oracle(torch, O, c, n_or, f"{name}: steady vs oracle after {n_or} steps")
+        _against_oracle(O, c, n_or, f"{name}: steady vs oracle after {n_or} steps")
         O.close()
     if c["max_steps"] < k:
         assert (A._h.env_steps() == k % c["max_steps"]).all(), "no auto-reset happened"

@@ -10,11 +10,12 @@ game's state dump.
 """
 import ctypes
 
-import numpy as np
 import pytest
 
+from tests.defs import SEED
+from tests.gpu_support import assert_same_outputs, torch_gpu
+
 MAP = "maps/16x16/basesWorkers16x16.xml"
-SEED = 0x5EEDC0DE
 
 # mrts_internal_steady_probe's deviations from the steady state, in its order (mrts_kernels.hip)
 DEVIATIONS = ["n_iter == 1", "8x8 shape", "partial observability", "a bot game", "a LightRush handle", "mask_delta off",
@@ -36,13 +37,6 @@ def test_predicate_picks_the_general_instance_for_every_single_deviation():
     assert probe(len(DEVIATIONS)) == -1, "the library knows a deviation this test does not name"
 
 
-def _torch():
-    import torch
-
-    assert torch.cuda.is_available(), "GPU tests need an MI355X"
-    return torch
-
-
 def _env(S, max_steps, general, ring):
     from microrts_amd import DeviceVecEnv
 
@@ -53,18 +47,6 @@ def _env(S, max_steps, general, ring):
     e.reset()
     e.random_policy(SEED, 0)
     return e
-
-
-def _assert_same(torch, A, B, tag):
-    A.synchronize()
-    B.synchronize()
-    for name in ("obs", "masks", "actions", "source", "reward", "done"):
-        assert torch.equal(getattr(A, name), getattr(B, name)), f"{tag}: {name}"
-    assert np.array_equal(A.error_flags(), B.error_flags()), f"{tag}: error flags"
-    assert not A.error_flags().any(), f"{tag}: error flags set"
-    assert np.array_equal(A._h.env_steps(), B._h.env_steps()), f"{tag}: env steps"
-    for s in range(0, A._h.S, 2):
-        assert np.array_equal(A.dump_state(s), B.dump_state(s)), f"{tag}: state of slot {s}"
 
 
 # (slots, max_steps, steps of each call): 3 games x 2 calls of 5 — not a multiple of 512 games, no balanced
@@ -78,16 +60,16 @@ SHAPES = {"6x5": (12, 2000, (5, 5)), "512x70": (1024, 2000, (70, 70)), "512x90_r
 @pytest.mark.parametrize("shape", list(SHAPES))
 def test_steady_equals_general(shape):
     """Two handles, same seed, same rollout_fused calls: one in the steady state, one held on the general instance."""
-    torch = _torch()
+    torch_gpu()
     S, max_steps, calls = SHAPES[shape]
     A, B = _env(S, max_steps, False, max(calls)), _env(S, max_steps, True, max(calls))
-    _assert_same(torch, A, B, f"{shape}: after reset")
+    assert_same_outputs(A, B, f"{shape}: after reset")
     k = 0
     for n in calls:
         A.rollout_fused(SEED, k + 1, n)
         B.rollout_fused(SEED, k + 1, n)
         k += n
-        _assert_same(torch, A, B, f"{shape}: after the call to step {k}")
+        assert_same_outputs(A, B, f"{shape}: after the call to step {k}")
     if max_steps < k:
         assert (A._h.env_steps() < max_steps).all() and (A._h.env_steps() == k % max_steps).all(), "no auto-reset happened"
     A.close()
@@ -98,7 +80,7 @@ def test_steady_equals_general(shape):
 def test_one_handle_alternating_instances():
     """steady -> general -> steady on one handle, mid-episode, against a twin that stays general: the forwarded
     action rows, the mask row sets and the game placement carry over between the instances."""
-    torch = _torch()
+    torch_gpu()
     S, ring = 1024, 70
     A, B = _env(S, 2000, False, ring), _env(S, 2000, True, ring)
     k = 0
@@ -107,6 +89,6 @@ def test_one_handle_alternating_instances():
         A.rollout_fused(SEED, k + 1, n)
         B.rollout_fused(SEED, k + 1, n)
         k += n
-        _assert_same(torch, A, B, f"after the {'general' if general else 'steady'} call to step {k}")
+        assert_same_outputs(A, B, f"after the {'general' if general else 'steady'} call to step {k}")
     A.close()
     B.close()

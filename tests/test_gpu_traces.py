@@ -26,6 +26,7 @@ import os
 import numpy as np
 import pytest
 
+from tests.gpu_support import torch_gpu
 from tests import oracle_py
 
 pytestmark = pytest.mark.gpu
@@ -38,9 +39,7 @@ TRACE_ISSUED, TRACE_GAMEOVER, TRACE_NO_UNIT = 1, 2, 4
 def _replay(entries_list, maps, generic, oracle=None, corrupt=None):
     """Replay the traces of one map size as the games of one forward-model handle.  Returns the number
     of entries checked; with `corrupt`, returns at the first mismatch instead (index of that entry)."""
-    import torch
-
-    assert torch.cuda.is_available(), "GPU tests need an MI355X"
+    torch_gpu()
     from microrts_amd import ForwardModel
 
     n = len(entries_list)

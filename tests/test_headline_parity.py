@@ -23,20 +23,15 @@ import os
 import numpy as np
 import pytest
 
-from tests import oracle_py
+from tests import dumps, oracle_py
+from tests.defs import SEED
+from tests.gpu_checks import record_exchange_loopback_ranks
+from tests.gpu_support import assert_matches_oracle, assert_same_outputs, torch_gpu
 
 pytestmark = pytest.mark.gpu
 
-SEED = 0x5EEDC0DE
 ROOT = os.path.dirname(os.path.dirname(os.path.abspath(__file__)))
 BURNIN = 1000
-
-
-def _torch():
-    import torch
-
-    assert torch.cuda.is_available(), "GPU tests need an MI355X"
-    return torch
 
 
 def _pick_games(n_games, per=2):
@@ -78,20 +73,12 @@ class _MaskedReplica:
 
 
 def _compare_launch_end(env, rep, tag):
-    env.synchronize()
-    ref, picks = rep.ref, rep.picks
-    assert np.array_equal(env.obs.cpu().numpy()[picks], ref.obs), f"{tag}: observations"
-    assert np.array_equal(env.reward.cpu().numpy()[picks], ref.reward), f"{tag}: rewards"
-    assert np.array_equal(env.done.cpu().numpy()[picks], ref.done), f"{tag}: dones"
-    m, nxt = rep.actions(rep.t)  # the rows the launch sampled for the next step
-    assert np.array_equal(env.masks.cpu().numpy()[picks], m), f"{tag}: masks"
-    assert np.array_equal(env.actions.cpu().numpy()[picks], nxt), f"{tag}: next action rows"
-    for i, s in enumerate(picks):
-        assert np.array_equal(env.dump_state(s), ref.dump(i)), f"{tag}: state of slot {s}"
+    _, nxt = rep.actions(rep.t)  # the rows the launch sampled for the next step
+    assert_matches_oracle(env, rep.ref, tag, slots=rep.picks, next_rows=nxt)
 
 
 def _masked_multi_step(mp, n_games, seed, partial_obs=False, max_units=0):
-    _torch()
+    torch_gpu()
     from microrts_amd import DeviceVecEnv
 
     S = 2 * n_games
@@ -130,7 +117,7 @@ def test_full_size_c2_multi_step():
     """BASELINE configs[1] (c2) as bench.py times it: 1024 games on basesWorkers8x8, unmasked uniform
     rows drawn by the step kernel, K steps per launch.  The oracle draws the same rows itself
     (oracle_py.policy_uniform = mrts_policy_uniform_dev's Philox stream)."""
-    _torch()
+    torch_gpu()
     from microrts_amd import DeviceVecEnv
 
     E = 1024
@@ -153,15 +140,8 @@ def test_full_size_c2_multi_step():
     for n in (BURNIN, 20, 200):
         env.rollout_uniform(SEED, t, n, fused=True)
         ref_run(n)
-        env.synchronize()
-        tag = f"c2 after a {n}-step rollout (step {t})"
-        assert np.array_equal(env.obs.cpu().numpy()[picks], ref.obs), f"{tag}: observations"
-        assert np.array_equal(env.reward.cpu().numpy()[picks], ref.reward), f"{tag}: rewards"
-        assert np.array_equal(env.done.cpu().numpy()[picks], ref.done), f"{tag}: dones"
-        last = np.stack([oracle_py.policy_uniform(H, W, K, SEED, s, t - 1) for s in picks])
-        assert np.array_equal(env.actions.cpu().numpy()[picks], last), f"{tag}: the last step's rows"
-        for i, s in enumerate(picks):
-            assert np.array_equal(env.dump_state(s), ref.dump(i)), f"{tag}: state of slot {s}"
+        last = np.stack([oracle_py.policy_uniform(H, W, K, SEED, s, t - 1) for s in picks])  # the last step's rows
+        assert_matches_oracle(env, ref, f"c2 after a {n}-step rollout (step {t})", slots=picks, masks=None, next_rows=last)
     assert not env.error_flags().any()
     env.close()
     ref.close()
@@ -177,7 +157,7 @@ def test_all_maps_load_product_path():
     The reset observation and the canonical state dump equal the oracle's parse.  Maps above 64x64
     cells run with max_units 1024 (their full unit capacity does not fit one CU's LDS; the largest
     map holds 64 units)."""
-    _torch()
+    torch_gpu()
     from microrts_amd import DeviceVecEnv
 
     assert len(MAPS) == 140
@@ -204,7 +184,7 @@ def test_c_abi_fused_write_needs_invalidate():
     counter involved): rows written into d_actions between fused calls are used iff
     mrts_policy_invalidate() is called — then the step equals a plain mrts_step_dev of those rows on
     a twin handle; without it they are ignored (the documented contract, shown here to hold)."""
-    torch = _torch()
+    torch = torch_gpu()
     from microrts_amd import DeviceVecEnv
 
     n = 16
@@ -273,7 +253,7 @@ def test_native_exchange_one_rank(mp, uniform, u8):
     (the last step's in send[(n - 1) % 2]); with mrts_set_exchange_bytes(1) the same as uint8 (refused
     on a shape no uint8 render writes); a second mrts_exchange_init and a partially observable
     handle are refused."""
-    torch = _torch()
+    torch = torch_gpu()
     from microrts_amd import DeviceVecEnv
 
     n_sp = 64
@@ -329,7 +309,7 @@ def test_native_exchange_graph_replay():
     """mrts_capture_begin / _end / mrts_replay around an exchange rollout: the replay reruns the
     captured steps verbatim — from the same start state it produces the same buffers as the eager call
     (observations, masks, next actions, states, and the all-gathered int16 observation)."""
-    torch = _torch()
+    torch = torch_gpu()
     from microrts_amd import DeviceVecEnv
 
     mp, n_sp = "maps/16x16/basesWorkers16x16.xml", 32
@@ -352,15 +332,9 @@ def test_native_exchange_graph_replay():
     torch.cuda.synchronize()
     B.restore(ck)  # capture ran nothing: the replay starts from the same state
     B.replay()
-    A.synchronize()
-    B.synchronize()
-    for name in ("obs", "reward", "done", "masks", "actions"):
-        assert torch.equal(getattr(A, name), getattr(B, name)), name
-    for s in range(0, n_sp, 2):
-        assert np.array_equal(A.dump_state(s), B.dump_state(s)), f"state slot {s}"
+    assert_same_outputs(A, B, "replay vs eager")
     assert torch.equal(bufs[0][1], bufs[1][1])
     for e in (A, B):
-        assert not e.error_flags().any()
         e.close()
 
 
@@ -371,7 +345,7 @@ def test_values_beyond_a_byte_after_injection():
     steps and in multi-step launches — and the uint8 transport must then be refused."""
     import json
 
-    torch = _torch()
+    torch = torch_gpu()
     from microrts_amd import DeviceVecEnv
 
     mp, n_sp = "maps/16x16/basesWorkers16x16.xml", 8
@@ -406,7 +380,7 @@ def test_values_beyond_a_byte_after_injection():
 def test_exchange_needs_an_observation_buffer():
     """the exchange's send buffers are written by the step's observation write, so an
     exchange rollout without d_obs would all-gather stale data — it is refused (-EINVAL)."""
-    torch = _torch()
+    torch = torch_gpu()
     from microrts_amd import DeviceVecEnv
 
     mp, n_sp = "maps/16x16/basesWorkers16x16.xml", 4
@@ -449,7 +423,7 @@ def test_record_exchange_one_rank(mp, uniform, spl, max_steps, po):
     (the 64-unit record): full observability on a map that starts with 64 units, records
     sized to the map's cell count (one unit per cell at most, so no game can overflow them) — the games pass
     64 live units (the general paths beyond one wave) and every step still renders exactly."""
-    torch = _torch()
+    torch = torch_gpu()
     from microrts_amd import DeviceVecEnv
 
     many = po == "many"
@@ -505,7 +479,7 @@ def test_record_exchange_one_rank(mp, uniform, spl, max_steps, po):
         for s in range(0, n_sp, 2):
             d = A.dump_state(s)
             assert np.array_equal(d, B.dump_state(s)), f"state slot {s} after {k}"
-            most = max(most, int(d[4]))
+            most = max(most, dumps.n_units(d))
     for e in (A, B):
         assert not e.error_flags().any()
     if po == "dead":
@@ -531,7 +505,7 @@ def test_step_responses_every_reward_function():
     uniform one): every step's ring entry equals the reward / done a twin returns from one launch per step,
     across auto-resets (max_steps 60 and gameovers); d_reward / d_done are left alone while the ring is on;
     a call longer than the ring is refused; NULL turns it off (then the plain buffers again)."""
-    torch = _torch()
+    torch = torch_gpu()
     from microrts_amd import DeviceVecEnv
     from microrts_amd._lib import REWARD_FUNCTIONS
 
@@ -595,7 +569,7 @@ def test_records_onehot_batch(mp, spl):
     8-rank loopback exchange — rendered from the records straight into MicroRTS-Py's one-hot layout equals
     the twin's int32 observation of the same slot (rank r's slot s = the twin's slot s + 2 (r - rank), the
     loopback's rotation) through mrts_onehot_dev, every step of 1 + 30 + 12 records steps."""
-    torch = _torch()
+    torch = torch_gpu()
     from microrts_amd import DeviceVecEnv
 
     n_sp, world, rank = 64, 8, 3
@@ -670,80 +644,4 @@ def test_record_exchange_loopback_ranks(mp, po, spl, world, rank):
     receive buffer too (rotated by slots).  And the chunk schedule does not depend on whether a handle is
     in the steady fused state: a twin made unsteady by a get_masks call reports the same
     per-step offsets."""
-    torch = _torch()
-    from microrts_amd import DeviceVecEnv
-
-    n_sp = 64
-    kw = dict(partial_obs=True, max_units=256) if po else {}
-    A = DeviceVecEnv(n_sp, 0, 300, [mp] * n_sp, seed=29, **kw)
-    B = DeviceVecEnv(n_sp, 0, 300, [mp] * n_sp, seed=29, **kw)
-    C = DeviceVecEnv(n_sp, 0, 300, [mp] * n_sp, seed=29, **kw)  # B's twin, never in the steady state at a call
-    A.set_multi_step(False)
-    for e in (A, B, C):
-        e.reset()
-        e.random_policy(SEED, 0)
-    L, h = B._h.L, B._h.h
-    assert L.mrts_exchange_init_loopback(h, world, world) != 0  # rank out of range
-    assert L.mrts_exchange_init_loopback(h, world, rank) == 0
-    assert L.mrts_exchange_init_loopback(h, world, rank) != 0  # already initialised
-    assert L.mrts_exchange_init_loopback(C._h.h, world, rank) == 0
-    words = B.set_records(64, spl)
-    assert C.set_records(64, spl) == words
-    distinct = 0  # steps whose games differed, so that a wrong rank place would have shown
-    G = n_sp // 2
-    k = 0
-    for n in (1, 40, 25):
-        want = []
-        for j in range(n):
-            A.rollout_fused(SEED, k + j + 1, 1)
-            A.synchronize()
-            want.append(A.obs.clone())
-        recv = B.records_buffer(n, world)
-        recv.fill_(-7)  # every record header the exchange owes must be written (unit words past n are don't-care)
-        off = B.rollout_fused_records(SEED, k + 1, n, recv)
-        C.get_masks()  # C leaves the steady fused state: its first launch of the call runs one step alone
-        recvC = C.records_buffer(n, world)
-        recvC.fill_(-7)  # (as recv: unit words past a record's n stay as they were)
-        offC = C.rollout_fused_records(SEED, k + 1, n, recvC)
-        assert np.array_equal(off, offC), "the chunk schedule must not depend on the steady state"
-        k += n
-        B.synchronize()
-        C.synchronize()
-        assert torch.equal(recv, recvC)
-        for j in range(n):
-            o, stride = int(off[j, 0]), int(off[j, 1])
-            assert stride >= G * words and (o + (world - 1) * stride + G * words) <= recv.numel()
-            mine = recv[o + rank * stride:o + rank * stride + G * words]
-            assert not bool((mine.view(G, words)[:, 0] == -7).any()), f"step {k - n + j}: a record header never written"
-            for r in range(world):  # peer r: this rank's game (g + r - rank) mod G at its game g
-                peer = recv[o + r * stride:o + r * stride + G * words].view(G, words)
-                assert torch.equal(peer, torch.roll(mine.view(G, words), -(r - rank), 0)), f"step {k - n + j}: rank {r}"
-            out = torch.zeros((world * 2 * G,) + tuple(B.obs.shape[1:]), dtype=torch.int32, device=B.device)
-            B.render_records(recv, o, stride, world, out)
-            B.synchronize()
-            for r in range(world):
-                assert torch.equal(out[r * 2 * G:(r + 1) * 2 * G], torch.roll(want[j], -2 * (r - rank), 0)), \
-                    f"step {k - n + j}: rendered rank {r}"
-            # the check can fail: once the games differ, the neighbour's place rendered as this rank's is not
-            # this rank's observation (right after a reset every game may still look the same)
-            if not torch.equal(torch.roll(want[j], -2, 0), want[j]):
-                nb = (rank + 1) % world
-                wrong = torch.zeros_like(B.obs)
-                B.render_records(recv, o + nb * stride, stride, 1, wrong)
-                B.synchronize()
-                assert not torch.equal(wrong, want[j]), f"step {k - n + j}: a neighbour's place renders like this rank's"
-                distinct += 1
-        assert torch.equal(A.obs, B.obs) and torch.equal(A.masks, B.masks)
-    if not po:  # the per-step tensor exchange: [ranks][slots][C][H][W]
-        send = [torch.zeros(tuple(B.obs.shape), dtype=torch.int16, device=B.device) for _ in range(2)]
-        tr = torch.full((world,) + tuple(B.obs.shape), -7, dtype=torch.int16, device=B.device)
-        A.rollout_fused(SEED, k + 1, 3)
-        B.rollout_fused_exchange(SEED, k + 1, 3, send, tr)
-        A.synchronize()
-        B.synchronize()
-        for r in range(world):  # peer r: this rank's slot (i + r - rank) mod slots at its slot i
-            assert torch.equal(tr[r], torch.roll(A.obs.to(torch.int16), -(r - rank), 0)), f"tensor exchange rank {r}"
-    assert distinct > 10, "the games never differed: the rank checks could not fail"
-    for e in (A, B, C):
-        assert not e.error_flags().any()
-        e.close()
+    record_exchange_loopback_ranks(mp, po, spl, world, rank)

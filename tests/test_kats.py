@@ -19,53 +19,16 @@ Attack index = (3 + dy) * 7 + (3 + dx) (maxAttackRadius 7, JNIGridnetClient.java
 import numpy as np
 import pytest
 
-from tests import oracle_py
-
-NONE, MOVE, HARVEST, RETURN, PRODUCE, ATTACK = range(6)
-RESOURCE, BASE, BARRACKS, WORKER, LIGHT, HEAVY, RANGED = range(7)
-UP, RIGHT, DOWN, LEFT = range(4)
-NAMES = {RESOURCE: "Resource", BASE: "Base", BARRACKS: "Barracks", WORKER: "Worker", LIGHT: "Light",
-         HEAVY: "Heavy", RANGED: "Ranged"}
-HP = {RESOURCE: 1, BASE: 10, BARRACKS: 4, WORKER: 1, LIGHT: 4, HEAVY: 4, RANGED: 1}
-
-
-def atk(dx, dy):
-    return (3 + dy) * 7 + (3 + dx)
-
-
-def write_map(path, W, H, units, walls=(), res=(5, 5)):
-    """units: (type, player, x, y[, resources[, hp]]) in list order."""
-    terr = ["0"] * (W * H)
-    for x, y in walls:
-        terr[y * W + x] = "1"
-    lines = [f'<rts.PhysicalGameState width="{W}" height="{H}">', f"  <terrain>{''.join(terr)}</terrain>", "  <players>"]
-    for i, r in enumerate(res):
-        lines += [f'    <rts.Player ID="{i}" resources="{r}">', "    </rts.Player>"]
-    lines += ["  </players>", "  <units>"]
-    for i, u in enumerate(units):
-        t, p, x, y = u[:4]
-        r = u[4] if len(u) > 4 else 0
-        hp = u[5] if len(u) > 5 else HP[t]
-        lines += [f'    <rts.units.Unit type="{NAMES[t]}" ID="{100 + i}" player="{p}" x="{x}" y="{y}" resources="{r}" '
-                  f'hitpoints="{hp}" >', "    </rts.units.Unit>"]
-    lines += ["  </units>", "</rts.PhysicalGameState>"]
-    with open(path, "w") as f:
-        f.write("\n".join(lines) + "\n")
-    return str(path)
-
+from tests import dumps, oracle_py
+from tests.defs import (ATTACK, BARRACKS, BASE, DOWN, HARVEST, HEAVY, HP, LEFT, LIGHT, MOVE, NONE, PRODUCE, RANGED, RESOURCE,
+                        RETURN, RIGHT, UP, WORKER, atk, row, write_map)
+from tests.gpu_support import torch_gpu
 
 def parse(d):
-    d = [int(v) for v in d]
-    out = {"time": d[0], "res": (d[2], d[3])}
-    n = d[4]
-    out["units"] = [tuple(d[5 + 6 * i:11 + 6 * i]) for i in range(n)]
-    k = 5 + 6 * n
-    out["assign"] = [tuple(d[k + 1 + 7 * i:k + 8 + 7 * i]) for i in range(d[k])]
-    return out
-
-
-def row(pos, t=NONE, move=0, harvest=0, ret=0, pdir=0, ptype=0, attack=0):
-    return [pos, t, move, harvest, ret, pdir, ptype, attack]
+    """A dump as plain ints and tuples, so that a KAT states what it expects as literals."""
+    s = dumps.parse(d)
+    return {"time": s.time, "res": s.res, "units": [tuple(u) for u in s.units.tolist()],
+            "assign": [tuple(a) for a in s.assign.tolist()]}
 
 
 class Runner:
@@ -79,12 +42,9 @@ class Runner:
                                                rewards=[oracle_py.REWARD_IDS[r] for r in rfs] if rfs else None)
             self.e.reset()
         else:
-            import torch
-
-            assert torch.cuda.is_available(), "GPU KATs need an MI355X"
             from microrts_amd import DeviceVecEnv
 
-            self.torch = torch
+            self.torch = torch_gpu()
             self.e = DeviceVecEnv(2, 0, max_steps, [map_path] * 2, partial_obs=partial_obs, rfs=rfs)
             self.e.reset()
 
@@ -513,9 +473,7 @@ def _ranged_window_kat(tmp, backend, W, H, po=False, max_units=0):
     if backend == "oracle":
         obs, masks = ref_obs, ref_masks
     else:
-        import torch
-
-        assert torch.cuda.is_available(), "GPU KATs need an MI355X"
+        torch_gpu()
         from microrts_amd import DeviceVecEnv
 
         e = DeviceVecEnv(S, 0, 2000, maps, partial_obs=po, max_units=max_units)

@@ -8,6 +8,7 @@ import pytest
 
 from microrts_amd import _lib
 from microrts_amd.vec_client import _bot_kind
+from tests.headers import internal_header
 
 ROOT = os.path.dirname(os.path.dirname(os.path.abspath(__file__)))
 
@@ -36,31 +37,12 @@ def test_header_enum_matches_the_binding():
     assert got["MRTS_BOT_LIGHT_RUSH"] == 2
 
 
-def _internal_header():
-    """The integer constants and one-line constexpr functions of mrts_internal.h, as Python (C's / on non-negative
-    ints is //)."""
-    txt = open(os.path.join(ROOT, "microrts_amd", "csrc", "mrts_internal.h")).read()
-    txt = re.sub(r"//[^\n]*", "", txt)
-    env = {}
-    for body in re.findall(r"enum(?:\s*:\s*\w+)?\s*\{([^}]*)\}", txt):
-        for k, v in re.findall(r"(\w+)\s*=\s*(\d+)\s*(?:,|$)", body):
-            env[k] = int(v)
-    for k, v in re.findall(r"constexpr\s+int\s+(\w+)\s*=\s*(\d+)\s*;", txt):
-        env[k] = int(v)
-    for name, args, expr in re.findall(r"constexpr\s+int\s+(\w+)\s*\(([^)]*)\)\s*\{\s*return\s+([^;]*);\s*\}", txt):
-        params = [a.split()[-1] for a in args.split(",") if a.strip()]
-        if "?" in expr:
-            continue
-        env[name] = eval(f"lambda {', '.join(params)}: {expr.replace('/', '//')}", env)
-    return env
-
-
 @pytest.mark.parametrize("cap,hw", [(128, 64), (320, 256), (320, 1024), (1280, 1024)], ids=["c2", "c3", "c5", "32x32-full"])
 def test_state_words_without_lightrush_is_unchanged(cap, hw):
     """stateWords(CAP, HW) is what it was before the bot memory existed: header, 7 unit arrays, the two previous
     mask row sets, the terrain bytes and the 64 forwarded action words; the LightRush memory is a separate
     botWords(CAP), appended only in handles that have a LightRush game."""
-    h = _internal_header()
+    h = internal_header()
     want = 16 + 7 * cap + 2 * ((hw + 31) // 32) + (hw + 3) // 4 + 64
     assert h["stateWords"](cap, hw) == want
     assert {(128, 64): 996, (320, 256): 2400, (320, 1024): 2640}.get((cap, hw), want) == want

@@ -9,8 +9,7 @@ import pytest
 
 from microrts_amd import _lib
 from tests import obs_pack_ref as OR
-from tests.test_abi_cpu import header_symbols
-from tests.test_lightrush_cpu import _internal_header
+from tests.headers import header_symbols, internal_header
 
 ROOT = os.path.dirname(os.path.dirname(os.path.abspath(__file__)))
 ENTRY_POINTS = ["mrts_obs_packed_words", "mrts_obs_pack_dev", "mrts_obs_unpack_dev", "mrts_obs_onehot_packed_dev",
@@ -28,7 +27,7 @@ def test_header_and_binding_name_the_entry_points():
 # 1 + 2 * cap + (C - 5) * ceil(H*W / 32); (8, 32x32, 128) is 1 + 256 + 3 * 32
 @pytest.mark.parametrize("C,HW,cap,want", [(6, 256, 128, 265), (8, 1024, 128, 353), (6, 72, 72, 148)])
 def test_word_count_formula(C, HW, cap, want):
-    f = _internal_header()["obsPackedWords"]
+    f = internal_header()["obsPackedWords"]
     assert want == 1 + 2 * cap + (C - 5) * -(-HW // 32)
     assert f(C, HW, cap) == want == OR.words(C, HW, cap)
 

@@ -6,8 +6,7 @@ import numpy as np
 import pytest
 
 from tests import oracle_py
-
-SEED = 0x5EEDC0DE
+from tests.defs import SEED
 
 
 @pytest.mark.parametrize("mp,po,uniform,base", [("maps/16x16/basesWorkers16x16.xml", False, False, 0),

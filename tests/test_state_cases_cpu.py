@@ -1,7 +1,7 @@
 """tests.state_cases on the oracle alone: the state source of tests/test_gpu_every_shape.py.
 
 * every picked entry of every recorded game survives dump -> GameState.toJSON text -> set_state_json ->
-  dump (under dump_xy_free: UnitAction.fromJSON leaves x / y of non-attack actions at -1);
+  dump (under dumps.xy_free: UnitAction.fromJSON leaves x / y of non-attack actions at -1);
 * the case list the GPU test imports reaches what it is there for.  These are conditions, asserted so
   that a later change to the generator cannot empty the GPU test silently: on a miss, change the
   generator's parameters or seed for that size, not the condition;
@@ -14,7 +14,7 @@ import pytest
 
 from tests import oracle_py
 from tests import state_cases as SC
-from tests.test_state_json import dump_xy_free
+from tests.dumps import xy_free
 
 _id = lambda size: f"{size[1]}x{size[0]}"  # noqa: E731
 
@@ -36,7 +36,7 @@ def test_trace_states_round_trip(size):
     for mp, fx, k, dump in st:
         s = 2 * maps.index(mp)
         ref.set_state_json(s, SC.dump_to_json(tm[mp], dump))
-        assert np.array_equal(dump_xy_free(ref.dump(s)), dump_xy_free(dump)), f"{fx} entry {k}"
+        assert np.array_equal(xy_free(ref.dump(s)), xy_free(dump)), f"{fx} entry {k}"
         assert ref.env_steps(s) == 0
     ref.close()
 

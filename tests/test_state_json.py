@@ -11,6 +11,8 @@ import numpy as np
 import pytest
 
 from tests import oracle_py
+from tests.dumps import xy_free
+from tests.gpu_support import torch_gpu
 from tests.state_json_invalid import BASE4X4_JSON, invalid_states
 
 M4 = "maps/4x4/base4x4.xml"
@@ -25,19 +27,6 @@ def normalise(text):
         u["ID"] = i
     for a in d["actions"]:
         a["ID"] = pos[a["ID"]]
-    return d
-
-
-def dump_xy_free(d):
-    """A canonical dump with x/y of non-attack assignments zeroed: UnitAction.fromJSON leaves them at
-    DIRECTION_NONE (-1) where a decoded action holds 0; only ATTACK_LOCATION reads them."""
-    d = np.array(d)
-    nu = int(d[4])
-    base = 5 + 6 * nu
-    for k in range(int(d[base])):
-        r = base + 1 + 7 * k
-        if d[r + 1] != 5:
-            d[r + 3] = d[r + 4] = 0
     return d
 
 
@@ -65,7 +54,7 @@ def test_oracle_json_round_trip_with_assignments():
     dump = ref.dump(0)
     ref.set_state_json(2, j)  # game 1 (slots 2, 3) becomes a copy of game 0
     assert ref.state_json(2) == j
-    assert np.array_equal(dump_xy_free(ref.dump(2)), dump_xy_free(dump))
+    assert np.array_equal(xy_free(ref.dump(2)), xy_free(dump))
     assert ref.env_steps(2) == 0
     ref.close()
 
@@ -73,17 +62,10 @@ def test_oracle_json_round_trip_with_assignments():
 # ------------------------------------------------------------------ GPU
 
 
-def _torch():
-    import torch
-
-    assert torch.cuda.is_available()
-    return torch
-
-
 @pytest.mark.gpu
 @pytest.mark.parametrize("mp,n_bot", [(M8, 2), ("maps/16x16/basesWorkers16x16.xml", 0)])
 def test_gpu_json_matches_oracle_and_injection(mp, n_bot):
-    torch = _torch()
+    torch = torch_gpu()
     from microrts_amd import DeviceVecEnv
 
     n_sp = 4
@@ -117,14 +99,14 @@ def test_gpu_json_matches_oracle_and_injection(mp, n_bot):
         assert np.array_equal(env.obs.cpu().numpy(), ref.obs), step
         assert np.array_equal(env.reward.cpu().numpy(), ref.reward), step
     for s in range(S):
-        assert np.array_equal(dump_xy_free(env.dump_state(s)), dump_xy_free(ref.dump(s)))
+        assert np.array_equal(xy_free(env.dump_state(s)), xy_free(ref.dump(s)))
     env.close()
     ref.close()
 
 
 @pytest.mark.gpu
 def test_gpu_set_state_json_rejects_invalid():
-    _torch()
+    torch_gpu()
     from microrts_amd import DeviceVecEnv
 
     env = DeviceVecEnv(2, 0, 2000, [M4] * 2)
@@ -146,7 +128,7 @@ def test_gpu_set_state_json_rejects_invalid():
 def test_gpu_checkpoint_restore_replays_identically(crs, bots):
     """A checkpoint holds the random streams too: CANCEL_RANDOM and RandomBiasedAI opponents replay
     the same after restore."""
-    torch = _torch()
+    torch = torch_gpu()
     from microrts_amd import DeviceVecEnv, UnitTypeTable
 
     S = 6 + bots
@@ -187,7 +169,7 @@ def test_gpu_restore_rejects_other_opponents_or_limits():
     vs RandomBiasedAI), another max_steps, other reward functions or other maps would silently run
     the checkpoint's game kinds until each game's next auto-reset.  The header carries a hash of
     those, and restore refuses a mismatch; the identical configuration restores."""
-    _torch()
+    torch_gpu()
     from microrts_amd import DeviceVecEnv
 
     base = dict(ai2s=["RandomBiasedAI"] * 2, seed=4)

@@ -11,7 +11,8 @@ import pytest
 from tests import oracle_py
 from tests import state_cases as SC
 from tests.state_json_invalid import BASE4X4_JSON, invalid_states
-from tests.test_state_json import dump_xy_free
+from tests import dumps
+from tests.dumps import xy_free
 
 _id = lambda size: f"{size[1]}x{size[0]}"  # noqa: E731
 
@@ -42,7 +43,7 @@ def probe(f, size, max_units, text, cap, utt_version=1, crs=1, utt_json=None):
 def test_round_trip_equals_the_oracles(lib, size):
     """One state per map size (a crowded one where the size has one: every unit type, both owners, assignments under
     way): the product's text after the round trip is the oracle's toJSON text of the same state, byte for byte, and
-    its dump is the oracle's (under dump_xy_free, as everywhere a dump follows fromJSON: UnitAction.fromJSON leaves
+    its dump is the oracle's (under dumps.xy_free, as everywhere a dump follows fromJSON: UnitAction.fromJSON leaves
     x / y of a non-attack action at -1 where the kernels' decoded action holds 0)."""
     c = SC.case(size)
     g = 1 if len(c["states"]) > 1 else 0
@@ -58,8 +59,9 @@ def test_round_trip_equals_the_oracles(lib, size):
     assert out.tobytes()[:n].decode() == want_json
     n, out, err = probe(lib.mrts_internal_dump_probe, size, c["max_units"], text, 1 << 18)
     assert n > 0, err
-    assert len(want_dump) == n and np.array_equal(dump_xy_free(out[:n]), dump_xy_free(want_dump))
-    assert np.array_equal(out[:5 + 6 * int(out[4])], want_dump[:5 + 6 * int(want_dump[4])]), "time, players and units exactly"
+    assert len(want_dump) == n and np.array_equal(xy_free(out[:n]), xy_free(want_dump))
+    got, want = dumps.parse(out[:n]), dumps.parse(want_dump)
+    assert got[:2] == want[:2] and np.array_equal(got.units, want.units), "time, players and units exactly"
 
 
 def test_invalid_states_are_refused_with_the_gpu_paths_codes(lib):

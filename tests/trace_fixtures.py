@@ -7,6 +7,8 @@ import xml.etree.ElementTree as ET
 
 import numpy as np
 
+from tests import dumps
+
 ROOT = os.path.dirname(os.path.dirname(os.path.abspath(__file__)))
 TR = os.path.join(ROOT, "tests", "golden", "traces")
 IDX = json.load(open(os.path.join(TR, "index.json")))
@@ -60,11 +62,10 @@ def issue_rows(acts):
 
 
 def check_vs_trace(dump, entry, tag):
-    time, (r0, r1), units, _ = entry
-    assert dump[0] == time, f"{tag}: time {dump[0]} vs {time}"
-    assert (dump[2], dump[3]) == (r0, r1), f"{tag}: player resources {dump[2:4]} vs {(r0, r1)}"
-    nu = int(dump[4])
-    assert nu == len(units), f"{tag}: unit count {nu} vs {len(units)}"
-    got = dump[5:5 + 6 * nu].reshape(-1, 6)
-    bad = np.nonzero((got != units).any(axis=1))[0]
-    assert len(bad) == 0, f"{tag}: unit {bad[0]} {got[bad[0]].tolist()} vs trace {units[bad[0]].tolist()}"
+    time, res, units, _ = entry
+    got = dumps.parse(dump)
+    assert got.time == time, f"{tag}: time {got.time} vs {time}"
+    assert got.res == tuple(res), f"{tag}: player resources {got.res} vs {tuple(res)}"
+    assert len(got.units) == len(units), f"{tag}: unit count {len(got.units)} vs {len(units)}"
+    bad = np.nonzero((got.units != units).any(axis=1))[0]
+    assert len(bad) == 0, f"{tag}: unit {bad[0]} {got.units[bad[0]].tolist()} vs trace {units[bad[0]].tolist()}"

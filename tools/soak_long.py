@@ -1,5 +1,5 @@
 #!/usr/bin/env python3
-"""Long every-game parity soak of the shipped kernels (round 6): tests/test_full_size_every_game.py's check — every
+"""Long every-game parity soak of the shipped kernels (round 6): tests/test_full_size_every_game.py's check (tests.gpu_checks.every_game) — every
 game of c3 / c5 / c2 in the bench's form (fused masked policy or fused uniform rows, delta masks, multi-step
 launches, c5's render helper wave) against oracle replicas stepping in native code — at other seeds and over a
 longer horizon with launches of several lengths: 1000 + 20 + 200 + 1040 + 777 + 2000 + 63 = 5100 steps, so every
@@ -19,7 +19,7 @@ ROOT = os.path.dirname(os.path.dirname(os.path.abspath(__file__)))
 sys.path.insert(0, ROOT)
 os.chdir(ROOT)
 
-from tests import test_full_size_every_game as T  # noqa: E402
+from tests import gpu_checks as T  # noqa: E402
 
 POINTS = (1000, 20, 200, 1040, 777, 2000, 63) * int(os.environ.get("SOAK_REPEAT", "1"))
 SEEDS = {"c3": (101, 211, 307), "c5": (103, 223, 311), "c2": (107, 227, 313)}
@@ -69,7 +69,7 @@ def main():
             t0 = time.time()
             err = None
             try:
-                T._every_game(cfg)
+                T.every_game(cfg)
             except AssertionError as e:
                 err = str(e)[:2000]
             print(json.dumps({"config": cfg, "form": form, "map": mp, "games": E, "env_seed": seed, "points": list(POINTS),
