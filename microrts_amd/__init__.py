@@ -2,7 +2,9 @@
 
 Drop-in for tests.JNIGridnetVecClient of the reference (src/tests/JNIGridnetVecClient.java).
 """
-from .vec_client import JNIGridnetVecClient, UnitTypeTable, DeviceVecEnv, ForwardModel  # noqa: F401
+from .vec_client import JNIGridnetVecClient, UnitTypeTable  # noqa: F401
+from .device_env import DeviceVecEnv  # noqa: F401
+from .forward_model import ForwardModel  # noqa: F401
 from .policy_head import evaluate_actions, evaluate_actions_packed  # noqa: F401
 
 __all__ = ["JNIGridnetVecClient", "UnitTypeTable", "DeviceVecEnv", "ForwardModel", "evaluate_actions", "evaluate_actions_packed"]

@@ -17,6 +17,12 @@ ERR_BITS = {
     1 << 4: "NEG_RESOURCES", 1 << 5: "MOVE_COLLISION", 1 << 6: "RECORD",
 }
 
+
+def err_bit(name):
+    """The MRTS_ERR_* bit that ERR_BITS names `name`"""
+    return next(bit for bit, n in ERR_BITS.items() if n == name)
+
+
 def _elf_sections(obj):
     """[(name, type, address, offset, size, link, entry size)] of a 64-bit little-endian ELF image, by section index"""
     import struct
@@ -81,17 +87,6 @@ def device_code_sha256(path=None):
     return hashlib.sha256(b"".join(_code_sections(o) for o in device_code_objects(path))).hexdigest()
 
 
-# every symbol include/mrts.h declares
-EXPORTS = [
-    "mrts_create", "mrts_dims", "mrts_reset", "mrts_step", "mrts_get_masks", "mrts_step_rows", "mrts_get_masks_i32",
-    "mrts_get_masks_host", "mrts_get_masks_i32_host",
-    "mrts_reset_dev", "mrts_step_dev", "mrts_get_masks_dev", "mrts_step_rows_dev", "mrts_get_masks_i32_dev", "mrts_onehot_features", "mrts_onehot_dev", "mrts_obs_packed_words", "mrts_obs_pack_dev", "mrts_obs_unpack_dev", "mrts_obs_onehot_packed_dev", "mrts_obs_packed_status", "mrts_policy_dev", "mrts_step_fused_dev", "mrts_rollout_fused_dev", "mrts_set_rollout_events", "mrts_rccl_unique_id", "mrts_exchange_init", "mrts_exchange_init_loopback", "mrts_rollout_fused_exchange_dev", "mrts_rollout_uniform_exchange_dev", "mrts_set_exchange_bytes", "mrts_set_records", "mrts_record_words", "mrts_rollout_fused_records_dev", "mrts_rollout_uniform_records_dev", "mrts_render_records_dev", "mrts_render_status", "mrts_render_records_onehot_dev", "mrts_set_step_responses", "mrts_capture_begin", "mrts_capture_end", "mrts_replay", "mrts_set_multi_step", "mrts_multi_step_capable", "mrts_set_obs16", "mrts_policy_uniform_dev", "mrts_step_uniform_dev", "mrts_rollout_uniform_dev", "mrts_policy_invalidate", "mrts_policy_head_sample_dev", "mrts_policy_head_score_dev", "mrts_policy_head_grad_dev", "mrts_policy_head_packed_words", "mrts_policy_head_pack_dev", "mrts_policy_head_pack_status", "mrts_policy_head_unpack_dev", "mrts_policy_head_score_packed_dev", "mrts_policy_head_grad_packed_dev", "mrts_set_obs_delta", "mrts_obs_invalidate", "mrts_set_source_output", "mrts_copy_games", "mrts_copy_games_dev", "mrts_playout", "mrts_playout_dev", "mrts_trace_step",
-    "mrts_evaluate", "mrts_evaluate_dev", "mrts_utt_json", "mrts_get_state_json",
-    "mrts_set_state_json", "mrts_checkpoint_size", "mrts_checkpoint", "mrts_restore", "mrts_get_state", "mrts_error_flags", "mrts_env_steps", "mrts_stream",
-    "mrts_destroy", "mrts_last_error",
-]
-
-
 class MrtsConfig(ctypes.Structure):
     _fields_ = [
         ("n_selfplay_slots", ctypes.c_int32),
@@ -123,6 +118,97 @@ class MrtsResponses(ctypes.Structure):
     ]
 
 
+_P, _C, _INT = ctypes.c_void_p, ctypes.c_char_p, ctypes.c_int
+_I32, _U32, _I64, _U64 = ctypes.c_int32, ctypes.c_uint32, ctypes.c_int64, ctypes.c_uint64
+_PP, _PI64 = ctypes.POINTER(_P), ctypes.POINTER(_I64)
+_CFG, _RESP = ctypes.POINTER(MrtsConfig), ctypes.POINTER(MrtsResponses)
+_BUFS = [_P, _P, _P, _P, _P]  # d_actions, d_players, d_obs, d_reward, d_done
+# every prototype of include/mrts.h: name -> (argument types, return type); load() sets them, and
+# tests/test_abi_cpu.py holds each entry against the header's prototype
+SIGNATURES = {
+    "mrts_create": ([_CFG, _PP], _INT),
+    "mrts_dims": ([_P, _P, _P, _P, _P, _P], _INT),
+    "mrts_reset": ([_P, _P, _RESP], _INT),
+    "mrts_step": ([_P, _P, _P, _RESP], _INT),
+    "mrts_get_masks": ([_P, _I32, _P], _INT),
+    "mrts_step_rows": ([_P, _P, _I32, _P, _RESP], _INT),
+    "mrts_get_masks_i32": ([_P, _I32, _P], _INT),
+    "mrts_get_masks_host": ([_P, _I32, _PP], _INT),
+    "mrts_get_masks_i32_host": ([_P, _I32, _PP], _INT),
+    "mrts_reset_dev": ([_P, _P, _P, _P, _P, _P, _I32, _P], _INT),
+    "mrts_step_dev": ([_P, *_BUFS, _P, _I32, _P], _INT),
+    "mrts_get_masks_dev": ([_P, _I32, _P, _P], _INT),
+    "mrts_step_rows_dev": ([_P, _P, _I32, _P, _P, _P, _P, _P, _I32, _P], _INT),
+    "mrts_get_masks_i32_dev": ([_P, _I32, _P, _P], _INT),
+    "mrts_policy_dev": ([_P, _P, _P, _U64, _U32, _P, _P], _INT),
+    "mrts_step_fused_dev": ([_P, *_BUFS, _P, _I32, _U64, _U32, _P], _INT),
+    "mrts_rollout_fused_dev": ([_P, *_BUFS, _P, _I32, _U64, _U32, _I32, _P], _INT),
+    "mrts_rccl_unique_id": ([_C, _P], _INT),
+    "mrts_exchange_init": ([_P, _C, _I32, _I32, _P], _INT),
+    "mrts_exchange_init_loopback": ([_P, _I32, _I32], _INT),
+    "mrts_rollout_fused_exchange_dev": ([_P, *_BUFS, _P, _I32, _U64, _U32, _I32, _P, _P, _P, _P], _INT),
+    "mrts_set_exchange_bytes": ([_P, _I32], _INT),
+    "mrts_rollout_uniform_exchange_dev": ([_P, *_BUFS, _U64, _U32, _I32, _P, _P, _P, _P], _INT),
+    "mrts_set_records": ([_P, _I32, _I32], _INT),
+    "mrts_rollout_fused_records_dev": ([_P, *_BUFS, _P, _I32, _U64, _U32, _I32, _P, _P, _P], _INT),
+    "mrts_rollout_uniform_records_dev": ([_P, *_BUFS, _U64, _U32, _I32, _P, _P, _P], _INT),
+    "mrts_record_words": ([_P], _I32),
+    "mrts_render_records_dev": ([_P, _P, _I64, _I32, _I64, _P, _I32, _P], _INT),
+    "mrts_render_records_onehot_dev": ([_P, _P, _I64, _I32, _I64, _P, _P, _I32, _P, _P], _INT),
+    "mrts_render_status": ([_P], _INT),
+    "mrts_set_step_responses": ([_P, _P, _P, _I32], _INT),
+    "mrts_capture_begin": ([_P, _P], _INT),
+    "mrts_capture_end": ([_P, _P], _INT),
+    "mrts_replay": ([_P, _P], _INT),
+    "mrts_set_rollout_events": ([_P, _P, _P], _INT),
+    "mrts_set_obs16": ([_P, _P], _INT),
+    "mrts_set_multi_step": ([_P, _I32], _INT),
+    "mrts_multi_step_capable": ([_P], _INT),
+    "mrts_policy_uniform_dev": ([_P, _U64, _U32, _P, _P], _INT),
+    "mrts_step_uniform_dev": ([_P, *_BUFS, _P, _I32, _U64, _U32, _P], _INT),
+    "mrts_rollout_uniform_dev": ([_P, *_BUFS, _U64, _U32, _I32, _I32, _P], _INT),
+    "mrts_set_obs_delta": ([_P, _I32], _INT),
+    "mrts_obs_invalidate": ([_P], _INT),
+    "mrts_policy_invalidate": ([_P], _INT),
+    "mrts_policy_head_sample_dev": ([_P, _P, _P, _P, _U64, _U32, _P, _P, _P, _P], _INT),
+    "mrts_policy_head_score_dev": ([_P, _I32, _P, _P, _P, _P, _P, _P], _INT),
+    "mrts_policy_head_grad_dev": ([_P, _I32, _P, _P, _P, _P, _P, _P, _P], _INT),
+    "mrts_policy_head_packed_words": ([_P, _I32], _I32),
+    "mrts_policy_head_pack_dev": ([_P, _I32, _P, _P, _P, _I32, _P, _P], _INT),
+    "mrts_policy_head_pack_status": ([_P, _PI64], _INT),
+    "mrts_policy_head_unpack_dev": ([_P, _I32, _P, _I32, _I32, _P, _P, _P, _P], _INT),
+    "mrts_policy_head_score_packed_dev": ([_P, _I32, _P, _P, _I32, _I32, _P, _P, _P, _P], _INT),
+    "mrts_policy_head_grad_packed_dev": ([_P, _I32, _P, _P, _I32, _I32, _P, _P, _P, _P, _P], _INT),
+    "mrts_set_source_output": ([_P, _P], _INT),
+    "mrts_onehot_features": ([_P], _INT),
+    "mrts_onehot_dev": ([_P, _P, _P, _P], _INT),
+    "mrts_obs_packed_words": ([_P, _I32], _I32),
+    "mrts_obs_pack_dev": ([_P, _I32, _P, _I32, _P, _P], _INT),
+    "mrts_obs_unpack_dev": ([_P, _I32, _P, _I32, _I32, _P, _P, _P], _INT),
+    "mrts_obs_onehot_packed_dev": ([_P, _I32, _P, _I32, _I32, _P, _P, _P], _INT),
+    "mrts_obs_packed_status": ([_P, _PI64, _PI64], _INT),
+    "mrts_copy_games": ([_P, _P, _P, _I32], _INT),
+    "mrts_copy_games_dev": ([_P, _P, _P, _I32, _P], _INT),
+    "mrts_playout": ([_P, _I32], _INT),
+    "mrts_playout_dev": ([_P, _I32, _P], _INT),
+    "mrts_evaluate": ([_P, _I32, _P], _INT),
+    "mrts_evaluate_dev": ([_P, _I32, _P, _P], _INT),
+    "mrts_trace_step": ([_P, _P, _I32, _P, _P, _I32], _INT),
+    "mrts_get_state": ([_P, _I32, _P, _I32], _INT),
+    "mrts_utt_json": ([_I32, _I32, _C, _C, _I32], _INT),
+    "mrts_error_flags": ([_P, _P], _INT),
+    "mrts_env_steps": ([_P, _P], _INT),
+    "mrts_get_state_json": ([_P, _I32, _C, _I32], _INT),
+    "mrts_set_state_json": ([_P, _I32, _C], _INT),
+    "mrts_checkpoint_size": ([_P], _I64),
+    "mrts_checkpoint": ([_P, _P, _I64], _INT),
+    "mrts_restore": ([_P, _P, _I64], _INT),
+    "mrts_stream": ([_P], _P),
+    "mrts_destroy": ([_P], None),
+    "mrts_last_error": ([], _C),
+}
+EXPORTS = list(SIGNATURES)  # every symbol include/mrts.h declares
+
 _lib = None
 
 
@@ -142,93 +228,9 @@ def load(path=LIB_PATH):
     except ImportError:
         pass
     L = ctypes.CDLL(path)
-    P, I32, U32, U64 = ctypes.c_void_p, ctypes.c_int32, ctypes.c_uint32, ctypes.c_uint64
-    L.mrts_create.argtypes = [ctypes.POINTER(MrtsConfig), ctypes.POINTER(P)]
-    L.mrts_create.restype = ctypes.c_int
-    L.mrts_dims.argtypes = [P, P, P, P, P, P]
-    L.mrts_reset.argtypes = [P, P, ctypes.POINTER(MrtsResponses)]
-    L.mrts_step.argtypes = [P, P, P, ctypes.POINTER(MrtsResponses)]
-    L.mrts_get_masks.argtypes = [P, I32, P]
-    L.mrts_step_rows.argtypes = [P, P, I32, P, ctypes.POINTER(MrtsResponses)]
-    L.mrts_get_masks_i32.argtypes = [P, I32, P]
-    L.mrts_get_masks_host.argtypes = [P, I32, ctypes.POINTER(ctypes.c_void_p)]
-    L.mrts_get_masks_i32_host.argtypes = [P, I32, ctypes.POINTER(ctypes.c_void_p)]
-    L.mrts_step_rows_dev.argtypes = [P, P, I32, P, P, P, P, P, I32, P]
-    L.mrts_get_masks_i32_dev.argtypes = [P, I32, P, P]
-    L.mrts_onehot_features.argtypes = [P]
-    L.mrts_onehot_dev.argtypes = [P, P, P, P]
-    L.mrts_obs_packed_words.argtypes = [P, I32]
-    L.mrts_obs_pack_dev.argtypes = [P, I32, P, I32, P, P]
-    L.mrts_obs_unpack_dev.argtypes = [P, I32, P, I32, I32, P, P, P]
-    L.mrts_obs_onehot_packed_dev.argtypes = [P, I32, P, I32, I32, P, P, P]
-    L.mrts_obs_packed_status.argtypes = [P, ctypes.POINTER(ctypes.c_int64), ctypes.POINTER(ctypes.c_int64)]
-    L.mrts_reset_dev.argtypes = [P, P, P, P, P, P, I32, P]
-    L.mrts_step_dev.argtypes = [P, P, P, P, P, P, P, I32, P]
-    L.mrts_get_masks_dev.argtypes = [P, I32, P, P]
-    L.mrts_policy_dev.argtypes = [P, P, P, U64, U32, P, P]
-    L.mrts_policy_invalidate.argtypes = [P]
-    L.mrts_policy_head_sample_dev.argtypes = [P, P, P, P, U64, U32, P, P, P, P]
-    L.mrts_policy_head_score_dev.argtypes = [P, I32, P, P, P, P, P, P]
-    L.mrts_policy_head_grad_dev.argtypes = [P, I32, P, P, P, P, P, P, P]
-    L.mrts_policy_head_packed_words.argtypes = [P, I32]
-    L.mrts_policy_head_pack_dev.argtypes = [P, I32, P, P, P, I32, P, P]
-    L.mrts_policy_head_pack_status.argtypes = [P, ctypes.POINTER(ctypes.c_int64)]
-    L.mrts_policy_head_unpack_dev.argtypes = [P, I32, P, I32, I32, P, P, P, P]
-    L.mrts_policy_head_score_packed_dev.argtypes = [P, I32, P, P, I32, I32, P, P, P, P]
-    L.mrts_policy_head_grad_packed_dev.argtypes = [P, I32, P, P, I32, I32, P, P, P, P, P]
-    L.mrts_step_fused_dev.argtypes = [P, P, P, P, P, P, P, I32, U64, U32, P]
-    L.mrts_rollout_fused_dev.argtypes = [P, P, P, P, P, P, P, I32, U64, U32, I32, P]
-    L.mrts_policy_uniform_dev.argtypes = [P, U64, U32, P, P]
-    L.mrts_step_uniform_dev.argtypes = [P, P, P, P, P, P, P, I32, U64, U32, P]
-    L.mrts_rollout_uniform_dev.argtypes = [P, P, P, P, P, P, U64, U32, I32, I32, P]
-    L.mrts_set_obs_delta.argtypes = [P, I32]
-    L.mrts_set_multi_step.argtypes = [P, I32]
-    L.mrts_set_rollout_events.argtypes = [P, P, P]
-    C = ctypes.c_char_p
-    L.mrts_rccl_unique_id.argtypes = [C, P]
-    L.mrts_exchange_init.argtypes = [P, C, I32, I32, P]
-    L.mrts_exchange_init_loopback.argtypes = [P, I32, I32]
-    L.mrts_rollout_fused_exchange_dev.argtypes = [P, P, P, P, P, P, P, I32, U64, U32, I32, P, P, P, P]
-    L.mrts_rollout_uniform_exchange_dev.argtypes = [P, P, P, P, P, P, U64, U32, I32, P, P, P, P]
-    L.mrts_set_exchange_bytes.argtypes = [P, I32]
-    I64 = ctypes.c_int64
-    L.mrts_set_records.argtypes = [P, I32, I32]
-    L.mrts_record_words.argtypes = [P]
-    L.mrts_rollout_fused_records_dev.argtypes = [P, P, P, P, P, P, P, I32, U64, U32, I32, P, P, P]
-    L.mrts_rollout_uniform_records_dev.argtypes = [P, P, P, P, P, P, U64, U32, I32, P, P, P]
-    L.mrts_render_records_dev.argtypes = [P, P, I64, I32, I64, P, I32, P]
-    L.mrts_render_status.argtypes = [P]
-    L.mrts_render_records_onehot_dev.argtypes = [P, P, I64, I32, I64, P, P, I32, P, P]
-    L.mrts_set_step_responses.argtypes = [P, P, P, I32]
-    L.mrts_capture_begin.argtypes = [P, P]
-    L.mrts_capture_end.argtypes = [P, P]
-    L.mrts_replay.argtypes = [P, P]
-    L.mrts_multi_step_capable.argtypes = [P]
-    L.mrts_set_obs16.argtypes = [P, P]
-    L.mrts_obs_invalidate.argtypes = [P]
-    L.mrts_set_source_output.argtypes = [P, P]
-    L.mrts_copy_games.argtypes = [P, P, P, I32]
-    L.mrts_copy_games_dev.argtypes = [P, P, P, I32, P]
-    L.mrts_playout.argtypes = [P, I32]
-    L.mrts_playout_dev.argtypes = [P, I32, P]
-    L.mrts_trace_step.argtypes = [P, P, I32, P, P, I32]
-    L.mrts_evaluate.argtypes = [P, I32, P]
-    L.mrts_evaluate_dev.argtypes = [P, I32, P, P]
-    L.mrts_utt_json.argtypes = [I32, I32, ctypes.c_char_p, ctypes.c_char_p, I32]
-    L.mrts_get_state.argtypes = [P, I32, P, I32]
-    L.mrts_get_state_json.argtypes = [P, I32, ctypes.c_char_p, I32]
-    L.mrts_set_state_json.argtypes = [P, I32, ctypes.c_char_p]
-    L.mrts_checkpoint_size.argtypes = [P]
-    L.mrts_checkpoint_size.restype = ctypes.c_int64
-    L.mrts_checkpoint.argtypes = [P, P, ctypes.c_int64]
-    L.mrts_restore.argtypes = [P, P, ctypes.c_int64]
-    L.mrts_error_flags.argtypes = [P, P]
-    L.mrts_env_steps.argtypes = [P, P]
-    L.mrts_stream.argtypes = [P]
-    L.mrts_stream.restype = P
-    L.mrts_destroy.argtypes = [P]
-    L.mrts_destroy.restype = None
-    L.mrts_last_error.restype = ctypes.c_char_p
+    for name, (argtypes, restype) in SIGNATURES.items():
+        fn = getattr(L, name)
+        fn.argtypes, fn.restype = argtypes, restype
     _lib = L
     return L
 

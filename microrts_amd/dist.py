@@ -1,7 +1,11 @@
 """Multi-GPU plumbing for the env step: one process per GPU, disjoint game shards,
 no collective inside the step.  Backend-agnostic (RCCL on MI355X, gloo on CPU for the tests)."""
+import ctypes
+
 import torch
 import torch.distributed as dist
+
+from . import _lib
 
 
 def shard(rank, games_per_rank):
@@ -153,6 +157,28 @@ def rccl_library_path():
     return bundled if os.path.exists(bundled) else "librccl.so"
 
 
+def _handle_communicator(env, group=None):
+    """One RCCL communicator for the env's handle over the ranks of `group` (mrts_exchange_init; its unique id is
+    broadcast over the torch process group).  Collective: every rank must call it.  Returns (world, rank)."""
+    world, rank = dist.get_world_size(group), dist.get_rank(group)
+    L, h = env._h.L, env._h.h
+    path = rccl_library_path().encode()
+    uid = (ctypes.c_char * 128)()
+    # every rank binds RCCL first (drawing an id it may not use) and the ranks agree before anyone
+    # enters the collective init: a rank that failed alone would leave the others waiting in it
+    ok = L.mrts_rccl_unique_id(path, uid) == 0
+    flag = torch.tensor([1 if ok else 0], device=env.device if dist.get_backend(group) != "gloo" else "cpu")
+    dist.all_reduce(flag, op=dist.ReduceOp.MIN, group=group)
+    if not bool(flag.item()):
+        why = L.mrts_last_error().decode() if not ok else "another rank"
+        raise RuntimeError(f"RCCL could not be bound on every rank: {why}")
+    box = [bytes(uid)]
+    dist.broadcast_object_list(box, src=0, group=group)
+    uid = (ctypes.c_char * 128).from_buffer_copy(box[0])
+    _lib.check(L.mrts_exchange_init(h, path, world, rank, uid))
+    return world, rank
+
+
 class NativeExchange:
     """The observation exchange of every step from native code (mrts_rollout_*_exchange_dev): one RCCL
     communicator per rank's handle (its unique id broadcast over the torch process group), the step
@@ -164,27 +190,9 @@ class NativeExchange:
         """u8: exchange the observation as uint8 (mrts_set_exchange_bytes: half the bytes) when the
         handle allows it (16x16 full observability, every value < 256), else int16; "auto" = try.
         Every rank decides the same way (the handles are built alike)."""
-        import ctypes
-
-        from microrts_amd import _lib
-
         self.env = env
-        self.world, self.rank = dist.get_world_size(group), dist.get_rank(group)
+        self.world, self.rank = _handle_communicator(env, group)
         L, h = env._h.L, env._h.h
-        path = rccl_library_path().encode()
-        uid = (ctypes.c_char * 128)()
-        # every rank binds RCCL first (drawing an id it may not use) and the ranks agree before anyone
-        # enters the collective init: a rank that failed alone would leave the others waiting in it
-        ok = L.mrts_rccl_unique_id(path, uid) == 0
-        flag = torch.tensor([1 if ok else 0], device=env.device if dist.get_backend(group) != "gloo" else "cpu")
-        dist.all_reduce(flag, op=dist.ReduceOp.MIN, group=group)
-        if not bool(flag.item()):
-            why = L.mrts_last_error().decode() if not ok else "another rank"
-            raise RuntimeError(f"RCCL could not be bound on every rank: {why}")
-        box = [bytes(uid)]
-        dist.broadcast_object_list(box, src=0, group=group)
-        uid = (ctypes.c_char * 128).from_buffer_copy(box[0])
-        _lib.check(L.mrts_exchange_init(h, path, self.world, self.rank, uid))
         self.u8 = False
         if u8:
             rc = L.mrts_set_exchange_bytes(h, 1)
@@ -225,26 +233,9 @@ class RecordExchange:
     rank's observations.  Every rank of `group` must construct it (ncclCommInitRank is collective)."""
 
     def __init__(self, env, units_per_record=64, steps_per_launch=0, group=None):
-        import ctypes
-
-        from microrts_amd import _lib
-
         self.env = env
-        self.world, self.rank = dist.get_world_size(group), dist.get_rank(group)
-        L, h = env._h.L, env._h.h
         self.words = env.set_records(units_per_record, steps_per_launch)
-        path = rccl_library_path().encode()
-        uid = (ctypes.c_char * 128)()
-        ok = L.mrts_rccl_unique_id(path, uid) == 0
-        flag = torch.tensor([1 if ok else 0], device=env.device if dist.get_backend(group) != "gloo" else "cpu")
-        dist.all_reduce(flag, op=dist.ReduceOp.MIN, group=group)
-        if not bool(flag.item()):
-            why = L.mrts_last_error().decode() if not ok else "another rank"
-            raise RuntimeError(f"RCCL could not be bound on every rank: {why}")
-        box = [bytes(uid)]
-        dist.broadcast_object_list(box, src=0, group=group)
-        uid = (ctypes.c_char * 128).from_buffer_copy(box[0])
-        _lib.check(L.mrts_exchange_init(h, path, self.world, self.rank, uid))
+        self.world, self.rank = _handle_communicator(env, group)
         self.recv = None
 
     def buffer(self, n_steps):
@@ -271,5 +262,5 @@ class RecordExchange:
         (MRTS_ERR_RECORD).  Synchronises; call it at a point where the learner may wait."""
         if self.env.render_overflow():
             raise RuntimeError("a rendered observation record overflowed (units missing): raise units_per_record")
-        if (self.env.error_flags() & (1 << 6)).any():
+        if (self.env.error_flags() & _lib.err_bit("RECORD")).any():
             raise RuntimeError("a game of this rank overflowed its observation record (MRTS_ERR_RECORD)")

@@ -3,13 +3,7 @@ keeps of each step's observation tensor int32 [C][H][W] — its occupied cells a
 bitmaps, 1 + 2 * cap + (C - 5) * ceil(H*W / 32) uint32 words a row.  DeviceVecEnv.pack_obs fills a step of an
 obs_packed_buffer; onehot_packed gives the network's input of a minibatch straight from the packed rows through a
 gather index, unpack_obs the int32 planes.  This module holds the argument checks (no GPU call)."""
-from .policy_head import check_tensor
-
-
-def default_cap(env):
-    """The packed observation rows' default capacity of occupied cells: min(H*W, 128)."""
-    _, H, W, _, _ = env.dims
-    return min(H * W, 128)
+from ._packed import PackedLayout, check_rows, check_tensor
 
 
 def _bitmap_words(env):
@@ -17,30 +11,18 @@ def _bitmap_words(env):
     return (C - 5) * ((H * W + 31) // 32)
 
 
+LAYOUT = PackedLayout(per_item=2, cap=128, fixed=lambda env: 1 + _bitmap_words(env), formula="{fixed} + {n} * cap",
+                      for_logits=False)
+
+
+def default_cap(env):
+    """The packed observation rows' default capacity of occupied cells: min(H*W, 128)."""
+    return LAYOUT.default_cap(env)
+
+
 def packed_words(env, cap=None):
     """uint32 words of a packed observation row of at most `cap` occupied cells (default min(H*W, 128))."""
-    _, H, W, _, _ = env.dims
-    cap = default_cap(env) if cap is None else cap
-    if not isinstance(cap, int) or isinstance(cap, bool) or cap < 1 or cap > H * W:
-        raise ValueError(f"cap: {cap!r}, expected an int in [1, H*W = {H * W}]")
-    return 1 + 2 * cap + _bitmap_words(env)
-
-
-def _cap_of(env, name, t, cap):
-    """The cap a packed tensor's last dimension stands for; ValueError naming the tensor unless that is a row's words."""
-    import torch
-
-    _, H, W, _, _ = env.dims
-    if not isinstance(t, torch.Tensor) or t.dim() < 2:
-        raise ValueError(f"{name}: expected a uint32 tensor [rows][words]")
-    words, fixed = t.shape[-1], 1 + _bitmap_words(env)
-    if cap is None:
-        if words < fixed + 2 or (words - fixed) % 2 or (words - fixed) // 2 > H * W:
-            raise ValueError(f"{name}: {words} words is not {fixed} + 2 * cap for a cap in [1, H*W = {H * W}]")
-        return (words - fixed) // 2
-    if words != packed_words(env, cap):
-        raise ValueError(f"{name}: {words} words, expected {packed_words(env, cap)} for cap {cap}")
-    return cap
+    return LAYOUT.words(env, cap)
 
 
 def check_pack_args(env, out, obs, cap=None):
@@ -49,14 +31,9 @@ def check_pack_args(env, out, obs, cap=None):
     import torch
 
     _, H, W, C, _ = env.dims
-    cap = _cap_of(env, "out", out, cap)
-    if out.dim() != 2:
-        raise ValueError(f"out: shape {tuple(out.shape)}, expected [rows][words]")
-    n = out.shape[0]
-    check_tensor("out", out, torch.uint32, [(n, packed_words(env, cap))], env.device)
+    n, cap = LAYOUT.check_out(env, out, cap)
     check_tensor("obs", obs, torch.int32, [(n, C, H, W)], env.device)
-    if n * H * W >= 1 << 31:
-        raise ValueError("out: rows * H*W must be below 2^31")
+    check_rows(env, "out", n)
     return n, cap
 
 
@@ -64,20 +41,4 @@ def check_read_args(env, packed, index, cap=None):
     """The argument checks of unpack_obs / onehot_packed: packed uint32 [...][words], contiguous on the env's device;
     index (optional) int32 [rows] on it.  Returns (rows, packed rows, cap): rows is index's length, else every
     packed row."""
-    import torch
-
-    _, H, W, _, _ = env.dims
-    cap = _cap_of(env, "packed", packed, cap)
-    check_tensor("packed", packed, torch.uint32, [tuple(packed.shape)], env.device)
-    n_packed = packed.numel() // packed.shape[-1]
-    if n_packed < 1:
-        raise ValueError("packed: no rows")
-    rows = n_packed
-    if index is not None:
-        if not isinstance(index, torch.Tensor) or index.dim() != 1:
-            raise ValueError("index: expected an int32 tensor [rows]")
-        rows = index.shape[0]
-        check_tensor("index", index, torch.int32, [(rows,)], env.device)
-    if rows * H * W >= 1 << 31:
-        raise ValueError(f"{'packed' if index is None else 'index'}: rows * H*W must be below 2^31")
-    return rows, n_packed, cap
+    return LAYOUT.check_read(env, packed, index, cap=cap)

@@ -8,25 +8,8 @@ evaluate_actions on the dense rows.
 Per candidate cell (mask slot 0 set) every field with a set mask bit is an independent masked categorical — the
 GridNet factorisation of MicroRTS-Py.  An empty field adds nothing here, where MicroRTS-Py's all-masked
 categorical adds the constants -log n (log-probability) and log n (entropy): PPO ratios and gradients are equal."""
-import ctypes
-
 from . import _lib
-
-
-def check_tensor(name, t, dtype, shapes, device):
-    """ValueError naming the argument unless t is a contiguous tensor of `dtype` on `device` with one of `shapes`."""
-    import torch
-
-    if not isinstance(t, torch.Tensor):
-        raise ValueError(f"{name}: expected a torch tensor, got {type(t).__name__}")
-    if t.dtype != dtype:
-        raise ValueError(f"{name}: dtype {t.dtype}, expected {dtype}")
-    if t.device != device:
-        raise ValueError(f"{name}: on {t.device}, expected {device}")
-    if tuple(t.shape) not in [tuple(s) for s in shapes]:
-        raise ValueError(f"{name}: shape {tuple(t.shape)}, expected " + " or ".join(str(tuple(s)) for s in shapes))
-    if not t.is_contiguous():
-        raise ValueError(f"{name}: not contiguous")
+from ._packed import PackedLayout, check_rows, check_tensor, ptr as _p
 
 
 def check_head_args(env, logits, masks, actions, n=None, actions_name="actions"):
@@ -42,13 +25,8 @@ def check_head_args(env, logits, masks, actions, n=None, actions_name="actions")
     check_tensor("logits", logits, torch.float32, [(n, H * W, K - 1)], env.device)
     check_tensor("masks", masks, torch.uint8, [(n, H, W, K), (n, H * W, K)], env.device)
     check_tensor(actions_name, actions, torch.int32, [(n, H * W, 7)], env.device)
-    if n * H * W >= 1 << 31:
-        raise ValueError("logits: rows * H*W must be below 2^31")
+    check_rows(env, "logits", n)
     return n
-
-
-def _p(t):
-    return ctypes.c_void_p(t.data_ptr()) if t is not None else None
 
 
 def _evaluate_fn():
@@ -99,38 +77,17 @@ def evaluate_actions(env, logits, masks, actions):
 
 
 CW = 5  # words per candidate of a packed row (include/mrts.h, "Packed policy rows")
+LAYOUT = PackedLayout(per_item=CW, cap=64, fixed=lambda env: 1, formula="{fixed} + cap * {n}", for_logits=True)
 
 
 def default_cap(env):
     """The packed rows' default candidate capacity: min(H*W, 64)."""
-    _, H, W, _, _ = env.dims
-    return min(H * W, 64)
+    return LAYOUT.default_cap(env)
 
 
 def packed_words(env, cap=None):
     """uint32 words of a packed row of at most `cap` candidates (default min(H*W, 64)): 1 + cap * 5."""
-    _, H, W, _, _ = env.dims
-    cap = default_cap(env) if cap is None else cap
-    if not isinstance(cap, int) or isinstance(cap, bool) or cap < 1 or cap > H * W:
-        raise ValueError(f"cap: {cap!r}, expected an int in [1, H*W = {H * W}]")
-    return 1 + cap * CW
-
-
-def _cap_of(env, name, t, cap):
-    """The cap a packed tensor's last dimension stands for; ValueError naming it unless that is 1 + cap * 5."""
-    import torch
-
-    _, H, W, _, _ = env.dims
-    if not isinstance(t, torch.Tensor) or t.dim() < 2:
-        raise ValueError(f"{name}: expected a uint32 tensor [rows][words]")
-    words = t.shape[-1]
-    if cap is None:
-        if words < 1 + CW or (words - 1) % CW or (words - 1) // CW > H * W:
-            raise ValueError(f"{name}: {words} words is not 1 + cap * {CW} for a cap in [1, H*W = {H * W}]")
-        return (words - 1) // CW
-    if words != packed_words(env, cap):
-        raise ValueError(f"{name}: {words} words, expected {packed_words(env, cap)} for cap {cap}")
-    return cap
+    return LAYOUT.words(env, cap)
 
 
 def check_pack_args(env, out, masks, actions, source=None, cap=None):
@@ -140,17 +97,12 @@ def check_pack_args(env, out, masks, actions, source=None, cap=None):
     import torch
 
     _, H, W, _, K = env.dims
-    cap = _cap_of(env, "out", out, cap)
-    if out.dim() != 2:
-        raise ValueError(f"out: shape {tuple(out.shape)}, expected [rows][words]")
-    n = out.shape[0]
-    check_tensor("out", out, torch.uint32, [(n, 1 + cap * CW)], env.device)
+    n, cap = LAYOUT.check_out(env, out, cap)
     check_tensor("masks", masks, torch.uint8, [(n, H, W, K), (n, H * W, K)], env.device)
     check_tensor("actions", actions, torch.int32, [(n, H * W, 7)], env.device)
     if source is not None:
         check_tensor("source", source, torch.int32, [(n, (H * W + 31) // 32)], env.device)
-    if n * H * W >= 1 << 31:
-        raise ValueError("out: rows * H*W must be below 2^31")
+    check_rows(env, "out", n)
     return n, cap
 
 
@@ -158,22 +110,7 @@ def check_packed_args(env, packed, index, rows, cap=None):
     """The argument checks of the calls that read packed rows (no GPU call): packed uint32 [...][words], contiguous
     on the env's device; index (optional) int32 [rows]; without an index packed holds `rows` rows.  Returns
     (packed rows, cap)."""
-    import torch
-
-    _, H, W, _, _ = env.dims
-    cap = _cap_of(env, "packed", packed, cap)
-    check_tensor("packed", packed, torch.uint32, [tuple(packed.shape)], env.device)
-    n_packed = packed.numel() // packed.shape[-1]
-    if n_packed < 1:
-        raise ValueError("packed: no rows")
-    if index is None:
-        if n_packed != rows:
-            raise ValueError(f"packed: {n_packed} rows for {rows} rows of logits (pass an index to gather)")
-    else:
-        check_tensor("index", index, torch.int32, [(rows,)], env.device)
-    if rows * H * W >= 1 << 31:
-        raise ValueError("logits: rows * H*W must be below 2^31")
-    return n_packed, cap
+    return LAYOUT.check_read(env, packed, index, rows, cap)[1:]
 
 
 def _evaluate_packed_fn():

@@ -7,13 +7,55 @@ import pytest
 
 from microrts_amd import _lib
 from microrts_amd.vec_client import UnitTypeTable, _check_rfs, _bot_kind
-from tests.headers import header_symbols
+from tests.headers import header_prototypes, header_symbols, signature_mismatches
 
 ROOT = os.path.dirname(os.path.dirname(os.path.abspath(__file__)))
 
 
 def test_header_matches_python_exports():
     assert header_symbols() == sorted(_lib.EXPORTS)
+
+
+def test_signature_table_matches_the_header_prototypes():
+    """Every prototype of include/mrts.h has its entry in _lib.SIGNATURES with as many arguments, each of the same
+    class (pointer / int32 / uint32 / int64 / uint64; C's int is int32, as ctypes.c_int is c_int32 here), and the same
+    return class; EXPORTS is the table's keys.  Needs no built library."""
+    protos = header_prototypes()
+    assert sorted(protos) == header_symbols(), "the prototype reader and header_symbols() disagree on the names"
+    assert _lib.EXPORTS == list(_lib.SIGNATURES)
+    assert signature_mismatches(protos, _lib.SIGNATURES) == []
+
+
+def test_signature_comparison_has_teeth():
+    """On stand-in tables the comparison names a dropped argument, an int32 <-> int64 swap, a wrong return type and
+    a missing entry."""
+    protos = header_prototypes()
+    I32, I64, P = ctypes.c_int32, ctypes.c_int64, ctypes.c_void_p
+
+    def changed(name, edit):
+        t = {k: (list(a), r) for k, (a, r) in _lib.SIGNATURES.items()}
+        t[name] = edit(*t[name])
+        return signature_mismatches(protos, t)
+
+    assert protos["mrts_step_dev"][1][-2:] == ["int32_t", "void*"] and protos["mrts_checkpoint"][1][-1] == "int64_t"
+    bad = changed("mrts_step_dev", lambda a, r: (a[:-1], r))
+    assert len(bad) == 1 and bad[0].startswith("mrts_step_dev: 8 arguments, the header has 9")
+    bad = changed("mrts_checkpoint", lambda a, r: (a[:-1] + [I32], r))
+    assert bad == ["mrts_checkpoint: argument 2 is int32, the header has int64_t"]
+    bad = changed("mrts_get_masks", lambda a, r: ([a[0], I64, a[2]], r))
+    assert bad == ["mrts_get_masks: argument 1 is int64, the header has int32_t"]
+    bad = changed("mrts_policy_dev", lambda a, r: (a[:3] + [ctypes.c_uint32, ctypes.c_uint64] + a[5:], r))
+    assert len(bad) == 2 and all(b.startswith("mrts_policy_dev: argument") for b in bad)
+    for name, wrong, text in (("mrts_checkpoint_size", ctypes.c_int, "returns int32, the header has int64_t"),
+                              ("mrts_stream", ctypes.c_int, "returns int32, the header has void*"),
+                              ("mrts_last_error", P, "returns pointer, the header has const char*"),
+                              ("mrts_destroy", ctypes.c_int, "returns int32, the header has void"),
+                              ("mrts_reset", None, "returns void, the header has int")):
+        assert changed(name, lambda a, r: (a, wrong)) == [f"{name}: {text}"]
+    short = {k: v for k, v in _lib.SIGNATURES.items() if k != "mrts_replay"}
+    assert signature_mismatches(protos, short) == ["mrts_replay: not in the table"]
+    assert signature_mismatches({k: v for k, v in protos.items() if k != "mrts_replay"}, _lib.SIGNATURES) == \
+        ["mrts_replay: not in the header"]
 
 
 def test_library_loads_and_exports_every_symbol():
@@ -99,6 +141,17 @@ def _load_missing(tmp_path):
         _lib.load(str(tmp_path / "nope.so"))
     finally:
         _lib._lib = saved
+
+
+def test_state_accessors_keep_their_keyword_names():
+    """ForwardModel addresses a game, DeviceVecEnv a slot: callers pass either by keyword."""
+    import inspect
+
+    from microrts_amd import DeviceVecEnv, ForwardModel
+
+    for cls, first in ((ForwardModel, "game"), (DeviceVecEnv, "slot")):
+        for name, rest in (("dump_state", []), ("state_json", []), ("set_state_json", ["text"])):
+            assert list(inspect.signature(getattr(cls, name)).parameters) == ["self", first] + rest, (cls, name)
 
 
 def test_vecclient_mirror_rejects_missing_bots():

@@ -26,7 +26,7 @@ import pytest
 from tests import dumps, oracle_py
 from tests.defs import SEED
 from tests.gpu_checks import record_exchange_loopback_ranks
-from tests.gpu_support import assert_matches_oracle, assert_same_outputs, torch_gpu
+from tests.gpu_support import assert_matches_oracle, assert_same_outputs, same, torch_gpu
 
 pytestmark = pytest.mark.gpu
 
@@ -225,6 +225,42 @@ def test_c_abi_fused_write_needs_invalidate():
     assert any(not np.array_equal(A.dump_state(s), C.dump_state(s)) for s in range(0, n, 2)), \
         "without invalidate the written rows should have been ignored"
     for e in (A, B, C):
+        e.close()
+
+
+@pytest.mark.parametrize("form", ["step_fused", "rollout_fused"])
+@pytest.mark.parametrize("mp,n", [("maps/8x8/basesWorkers8x8.xml", 4), ("maps/16x16/basesWorkers16x16.xml", 16)],
+                         ids=["generic 8x8", "specialised 16x16"])
+def test_python_guard_makes_fused_calls_decode_foreign_rows(mp, n, form):
+    """The same contract through DeviceVecEnv's own methods, which call mrts_policy_invalidate() themselves: rows
+    copy_-ed into env.actions between two fused calls move the tensor's version counter, so the next step_fused /
+    rollout_fused(n_steps=1) decodes them — the state equals a twin's that takes them through a plain step(), and
+    so do the outputs and the rows sampled next."""
+    torch = torch_gpu()
+    from microrts_amd import DeviceVecEnv
+
+    A, B = (DeviceVecEnv(n, 0, 300, [mp] * n, seed=5) for _ in range(2))
+    fused = (lambda k: B.step_fused(SEED, k)) if form == "step_fused" else (lambda k: B.rollout_fused(SEED, k, 1))
+    for e in (A, B):
+        e.reset()
+        e.random_policy(SEED, 0)
+    g = torch.Generator(device="cpu").manual_seed(3)
+    hi = torch.tensor([6, 4, 4, 4, 4, 7, 49], dtype=torch.int32)
+    for k in range(12):
+        if k in (5, 11):  # after fused calls whose sampled rows the handle kept
+            alt = (torch.rand(tuple(A.actions.shape), generator=g) * hi).to(torch.int32).to(A.device)
+            assert not torch.equal(alt, B.actions)
+            for e in (A, B):
+                e.actions.copy_(alt)
+        A.step()
+        A.random_policy(SEED, k + 1)
+        fused(k + 1)
+        for name in ("obs", "reward", "done", "masks", "actions"):
+            same(getattr(B, name), getattr(A, name), name, f"{form} after step {k}")
+        for s in range(0, n, 2):
+            assert np.array_equal(A.dump_state(s), B.dump_state(s)), f"{form} after step {k}: state of slot {s}"
+    assert np.array_equal(A.error_flags(), B.error_flags())
+    for e in (A, B):
         e.close()
 
 

@@ -13,6 +13,7 @@ import torch
 from microrts_amd import _lib, policy_head
 from tests import oracle_py
 from tests import policy_head_ref as R
+from tests.python_refusal_cases import cases as refusal_cases
 
 ROOT = os.path.dirname(os.path.dirname(os.path.abspath(__file__)))
 HEAD = ["mrts_policy_head_sample_dev", "mrts_policy_head_score_dev", "mrts_policy_head_grad_dev"]
@@ -83,6 +84,55 @@ def test_reference_alone_stays_under_the_boundary_cap():
         assert torch.equal(r["actions"][keep], r32["actions"][keep])
 
 
+def test_scorers_hand_each_entry_point_its_arguments():
+    """The autograd functions of evaluate_actions and evaluate_actions_packed: on a stand-in library that records
+    its calls, forward and backward of both reach their own entry points with as many arguments as _lib.SIGNATURES
+    lists, an int where it has an int32 and a pointer (or None) where it has a pointer, the tensors in their places."""
+    calls = []
+
+    class Library:
+        def __getattr__(self, name):
+            return lambda *args: calls.append((name, args)) or 0
+
+    env = types.SimpleNamespace(dims=(4, 4, 4, 27, 79), device=torch.device("cpu"), _s=lambda stream: None,
+                                _h=types.SimpleNamespace(L=Library(), h="handle"))
+    lg = torch.zeros((4, 16, 78), requires_grad=True)
+    mk = torch.zeros((4, 4, 4, 79), dtype=torch.uint8)
+    ac = torch.zeros((4, 16, 7), dtype=torch.int32)
+    pk = torch.zeros((2, 1 + 8 * 5), dtype=torch.uint32)
+    idx = torch.zeros(4, dtype=torch.int32)
+    for run, names, rows in (
+            (lambda: policy_head.evaluate_actions(env, lg, mk, ac), HEAD[1:], [mk, ac]),
+            (lambda: policy_head.evaluate_actions_packed(env, lg, pk, idx),
+             ["mrts_policy_head_score_packed_dev", "mrts_policy_head_grad_packed_dev"], [pk, 2, 8, idx]),
+            (lambda: policy_head.evaluate_actions_packed(env, lg, torch.zeros((4, 41), dtype=torch.uint32)), None, None)):
+        calls.clear()
+        logprob, entropy = run()
+        (logprob.sum() + 2 * entropy.sum()).backward()
+        assert lg.grad is not None and lg.grad.shape == lg.shape
+        lg.grad = None
+        assert len(calls) == 2
+        for name, args in calls:
+            argtypes = _lib.SIGNATURES[name][0]
+            assert len(args) == len(argtypes), name
+            for a, t in zip(args[1:], argtypes[1:]):
+                assert isinstance(a, int) if t is ctypes.c_int32 else a is None or isinstance(a, ctypes.c_void_p), (name, a, t)
+        if names is None:  # no index: a null pointer in its place
+            assert [c[0] for c in calls] == ["mrts_policy_head_score_packed_dev", "mrts_policy_head_grad_packed_dev"]
+            assert calls[0][1][6] is None and calls[1][1][6] is None
+            continue
+        assert [c[0] for c in calls] == names
+        want = [r.data_ptr() if isinstance(r, torch.Tensor) else r for r in rows]
+        for name, args in calls:
+            assert args[:2] == ("handle", 4) and args[2].value == lg.data_ptr()
+            assert [a.value if isinstance(a, ctypes.c_void_p) else a for a in args[3:3 + len(rows)]] == want, name
+        # the backward's three last pointers before the stream: the two incoming gradients and the one it writes
+        assert all(isinstance(a, ctypes.c_void_p) for a in calls[1][1][-4:-1]) and calls[1][1][-1] is None
+    calls.clear()
+    policy_head.evaluate_actions(env, lg.detach(), mk, ac)  # nothing to differentiate: no backward call
+    assert [c[0] for c in calls] == ["mrts_policy_head_score_dev"]
+
+
 def test_bad_tensors_are_refused_before_any_gpu_call():
     env = types.SimpleNamespace(dims=(4, 4, 4, 27, 79), device=torch.device("cpu"))
     lg = torch.zeros((4, 16, 78))
@@ -90,15 +140,8 @@ def test_bad_tensors_are_refused_before_any_gpu_call():
     ac = torch.zeros((4, 16, 7), dtype=torch.int32)
     assert policy_head.check_head_args(env, lg, mk, ac) == 4
     assert policy_head.check_head_args(env, lg, mk.reshape(4, 16, 79), ac, n=4) == 4
-    bad = [("logits", (lg.double(), mk, ac)), ("logits", (torch.zeros((4, 16, 79)), mk, ac)),
-           ("logits", (torch.zeros((4, 78, 16)).transpose(1, 2), mk, ac)), ("logits", (lg.numpy(), mk, ac)),
-           ("masks", (lg, mk.bool(), ac)), ("masks", (lg, mk[:3], ac)), ("actions", (lg, mk, ac.long())),
-           ("actions", (lg, mk, torch.zeros((4, 16, 8), dtype=torch.int32)[:, :, :7]))]
-    for name, args in bad:
-        with pytest.raises(ValueError, match=name):
-            policy_head.check_head_args(env, *args)
-    with pytest.raises(ValueError, match="logits"):  # the slot count is fixed for sample_actions
-        policy_head.check_head_args(env, lg[:3], mk, ac, n=4)
-    cuda = types.SimpleNamespace(dims=env.dims, device=torch.device("cuda", 0))
-    with pytest.raises(ValueError, match="logits: on cpu"):
-        policy_head.evaluate_actions(cuda, lg, mk, ac)
+    bad = refusal_cases()["head"]
+    assert len(bad) == 10
+    for name, match, call in bad:
+        with pytest.raises(ValueError, match=match):
+            call()

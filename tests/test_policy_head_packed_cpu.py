@@ -11,6 +11,7 @@ import torch
 
 from microrts_amd import DeviceVecEnv, _lib, policy_head
 from tests import policy_head_packed_ref as PR
+from tests.python_refusal_cases import cases as refusal_cases
 
 ROOT = os.path.dirname(os.path.dirname(os.path.abspath(__file__)))
 PACKED = ["mrts_policy_head_pack_dev", "mrts_policy_head_unpack_dev", "mrts_policy_head_score_packed_dev",
@@ -45,9 +46,11 @@ def test_packed_words_follows_the_header():
     assert DeviceVecEnv.packed_words(env, 256) == 1 + 256 * cw
     small = types.SimpleNamespace(dims=(4, 4, 4, 27, 79), device=torch.device("cpu"))
     assert policy_head.packed_words(small) == 1 + 16 * cw and policy_head.packed_words(small, 1) == 1 + cw
-    for bad in (0, -1, 17, 2.0, True, "8"):
-        with pytest.raises(ValueError, match="cap"):
-            policy_head.packed_words(small, bad)
+    bad = refusal_cases()["packed_words"]
+    assert len(bad) == 6
+    for name, match, call in bad:
+        with pytest.raises(ValueError, match=match):
+            call()
 
 
 def test_numpy_packer_on_a_hand_made_row():
@@ -81,46 +84,15 @@ def test_bad_arguments_are_refused_before_any_gpu_call():
     mk = torch.zeros((4, 4, 4, 79), dtype=torch.uint8)
     ac = torch.zeros((4, 16, 7), dtype=torch.int32)
     src = torch.zeros((4, 1), dtype=torch.int32)
-    lg = torch.zeros((4, 16, 78))
     idx = torch.zeros(4, dtype=torch.int32)
     assert policy_head.check_pack_args(env, out, mk, ac, src) == (4, 8)
     assert policy_head.check_pack_args(env, out, mk.reshape(4, 16, 79), ac, None, cap=8) == (4, 8)
     assert policy_head.check_packed_args(env, out, None, 4) == (4, 8)
     assert policy_head.check_packed_args(env, out.reshape(2, 2, W8), idx[:3], 3) == (4, 8)
-    # pack_step itself, on an object that has no handle: every refusal comes before the library is touched
-    fake = types.SimpleNamespace(dims=env.dims, device=cpu, masks=mk, actions=ac, source=src, _h=None)
-    bad = [("out", dict(out=out.to(torch.int32))), ("out", dict(out=torch.zeros((4, W8 + 1), dtype=torch.uint32))),
-           ("out", dict(out=torch.zeros((4, 1 + 17 * 5), dtype=torch.uint32))), ("out", dict(out=out, cap=7)),
-           ("cap", dict(out=out, cap=0)), ("out", dict(out=torch.zeros((4, 2 * W8), dtype=torch.uint32)[:, :W8])),
-           ("out", dict(out=out.reshape(2, 2, W8))), ("out", dict(out=out.numpy())),
-           ("masks", dict(out=out, masks=mk.bool(), actions=ac)), ("masks", dict(out=out, masks=mk[:3], actions=ac)),
-           ("actions", dict(out=out, actions=ac.long())),
-           ("actions", dict(out=out, actions=torch.zeros((4, 16, 8), dtype=torch.int32)[:, :, :7]))]
-    for name, kw in bad:
-        with pytest.raises(ValueError, match=name):
-            DeviceVecEnv.pack_step(fake, **kw)
-    with pytest.raises(ValueError, match="masks"):
-        fake.masks = None
-        DeviceVecEnv.pack_step(fake, out)
-    with pytest.raises(ValueError, match="source"):
-        policy_head.check_pack_args(env, out, mk, ac, src.long())
-    bad = [("logits", (lg.double(), out, None)), ("logits", (torch.zeros((4, 16, 79)), out, None)),
-           ("logits", (lg.numpy(), out, None)),
-           ("logits", (torch.zeros((4, 78, 16)).transpose(1, 2), out, None)),
-           ("packed", (lg, out.to(torch.int32), None)), ("packed", (lg, out[:3], None)), ("packed", (lg, out[:, :W8 - 1], None)),
-           ("packed", (lg, torch.zeros((4, 2 * W8), dtype=torch.uint32)[:, :W8], None)), ("packed", (lg, out.reshape(-1), None)),
-           ("packed", (lg, torch.zeros((4, 1 + 17 * 5), dtype=torch.uint32), None)),
-           ("index", (lg, out, idx.long())), ("index", (lg, out, idx[:3])), ("index", (lg, out, idx.reshape(2, 2))),
-           ("index", (lg, out, torch.zeros(8, dtype=torch.int32)[::2])), ("index", (lg, out, [0, 1, 2, 3]))]
-    for name, args in bad:
-        with pytest.raises(ValueError, match=name):
-            policy_head.evaluate_actions_packed(env, *args)
-    cuda = types.SimpleNamespace(dims=env.dims, device=torch.device("cuda", 0))
-    with pytest.raises(ValueError, match="logits: on cpu"):
-        policy_head.evaluate_actions_packed(cuda, lg, out)
-    # rows * H*W >= 2^31, on tensors that take no memory
-    big = types.SimpleNamespace(dims=(4, 256, 256, 27, 79), device=torch.device("meta"))
-    n = (1 << 31) // (256 * 256)
-    with pytest.raises(ValueError, match="2\\^31"):
-        policy_head.evaluate_actions_packed(big, torch.empty((n, 256 * 256, 78), device="meta"),
-                                            torch.empty((n, 6), dtype=torch.uint32, device="meta"))
+    # pack_step and unpack themselves, on an object that has no handle: every refusal comes before the library is touched
+    cases = refusal_cases()
+    assert len(cases["pack_step"]) == 14 and len(cases["evaluate_packed"]) == 17
+    for group in ("pack_step", "evaluate_packed", "unpack"):
+        for name, match, call in cases[group]:
+            with pytest.raises(ValueError, match=match):
+                call()
