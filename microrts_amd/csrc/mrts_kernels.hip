@@ -140,7 +140,7 @@ enum : uint32_t { TR_ISSUED = 1u, TR_GAMEOVER = 2u, TR_NO_UNIT = 4u };
 // 1: partially observable multi-step launches without the render helper wave (tools/po_helper_repro.py).  Round 4
 // had made it the default after its full-size soak found 2 of 2048 c5 games with one stale observation value
 // for a unit that died in the observed step; round 5 found the cause (the renders read the dead unit's
-// fields by readlane inside their divergent chunk loop, from a lane that was off there — writeObsPOFast)
+// fields by readlane inside their divergent chunk loop, from a lane that was off there — poChunk)
 // and the helper is back on.
 #ifndef MRTS_NO_PO_HELPER
 #define MRTS_NO_PO_HELPER 0
@@ -2124,22 +2124,10 @@ struct Game {
         const int t = utyp(u);
         paintDiskRows(rows, H, W, ux(u), uy(u), U.sight[t], U.diskLo[t], U.diskHi[t]);
     }
-    // paintDisk for every lane with `act` at once, maps with W <= 32 (one row word) and sight <= 15:
-    // a uniform loop over dy up to the table's largest sight, one predicated atomicOr per row
-    DEV void paintDisks(bool act, uint32_t u, uint32_t* rows) const {
-        const int t = utyp(u), x = ux(u), y = uy(u);
-        const int sr = act ? U.sight[t] : -1, SM = U.maxSight;
-        const uint32_t dlo = act ? U.diskLo[t] : 0u, dhi = act ? U.diskHi[t] : 0u;
-        for (int dy = -SM; dy <= SM; dy++) {
-            const int yy = y + dy, ady = dy < 0 ? -dy : dy;
-            const int w = (int)(((ady < 8 ? dlo : dhi) >> (4 * (ady & 7))) & 0xFu);
-            const int x0 = max(0, x - w), x1 = min(W - 1, x + w);
-            const uint32_t b = ((2u << (x1 - x0)) - 1u) << x0;  // columns x0..x1 (x1 - x0 = 31: 2u << 31 wraps to 0)
-            if (ady <= sr && yy >= 0 && yy < H) atomicOr(&rows[yy], b);
-        }
-    }
-    // paintDisks into two views at once: the same disk (same unit) ORed into view 0's rows when act0
-    // and into view 1's when act1 (row buffers rows0 / rows1 chosen per lane)
+    // paintDisk for every lane with act0 or act1 at once, maps with W <= 32 (one row word) and sight
+    // <= 15: a uniform loop over dy up to the table's largest sight, one predicated atomicOr per row
+    // and view.  Two views at once: the same disk (same unit) ORed into view 0's rows when act0 and
+    // into view 1's when act1 (row buffers rows0 / rows1 chosen per lane).
     DEV void paintDisks2(bool act0, uint32_t* rows0, bool act1, uint32_t* rows1, uint32_t u) const {
         const bool act = act0 || act1;
         const int t = utyp(u), x = ux(u), y = uy(u);
@@ -2149,12 +2137,14 @@ struct Game {
             const int yy = y + dy, ady = dy < 0 ? -dy : dy;
             const int w = (int)(((ady < 8 ? dlo : dhi) >> (4 * (ady & 7))) & 0xFu);
             const int x0 = max(0, x - w), x1 = min(W - 1, x + w);
-            const uint32_t b = ((2u << (x1 - x0)) - 1u) << x0;
+            const uint32_t b = ((2u << (x1 - x0)) - 1u) << x0;  // columns x0..x1 (x1 - x0 = 31: 2u << 31 wraps to 0)
             const bool row = ady <= sr && yy >= 0 && yy < H;
             if (row && act0) atomicOr(&rows0[yy], b);
             if (row && act1) atomicOr(&rows1[yy], b);
         }
     }
+    // one view (the second view's arm folds away)
+    DEV void paintDisks(bool act, uint32_t u, uint32_t* rows) const { paintDisks2(act, rows, false, rows, u); }
     DEV bool seen(const uint32_t* rows, int x, int y) const {
         const int WPR = (W + 31) >> 5;
         return (rows[y * WPR + (x >> 5)] >> (x & 31)) & 1u;
@@ -3028,22 +3018,136 @@ struct Game {
     // or rendered fields changed (before and after — slots keep their index until the compaction),
     // those of rendered units that died last step (gone from the list: poPend), and the exact XOR
     // of old and new sight rows.  Only the 4-cell chunks holding them are rendered and stored.
+    // The passes that the renderers share are defined here, once: the plane values and the row chunks
+    // for all four (the general writeObsPO, writeObsPOFast, writeObsPOFast2, the helper's renderPOPacked),
+    // the unit chunks for the first three, the item list and the chunk render for the game wave's two
+    // fast forms.
+
+    // cell c's 4-cell chunk into a chunk bitmap (32 chunks = 128 cells per word)
+    DEV void poMarkCell(uint32_t* bits, int c) const { atomicOr(&bits[c >> 7], 1u << ((c >> 2) & 31)); }
+    // The eight plane values of one cell in view v.  occ: a unit of the view's snapshot is the cell's
+    // last writer, with unit word cu, snapshot byte sb, hp h and resources r (ignored without one);
+    // mr / tr: the words of the view's own / the other player's sight rows whose bit x is this cell's.
+    DEV void poPlanes(int* o, bool occ, uint32_t cu, uint32_t sb, int h, int r, bool wall, int v, uint32_t mr, uint32_t tr, int x) const {
+        const int pl = uplay(cu), sa = snap_act(sb, v);
+        o[0] = occ ? h : 0;
+        o[1] = occ ? r : 0;
+        o[2] = (occ && pl >= 0) ? ((pl + v) % 2) + 1 : 0;
+        o[3] = occ ? utyp(cu) + 1 : 0;
+        o[4] = (occ && sa) ? sa - 1 : 0;
+        o[5] = wall ? 1 : 0;
+        o[6] = (int)((mr >> x) & 1u);
+        o[7] = (int)((tr >> x) & 1u);
+    }
+    // A sight row's changed columns d (old XOR new row word: W <= 32) into the dirty bits of that
+    // row's chunks.  k0 = the row's first chunk (W / 4 chunks per row, <= 8); the row's chunk bits
+    // go out in one atomic unless they straddle two dirty words (24x24: k0 = 30 at y = 5).
+    DEV void poRowChunks(uint32_t* dirty, uint32_t d, int k0) const {
+        if (!d) return;
+        uint32_t gbits = 0;  // bit j = column group 4j..4j+3 changed
+#pragma unroll
+        for (int j = 0; j < 8; j++) gbits |= ((d >> (4 * j)) & 0xFu) ? (1u << j) : 0u;
+        if ((k0 & 31) + (W >> 2) <= 32) {
+            atomicOr(&dirty[k0 >> 5], gbits << (k0 & 31));
+        } else {
+            for (uint32_t gg = gbits; gg; gg &= gg - 1) {
+                const int k = k0 + __builtin_ctz(gg);
+                atomicOr(&dirty[k >> 5], 1u << (k & 31));
+            }
+        }
+    }
+    // View v's change test for the unit of one slot, into the view's dirty bits.  in: the unit is in
+    // the view now, at cell cc with snapshot byte sb and key = hp | resources << 16; had: the slot
+    // held a unit at the previous render, at cell cp with that render's snapshot byte lsnapP and key
+    // lkeyP.  A unit that entered or left the view, moved, or changed a rendered field dirties the
+    // chunk it was rendered in and the chunk it is rendered in.
+    DEV void poUnitChunks(uint32_t* dirty, int v, bool in, bool had, int cc, int cp, uint32_t sb, uint32_t key,
+                          uint32_t lsnapP, uint32_t lkeyP) const {
+        const bool inP = had && ((lsnapP >> v) & 1u);
+        bool chg = in != inP;
+        if (in && inP) chg = cc != cp || key != lkeyP || snap_act(sb, v) != (int)((lsnapP >> (2 + 3 * v)) & 7u);
+        if (chg && inP) poMarkCell(dirty, cp);
+        if (chg && in) poMarkCell(dirty, cc);
+    }
+    // A dirty bitmap into the item list: tag | k for every chunk k < HW / 4 whose bit is set (all:
+    // for every chunk), in chunk order, from poList[n] on; the new item count.  Lane l of the whole
+    // wave (ballots).  writeObsPOFast passes constants for `all` and `tag`, which fold away.
+    DEV int poListChunks(int l, int n, const uint32_t* dirty, bool all, uint32_t tag) {
+        const int NC = HW >> 2;
+#pragma unroll
+        for (int c0 = 0; c0 < 256; c0 += 64) {  // NC <= 256 (H, W <= 32)
+            if (c0 < NC) {
+                const int k = c0 + l;
+                const bool dk = k < NC && (all || ((dirty[k >> 5] >> (k & 31)) & 1u));
+                const uint64_t m = ballot(dk);
+                if (dk) poList[n + lanes_below(m)] = (uint16_t)(tag | (uint32_t)k);
+                n += __popcll(m);
+            }
+        }
+        return n;
+    }
+    // Chunk c4's four cells in view v, as plane values o[cell][plane].  A cell's last snapshot writer
+    // (list order) is the later of its live occupant, when that unit is in the view, and the view's
+    // dead units on it (few), so no per-cell scratch map is built.  deadAll: the slots of the dead
+    // units the wave walks (uniform: of both views in a two-view render); deadView: those of view v.
+    // rows: the view's sight rows [mine H][theirs H].  Shared by the game wave's renders (writeObsPOFast,
+    // writeObsPOFast2), which read the live LDS state; the helper wave's renderPOPacked reads a pack and
+    // has the same loop over it.
+    DEV void poChunk(int v, int c4, uint64_t deadAll, uint64_t deadView, const uint32_t* rows, int (&o)[4][8]) const {
+        const int y = (4 * c4) / W, x0 = (4 * c4) % W;  // lane = 4 consecutive cells of one row
+        int cs[4], sl[4];
+#pragma unroll
+        for (int j = 0; j < 4; j++) cs[j] = cell[4 * c4 + j];
+        const uint32_t mr = rows[y], tr = rows[H + y];
+        uint32_t ocu[4], osb[4];
+        int ohp[4], ors[4];
+#pragma unroll
+        for (int j = 0; j < 4; j++) {  // the live occupant's fields (an empty cell reads slot 0, masked)
+            const int s = cs[j] < CAP ? cs[j] : 0;
+            ocu[j] = uc[s];
+            osb[j] = snap[s];
+            ohp[j] = hp[s];
+            ors[j] = res[s];
+        }
+#pragma unroll
+        for (int j = 0; j < 4; j++) sl[j] = (cs[j] < CAP && snap_in(osb[j], v)) ? cs[j] : -1;
+        for (uint64_t m = deadAll; m; m &= m - 1) {  // the view's dead units: a later list position wins
+            const int ds = __builtin_ctzll(m);
+            // the dead unit's fields from LDS, never by readlane: this loop is divergent (lanes >= n
+            // are off), and the compiler may recompute a lane's cu / hp / snapshot byte inside it for
+            // the active lanes only, so a readlane of an inactive lane returns a stale register
+            // (round 4's soak saw the stale value in c5, round 5 found this cause in all three fast
+            // renders: DESIGN.md §4)
+            const uint32_t dcu = uc[ds];
+            const int dcell = uy(dcu) * W + ux(dcu);
+            const int dh = hp[ds], dr = res[ds];
+            const uint32_t dsb = snap[ds];
+            const bool mine = (deadView >> ds) & 1ull;
+#pragma unroll
+            for (int j = 0; j < 4; j++)
+                if (mine && dcell == 4 * c4 + j && ds > sl[j]) {
+                    sl[j] = ds;
+                    ocu[j] = dcu;
+                    osb[j] = dsb;
+                    ohp[j] = dh;
+                    ors[j] = dr;
+                }
+        }
+#pragma unroll
+        for (int j = 0; j < 4; j++) poPlanes(o[j], sl[j] >= 0, ocu[j], osb[j], ohp[j], ors[j], cs[j] == WALL, v, mr, tr, x0 + j);
+    }
     // writeObsPO for maps with W % 4 == 0, W <= 32 (one word per sight row), H <= 32, sight <= 15
     // and every unit in one wave (lane = slot).  One unit pass paints the sight disks, marks the
     // chunks of changed units (delta) and of the view's dead units (the next record's pending
-    // chunks).  A cell's last snapshot writer (list order) is the later of its live occupant (cell
-    // map), when that unit is in the view, and the view's dead units on it (a register list: few),
-    // so no per-cell scratch map is built.  Same output as the general form below.
+    // chunks).  Same output as the general form below.
     DEV void writeObsPOFast(int slot, int p, bool delta) {
         const int l = lid(), NCW = poChunkWords(HW), NC = HW >> 2;
-        uint32_t* mineRows = vis;
-        uint32_t* theirRows = vis + H;
         uint32_t* dirty = poDirty;
         uint32_t* nextPend = poDirty + NCW;
         int32_t* pr = D.po_prev ? D.po_prev + (size_t)g * D.po_words : nullptr;
         const int SW = poSnapWords(CAP);
         const int nu0 = delta ? hget(H_NU) : 0;  // the header holds the loaded unit count until store()
-        if (l < 2 * H) vis[l] = 0;
+        if (l < 2 * H) vis[l] = 0;  // [mine H][theirs H]
         if (l < NCW) {
             dirty[l] = delta ? poPend[p * NCW + l] : 0u;
             nextPend[l] = 0u;
@@ -3067,115 +3171,28 @@ struct Game {
 #ifdef MRTS_ABLATE
         if (!ab(AB_PO_NOPAINT))
 #endif
-        if (ballot(painter)) paintDisks(painter, cu, uplay(cu) == p ? mineRows : theirRows);
+        if (ballot(painter)) paintDisks(painter, cu, uplay(cu) == p ? vis : vis + H);
         const uint64_t deadM = ballot(dead);
-        if (pr && dead) atomicOr(&nextPend[cc >> 7], 1u << ((cc >> 2) & 31));
+        if (pr && dead) poMarkCell(nextPend, cc);
         if (delta && (live || l < nu0)) {
-            const bool inP = l < nu0 && ((lsnap >> p) & 1u);
-            const int cp = uy(lcu) * W + ux(lcu);
-            bool chg = in != inP;
-            if (in && inP) {
-                const uint32_t key = (uint32_t)(uint16_t)hv | ((uint32_t)(uint16_t)rv << 16);
-                chg = cc != cp || key != lkey || snap_act(sb, p) != (int)((lsnap >> (2 + 3 * p)) & 7u);
-            }
-            if (chg && inP) atomicOr(&dirty[cp >> 7], 1u << ((cp >> 2) & 31));
-            if (chg && in) atomicOr(&dirty[cc >> 7], 1u << ((cc >> 2) & 31));
+            const uint32_t key = (uint32_t)(uint16_t)hv | ((uint32_t)(uint16_t)rv << 16);
+            poUnitChunks(dirty, p, in, l < nu0, cc, uy(lcu) * W + ux(lcu), sb, key, lsnap, lkey);
         }
         wsync();
         if (l < 2 * H) {  // sight rows: changed columns -> chunk bits of that row; the record's copy
             const uint32_t row = vis[l];
-            if (delta) {
-                const uint32_t d = row ^ poVis[p * 2 * H + l];
-                if (d) {
-                    const int y = l < H ? l : l - H;
-                    uint32_t gbits = 0;  // bit j = column group 4j..4j+3 changed
-#pragma unroll
-                    for (int j = 0; j < 8; j++) gbits |= ((d >> (4 * j)) & 0xFu) ? (1u << j) : 0u;
-                    const int k0 = y * (W >> 2);
-                    if ((k0 & 31) + (W >> 2) <= 32) {
-                        atomicOr(&dirty[k0 >> 5], gbits << (k0 & 31));
-                    } else {
-                        for (uint32_t gg = gbits; gg; gg &= gg - 1) {
-                            const int k = k0 + __builtin_ctz(gg);
-                            atomicOr(&dirty[k >> 5], 1u << (k & 31));
-                        }
-                    }
-                }
-            }
+            if (delta) poRowChunks(dirty, row ^ poVis[p * 2 * H + l], (l < H ? l : l - H) * (W >> 2));
             if (pr) pr[1 + SW + p * 2 * H + l] = (int32_t)row;
         }
         wsync();
-        int n = NC;  // chunks to render: all, or the dirty list
-        if (delta) {
-            n = 0;
-#pragma unroll
-            for (int c0 = 0; c0 < 256; c0 += 64) {  // NC <= 256 (H, W <= 32)
-                if (c0 < NC) {
-                    const int k = c0 + l;
-                    const bool dk = k < NC && ((dirty[k >> 5] >> (k & 31)) & 1u);
-                    const uint64_t m = ballot(dk);
-                    if (dk) poList[n + lanes_below(m)] = (uint16_t)k;
-                    n += __popcll(m);
-                }
-            }
-        }
+        const int n = delta ? poListChunks(l, 0, dirty, false, 0u) : NC;  // chunks to render: the dirty list, or all
         if (pr && l < NCW) pr[1 + SW + 4 * H + p * NCW + l] = (int32_t)nextPend[l];
         wsync();
         int32_t* out = D.obs + (size_t)slot * D.C * HW;
         for (int it = l; it < n; it += 64) {
-            const int c4 = delta ? (int)poList[it] : it;  // lane = 4 consecutive cells of one row
-            const int y = (4 * c4) / W, x0 = (4 * c4) % W;
-            int cs[4], sl[4];
-#pragma unroll
-            for (int j = 0; j < 4; j++) cs[j] = cell[4 * c4 + j];
-            const uint32_t mr = mineRows[y], tr = theirRows[y];
-            uint32_t ocu[4], osb[4];
-            int ohp[4], ors[4];
-#pragma unroll
-            for (int j = 0; j < 4; j++) {  // the live occupant's fields (an empty cell reads slot 0, masked)
-                const int s = cs[j] < CAP ? cs[j] : 0;
-                ocu[j] = uc[s];
-                osb[j] = snap[s];
-                ohp[j] = hp[s];
-                ors[j] = res[s];
-            }
-#pragma unroll
-            for (int j = 0; j < 4; j++) sl[j] = (cs[j] < CAP && snap_in(osb[j], p)) ? cs[j] : -1;
-            for (uint64_t m = deadM; m; m &= m - 1) {  // the view's dead units: a later list position wins
-                const int ds = __builtin_ctzll(m);
-                // the dead unit's fields from LDS, never by readlane: this loop is divergent (lanes >= n
-                // are off), and the compiler may recompute a lane's cu / hp / snapshot byte inside it for
-                // the active lanes only, so a readlane of an inactive lane returns a stale register
-                // (round 5: the c5 helper's stale-value case)
-                const uint32_t dcu = uc[ds];
-                const int dcell = uy(dcu) * W + ux(dcu);
-                const int dh = hp[ds], dr = res[ds];
-                const uint32_t dsb = snap[ds];
-#pragma unroll
-                for (int j = 0; j < 4; j++)
-                    if (dcell == 4 * c4 + j && ds > sl[j]) {
-                        sl[j] = ds;
-                        ocu[j] = dcu;
-                        osb[j] = dsb;
-                        ohp[j] = dh;
-                        ors[j] = dr;
-                    }
-            }
+            const int c4 = delta ? (int)poList[it] : it;
             int v[4][8];
-#pragma unroll
-            for (int j = 0; j < 4; j++) {
-                const bool occ = sl[j] >= 0;
-                const int pl = uplay(ocu[j]);
-                const int sa = snap_act(osb[j], p);
-                v[j][0] = occ ? ohp[j] : 0;
-                v[j][1] = occ ? ors[j] : 0;
-                v[j][2] = (occ && pl >= 0) ? ((pl + p) % 2) + 1 : 0;
-                v[j][3] = occ ? utyp(ocu[j]) + 1 : 0;
-                v[j][4] = (occ && sa) ? sa - 1 : 0;
-                v[j][5] = cs[j] == WALL ? 1 : 0;
-                v[j][6] = (int)((mr >> (x0 + j)) & 1u);
-                v[j][7] = (int)((tr >> (x0 + j)) & 1u);
-            }
+            poChunk(p, c4, deadM, deadM, vis, v);
             const __amdgpu_buffer_rsrc_t rs = bufRsrc(out, (uint32_t)(D.C * HW * 4));
 #pragma unroll
             for (int k = 0; k < 8; k++) st4sc1(rs, (uint32_t)(k * HW + 4 * c4) * 4u, v[0][k], v[1][k], v[2][k], v[3][k]);
@@ -3188,18 +3205,19 @@ struct Game {
     // item — half the dependent LDS rounds of two writeObsPOFast calls.  delta: bit v = view v's
     // buffer holds its previous render (writeObsPOFast's delta).  Same output as
     // writeObsPOFast(slot0, 0, delta & 1) followed by writeObsPOFast(slot0 + 1, 1, delta >> 1 & 1).
+    // The record's global copy is for the next launch: inside a multi-step launch this render keeps the
+    // record in LDS (poLds: poVis, poPend) and the next iteration reads it there, so only the last
+    // iteration stores it (the sight rows and pending chunks here, the snapshot bytes in poRecordSnaps).
     DEV void writeObsPOFast2(int slot0, uint32_t delta) {
-        const int l = lid(), NCW = poChunkWords(HW), NC = HW >> 2;
-        uint32_t* const rowsV0 = vis;   // [mine H][theirs H]
+        const int l = lid();
+        uint32_t* const rowsV0 = vis;  // [mine H][theirs H]
+        const int nu0 = delta ? hget(H_NU) : 0;  // the header holds the loaded unit count until store()
+        const int NCW = poChunkWords(HW);
         uint32_t* const rowsV1 = vis2;
         int32_t* pr = D.po_prev ? D.po_prev + (size_t)g * D.po_words : nullptr;
-        // the record's global copy is for the next launch: inside a multi-step launch this render keeps
-        // the record in LDS (poLds) and the next iteration reads it there, so only the last iteration
-        // stores it (the sight rows and pending chunks here, the snapshot bytes in poRecordSnaps)
         int32_t* const prG = (!iter || lastIt) ? pr : nullptr;
         const int SW = poSnapWords(CAP);
         const bool d0 = delta & 1u, d1 = (delta >> 1) & 1u;
-        const int nu0 = delta ? hget(H_NU) : 0;  // the header holds the loaded unit count until store()
         if (l < 2 * H) {
             rowsV0[l] = 0;
             rowsV1[l] = 0;
@@ -3234,71 +3252,31 @@ struct Game {
                 paintDisks2(pt0, own == 0 ? rowsV0 : rowsV0 + H, pt1, own == 1 ? rowsV1 : rowsV1 + H, cu);
         }
         const uint64_t deadM0 = ballot(dead0), deadM1 = ballot(dead1);
-        if (pr && dead0) atomicOr(&poDirty[NCW + (cc >> 7)], 1u << ((cc >> 2) & 31));
-        if (pr && dead1) atomicOr(&poDirty[3 * NCW + (cc >> 7)], 1u << ((cc >> 2) & 31));
+        if (pr && dead0) poMarkCell(poDirty + NCW, cc);
+        if (pr && dead1) poMarkCell(poDirty + 3 * NCW, cc);
         if (delta && (live || l < nu0)) {
             const int cp = uy(lcu) * W + ux(lcu);
             const uint32_t key = (uint32_t)(uint16_t)hv | ((uint32_t)(uint16_t)rv << 16);
-#pragma unroll
-            for (int v = 0; v < 2; v++) {
-                if (!(v ? d1 : d0)) continue;
-                const bool in = v ? in1 : in0;
-                const bool inP = l < nu0 && ((lsnap >> v) & 1u);
-                bool chg = in != inP;
-                if (in && inP)
-                    chg = cc != cp || key != lkey || snap_act(sb, v) != (int)((lsnap >> (2 + 3 * v)) & 7u);
-                uint32_t* dirty = poDirty + 2 * v * NCW;
-                if (chg && inP) atomicOr(&dirty[cp >> 7], 1u << ((cp >> 2) & 31));
-                if (chg && in) atomicOr(&dirty[cc >> 7], 1u << ((cc >> 2) & 31));
-            }
+            if (d0) poUnitChunks(poDirty, 0, in0, l < nu0, cc, cp, sb, key, lsnap, lkey);
+            if (d1) poUnitChunks(poDirty + 2 * NCW, 1, in1, l < nu0, cc, cp, sb, key, lsnap, lkey);
         }
         wsync();
         if (l < 2 * H) {  // sight rows: changed columns -> chunk bits of that row; the record's copies
-            const int y = l < H ? l : l - H;
-            const int k0 = y * (W >> 2);
+            const int k0 = (l < H ? l : l - H) * (W >> 2);
 #pragma unroll
             for (int v = 0; v < 2; v++) {
                 const uint32_t row = (v ? rowsV1 : rowsV0)[l];
-                if (v ? d1 : d0) {
-                    const uint32_t d = row ^ poVis[v * 2 * H + l];
-                    poVis[v * 2 * H + l] = row;  // the record's LDS copy (a multi-step launch's next render)
-                    if (d) {
-                        uint32_t gbits = 0;  // bit j = column group 4j..4j+3 changed
-#pragma unroll
-                        for (int j = 0; j < 8; j++) gbits |= ((d >> (4 * j)) & 0xFu) ? (1u << j) : 0u;
-                        uint32_t* dirty = poDirty + 2 * v * NCW;
-                        if ((k0 & 31) + (W >> 2) <= 32) {
-                            atomicOr(&dirty[k0 >> 5], gbits << (k0 & 31));
-                        } else {
-                            for (uint32_t gg = gbits; gg; gg &= gg - 1) {
-                                const int k = k0 + __builtin_ctz(gg);
-                                atomicOr(&dirty[k >> 5], 1u << (k & 31));
-                            }
-                        }
-                    }
-                }
+                if (v ? d1 : d0) poRowChunks(poDirty + 2 * v * NCW, row ^ poVis[v * 2 * H + l], k0);
+                // the record's LDS copy.  Only this lane reads or writes this word of poVis between the
+                // barriers around this pass, so the store may sit anywhere after the read above.
+                poVis[v * 2 * H + l] = row;
                 if (prG) prG[1 + SW + v * 2 * H + l] = (int32_t)row;
-                if (!(v ? d1 : d0)) poVis[v * 2 * H + l] = row;
             }
         }
         wsync();
         // one list of (view << 15 | chunk) items: view 0's dirty chunks (all, without delta), then view 1's
-        int n = 0;
-#pragma unroll
-        for (int v = 0; v < 2; v++) {
-            const bool dv = v ? d1 : d0;
-            const uint32_t* dirty = poDirty + 2 * v * NCW;
-#pragma unroll
-            for (int c0 = 0; c0 < 256; c0 += 64) {  // NC <= 256 (H, W <= 32)
-                if (c0 < NC) {
-                    const int k = c0 + l;
-                    const bool dk = k < NC && (!dv || ((dirty[k >> 5] >> (k & 31)) & 1u));
-                    const uint64_t m = ballot(dk);
-                    if (dk) poList[n + lanes_below(m)] = (uint16_t)((v << 15) | k);
-                    n += __popcll(m);
-                }
-            }
-        }
+        int n = poListChunks(l, 0, poDirty, !d0, 0u);
+        n = poListChunks(l, n, poDirty + 2 * NCW, !d1, 1u << 15);
         if (pr && l < NCW) {
             if (prG) {
                 prG[1 + SW + 4 * H + l] = (int32_t)poDirty[NCW + l];
@@ -3322,59 +3300,9 @@ struct Game {
         const uint64_t deadAny = deadM0 | deadM1;
         for (int it = l; it < n; it += 64) {
             const uint32_t e = poList[it];
-            const int v = (int)(e >> 15), c4 = (int)(e & 0x7FFFu);  // lane = 4 consecutive cells of one row
-            const uint64_t deadM = v ? deadM1 : deadM0;
-            const int y = (4 * c4) / W, x0 = (4 * c4) % W;
-            const uint32_t* rows = v ? rowsV1 : rowsV0;
-            int cs[4], sl[4];
-#pragma unroll
-            for (int j = 0; j < 4; j++) cs[j] = cell[4 * c4 + j];
-            const uint32_t mr = rows[y], tr = rows[H + y];
-            uint32_t ocu[4], osb[4];
-            int ohp[4], ors[4];
-#pragma unroll
-            for (int j = 0; j < 4; j++) {  // the live occupant's fields (an empty cell reads slot 0, masked)
-                const int s = cs[j] < CAP ? cs[j] : 0;
-                ocu[j] = uc[s];
-                osb[j] = snap[s];
-                ohp[j] = hp[s];
-                ors[j] = res[s];
-            }
-#pragma unroll
-            for (int j = 0; j < 4; j++) sl[j] = (cs[j] < CAP && snap_in(osb[j], v)) ? cs[j] : -1;
-            for (uint64_t m = deadAny; m; m &= m - 1) {  // the view's dead units: a later list position wins
-                const int ds = __builtin_ctzll(m);
-                // from LDS, not by readlane of an inactive lane (writeObsPOFast)
-                const uint32_t dcu = uc[ds];
-                const int dcell = uy(dcu) * W + ux(dcu);
-                const int dh = hp[ds], dr = res[ds];
-                const uint32_t dsb = snap[ds];
-                const bool mine = (deadM >> ds) & 1ull;
-#pragma unroll
-                for (int j = 0; j < 4; j++)
-                    if (mine && dcell == 4 * c4 + j && ds > sl[j]) {
-                        sl[j] = ds;
-                        ocu[j] = dcu;
-                        osb[j] = dsb;
-                        ohp[j] = dh;
-                        ors[j] = dr;
-                    }
-            }
+            const int v = (int)(e >> 15), c4 = (int)(e & 0x7FFFu);
             int vv[4][8];
-#pragma unroll
-            for (int j = 0; j < 4; j++) {
-                const bool occ = sl[j] >= 0;
-                const int pl = uplay(ocu[j]);
-                const int sa = snap_act(osb[j], v);
-                vv[j][0] = occ ? ohp[j] : 0;
-                vv[j][1] = occ ? ors[j] : 0;
-                vv[j][2] = (occ && pl >= 0) ? ((pl + v) % 2) + 1 : 0;
-                vv[j][3] = occ ? utyp(ocu[j]) + 1 : 0;
-                vv[j][4] = (occ && sa) ? sa - 1 : 0;
-                vv[j][5] = cs[j] == WALL ? 1 : 0;
-                vv[j][6] = (int)((mr >> (x0 + j)) & 1u);
-                vv[j][7] = (int)((tr >> (x0 + j)) & 1u);
-            }
+            poChunk(v, c4, deadAny, v ? deadM1 : deadM0, v ? rowsV1 : rowsV0, vv);
             const uint32_t base = (uint32_t)(v * D.C * HW + 4 * c4) * 4u;
 #ifdef MRTS_ABLATE
             if (ab(AB_PO_ZEROSTORE)) {  // pricing: the render's values computed, not stored
@@ -3487,7 +3415,9 @@ struct Game {
         wsync();
     }
     // writeObsPOFast2 as run by the helper wave (lane l = threadIdx.x - 64) from a packed step (packPO):
-    // the same passes and stores.  What the game wave's live LDS state gave it comes from the pack:
+    // the same passes and stores, written out here and not shared with it beyond poPlanes and
+    // poRowChunks: built from the game wave's shared passes over a pack-reading source, the c5 helper
+    // instance measured 0.4 - 1.2 % slower (profiles/po_render_refactor.md).  What the game wave's live LDS state gave it comes from the pack:
     // the units' fields, and the live occupant of a cell from hcell (slot, or 0xFF), a per-step map
     // built here from the packed positions (a unit in the list and not dead = the game's cell map);
     // walls from the game's cell map (WALL entries are static: units never stand on walls).  rowsV0 =
@@ -3559,20 +3489,7 @@ struct Game {
                 const uint32_t row = (v ? rowsV1 : rowsV0)[l];
                 if (v ? d1 : d0) {
                     const uint32_t d = row ^ poVis[v * 2 * H + l];
-                    if (d) {
-                        uint32_t gbits = 0;  // bit j = column group 4j..4j+3 changed
-#pragma unroll
-                        for (int j = 0; j < 8; j++) gbits |= ((d >> (4 * j)) & 0xFu) ? (1u << j) : 0u;
-                        uint32_t* dirty = poDirty + 2 * v * NCW;
-                        if ((k0 & 31) + (W >> 2) <= 32) {
-                            atomicOr(&dirty[k0 >> 5], gbits << (k0 & 31));
-                        } else {
-                            for (uint32_t gg = gbits; gg; gg &= gg - 1) {
-                                const int k = k0 + __builtin_ctz(gg);
-                                atomicOr(&dirty[k >> 5], 1u << (k & 31));
-                            }
-                        }
-                    }
+                    poRowChunks(poDirty + 2 * v * NCW, d, k0);
                 }
                 poVis[v * 2 * H + l] = row;  // the record's LDS copy (the next render)
                 if (prG) prG[1 + SW + v * 2 * H + l] = (int32_t)row;
@@ -3636,7 +3553,7 @@ struct Game {
             for (int j = 0; j < 4; j++) sl[j] = (cs[j] < CAP && snap_in(osb[j], v)) ? cs[j] : -1;
             for (uint64_t m = deadAny; m; m &= m - 1) {  // the view's dead units: a later list position wins
                 const int ds = __builtin_ctzll(m);
-                // from the pack, not by readlane of an inactive lane (writeObsPOFast): the compiler sank
+                // from the pack, not by readlane of an inactive lane (poChunk's comment): the compiler sank
                 // this wave's pack reads (cu, hp | res, snapshot byte) into the divergent item loop, so
                 // lane ds's registers held a stale value whenever lane ds had no item (round 4's soak case)
                 const uint32_t dcu = pk[ds], dkv = pk[64 + ds];
@@ -3656,25 +3573,16 @@ struct Game {
             }
             int vv[4][8];
 #pragma unroll
-            for (int j = 0; j < 4; j++) {
-                const bool occ = sl[j] >= 0;
-                const int pl = uplay(ocu[j]);
-                const int sa = snap_act(osb[j], v);
-                vv[j][0] = occ ? ohp[j] : 0;
-                vv[j][1] = occ ? ors[j] : 0;
-                vv[j][2] = (occ && pl >= 0) ? ((pl + v) % 2) + 1 : 0;
-                vv[j][3] = occ ? utyp(ocu[j]) + 1 : 0;
-                vv[j][4] = (occ && sa) ? sa - 1 : 0;
-                vv[j][5] = cs[j] == WALL ? 1 : 0;
-                vv[j][6] = (int)((mr >> (x0 + j)) & 1u);
-                vv[j][7] = (int)((tr >> (x0 + j)) & 1u);
-            }
+            for (int j = 0; j < 4; j++) poPlanes(vv[j], sl[j] >= 0, ocu[j], osb[j], ohp[j], ors[j], cs[j] == WALL, v, mr, tr, x0 + j);
             const uint32_t base = (uint32_t)(v * D.C * HW + 4 * c4) * 4u;
 #pragma unroll
             for (int k = 0; k < 8; k++) st4sc1(rs, base + (uint32_t)(k * HW) * 4u, vv[0][k], vv[1][k], vv[2][k], vv[3][k]);
         }
         wsync();
     }
+    // the general form: any map, any unit count.  The last snapshot writer of every cell goes into a
+    // per-cell scratch map (scell: slot + 1, the largest slot wins), the sight rows take several words
+    // per row when W > 32.  delta (poDeltaShape maps, at most 64 units): as writeObsPOFast.
     DEV void writeObsPO(int slot, int p, bool delta = false) {
         if ((W & 3) == 0 && W <= 32 && H <= 32 && nu <= 64 && U.maxSight <= 15) {
             writeObsPOFast(slot, p, delta);
@@ -3715,50 +3623,28 @@ struct Game {
             }
         }
         wsync();
-        const int NC = (HW + 3) >> 2, NCW = poChunkWords(HW);
-        int n = NC;  // chunks to render: all, or the dirty list (delta maps have HW % 4 == 0)
+        int n = (HW + 3) >> 2;  // chunks to render: all, or the dirty list (delta maps have HW % 4 == 0)
         if (delta) {
-            const int l = lid();
+            const int l = lid(), NCW = poChunkWords(HW);
             if (l < NCW) poDirty[l] = poPend[p * NCW + l];
             wsync();
             const int nu0 = hget(H_NU);  // the header holds the loaded unit count until store()
             if (l < nu || l < nu0) {
-                const uint32_t cu = l < nu ? uc[l] : 0u;
-                const uint32_t sb = l < nu ? (uint32_t)snap[l] : 0u;
-                const bool inC = l < nu && snap_in(sb, p), inP = l < nu0 && ((lsnap >> p) & 1u);
-                const int cc = uy(cu) * W + ux(cu), cp = uy(lcu) * W + ux(lcu);
-                bool chg = inC != inP;
-                if (inC && inP) {
-                    const uint32_t key = (uint32_t)(uint16_t)hp[l] | ((uint32_t)(uint16_t)res[l] << 16);
-                    chg = cc != cp || key != lkey || snap_act(sb, p) != (int)((lsnap >> (2 + 3 * p)) & 7u);
-                }
-                if (chg && inP) atomicOr(&poDirty[cp >> 7], 1u << ((cp >> 2) & 31));
-                if (chg && inC) atomicOr(&poDirty[cc >> 7], 1u << ((cc >> 2) & 31));
+                const bool live = l < nu;
+                const uint32_t cu = live ? uc[l] : 0u, sb = live ? (uint32_t)snap[l] : 0u;
+                const uint32_t key = live ? (uint32_t)(uint16_t)hp[l] | ((uint32_t)(uint16_t)res[l] << 16) : 0u;
+                poUnitChunks(poDirty, p, live && snap_in(sb, p), l < nu0, uy(cu) * W + ux(cu), uy(lcu) * W + ux(lcu), sb, key,
+                             lsnap, lkey);
             }
-            // sight rows (W <= 32: one word per row): changed columns -> chunk bits of that row
-            for (int i = l; i < 2 * H; i += 64) {
-                const uint32_t d = vis[i] ^ poVis[p * 2 * H + i];
-                if (d) {
-                    const int y = i < H ? i : i - H;
-                    uint32_t g = 0;  // bit j = column group 4j..4j+3 changed
-#pragma unroll
-                    for (int j = 0; j < 8; j++) g |= ((d >> (4 * j)) & 0xFu) ? (1u << j) : 0u;
-                    const int k0 = y * (W >> 2);  // first chunk of row y (W/4 chunks per row, <= 8)
-                    if ((k0 & 31) + (W >> 2) <= 32) {
-                        atomicOr(&poDirty[k0 >> 5], g << (k0 & 31));
-                    } else {
-                        for (uint32_t gg = g; gg; gg &= gg - 1) {
-                            const int k = k0 + __builtin_ctz(gg);
-                            atomicOr(&poDirty[k >> 5], 1u << (k & 31));
-                        }
-                    }
-                }
-            }
+            // sight rows (W <= 32: one word per row)
+            for (int i = l; i < 2 * H; i += 64) poRowChunks(poDirty, vis[i] ^ poVis[p * 2 * H + i], (i < H ? i : i - H) * (W >> 2));
             wsync();
+            // (a rolled loop of its own, not poListChunks' four unrolled rounds: this arm runs only for a
+            // sight radius above 15, and its size counts in every kernel that holds it)
             n = 0;
-            for (int c0 = 0; c0 < NC; c0 += 64) {
+            for (int c0 = 0; c0 < (HW >> 2); c0 += 64) {
                 const int k = c0 + l;
-                const bool dk = k < NC && ((poDirty[k >> 5] >> (k & 31)) & 1u);
+                const bool dk = k < (HW >> 2) && ((poDirty[k >> 5] >> (k & 31)) & 1u);
                 const uint64_t m = ballot(dk);
                 if (dk) poList[n + lanes_below(m)] = (uint16_t)k;
                 n += __popcll(m);
@@ -3771,32 +3657,25 @@ struct Game {
             int sc[4];
 #pragma unroll
             for (int j = 0; j < 4; j++) sc[j] = 4 * c4 + j < HW ? (int)scell[4 * c4 + j] - 1 : -1;
-            uint32_t cu[4];
-            int ch[4], cr[4], ca[4];
+            uint32_t cu[4], sb[4];
+            int ch[4], cr[4];
 #pragma unroll
             for (int j = 0; j < 4; j++) {  // branch-free: an empty cell reads slot 0 and is masked
                 const int s = sc[j] >= 0 ? sc[j] : 0;
                 cu[j] = uc[s];
                 ch[j] = hp[s];
                 cr[j] = res[s];
-                ca[j] = snap_act(snap[s], p);
+                sb[j] = snap[s];
             }
             const int cy = (4 * c4) / W, cx0 = (4 * c4) % W;  // W % 4 == 0 here, or one cell per lane below
             int v[4][8];
 #pragma unroll
             for (int j = 0; j < 4; j++) {
-                const bool occ = sc[j] >= 0;
-                const int pl = uplay(cu[j]);
-                v[j][0] = occ ? ch[j] : 0;
-                v[j][1] = occ ? cr[j] : 0;
-                v[j][2] = (occ && pl >= 0) ? ((pl + p) % 2) + 1 : 0;
-                v[j][3] = occ ? utyp(cu[j]) + 1 : 0;
-                v[j][4] = (occ && ca[j]) ? ca[j] - 1 : 0;
                 const bool in = 4 * c4 + j < HW;
-                v[j][5] = in && cell[4 * c4 + j] == WALL ? 1 : 0;
                 const int x = (W & 3) == 0 ? cx0 + j : (4 * c4 + j) % W, y = (W & 3) == 0 ? cy : (4 * c4 + j) / W;
-                v[j][6] = in && seen(mineRows, x, y) ? 1 : 0;
-                v[j][7] = in && seen(theirRows, x, y) ? 1 : 0;
+                // (the sight bits as words whose bit 0 is the cell's: rows of several words when W > 32)
+                poPlanes(v[j], sc[j] >= 0, cu[j], sb[j], ch[j], cr[j], in && cell[4 * c4 + j] == WALL, p,
+                         in && seen(mineRows, x, y) ? 1u : 0u, in && seen(theirRows, x, y) ? 1u : 0u, 0);
             }
             if ((HW & 3) == 0) {
 #pragma unroll
@@ -3824,10 +3703,7 @@ struct Game {
         wsync();
         for (int o = l; o < nu; o += 64) {
             const uint32_t cu = uc[o];
-            if ((cu & UC_DEAD) && snap_in(snap[o], p)) {
-                const int c = uy(cu) * W + ux(cu);
-                atomicOr(&poDirty[c >> 7], 1u << ((c >> 2) & 31));
-            }
+            if ((cu & UC_DEAD) && snap_in(snap[o], p)) poMarkCell(poDirty, uy(cu) * W + ux(cu));
         }
         wsync();
         if (l < NCW) pr[1 + SW + 4 * H + p * NCW + l] = (int32_t)poDirty[l];

@@ -759,6 +759,8 @@ def test_po_helper_wave_over_64_units(tmp_path):
     ("maps/8x8/basesWorkers8x8.xml", 8, 4, True, 0),          # Java rows (shuffled, duplicates)
     ("maps/24x24/basesWorkers24x24.xml", 8, 2, False, 0),
     ("maps/10x10/basesWorkers10x10.xml", 8, 2, False, 0),     # W % 4 != 0: always full renders
+    # a Worker that sees 16 cells: past the fast renders' sight limit, so the general writeObsPO renders the deltas
+    ("maps/8x8/basesWorkers8x8.xml", 8, 4, "sight16", 0),
 ])
 def test_po_obs_delta_matches_full(mp, n_sp, n_bot, rows, max_units):
     """Persistent-buffer partially observable observations (only the 4-cell chunks whose cells can have
@@ -766,14 +768,24 @@ def test_po_obs_delta_matches_full(mp, n_sp, n_bot, rows, max_units):
     in the last render, the XOR of old and new sight rows) stay byte-identical to full renders after
     every step: self-play and agent-vs-RandomBiasedAI games (the agent's side flips every 7 steps),
     auto-resets (max_steps 120), a caller's in-place edit of env.obs, a checkpoint restore and a
-    GameState.fromJSON injection."""
+    GameState.fromJSON injection.  rows: True = the actions as Java rows; "sight16" = the built-in
+    unit-type table with the Worker's sightRadius at 16 (the general renderer's delta arm: every other
+    row's deltas go through writeObsPOFast or the two-view render)."""
     torch = torch_gpu()
-    from microrts_amd import DeviceVecEnv
+    from microrts_amd import DeviceVecEnv, UnitTypeTable
 
+    utt = None
+    if rows == "sight16":
+        import json
+
+        rows = False
+        table = json.loads(UnitTypeTable().toJSON())
+        next(t for t in table["unitTypes"] if t["name"] == "Worker")["sightRadius"] = 16
+        utt = UnitTypeTable.fromJSON(json.dumps(table))
     S = n_sp + n_bot
     maps = [mp] * S
     bots = ["RandomBiasedAI"] * n_bot if n_bot else None
-    mk = lambda d: DeviceVecEnv(n_sp, n_bot, 120, maps, seed=8, ai2s=bots, partial_obs=True, obs_delta=d,  # noqa: E731
+    mk = lambda d: DeviceVecEnv(n_sp, n_bot, 120, maps, seed=8, ai2s=bots, utt=utt, partial_obs=True, obs_delta=d,  # noqa: E731
                                 max_units=max_units)
     a, b = mk(True), mk(False)
     a.reset()
