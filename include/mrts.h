@@ -51,9 +51,21 @@ enum {
     MRTS_RF_CLOSER_TO_ENEMY_UNIT = 7 /* CloserToEnemyUnitRewardFunction (the reference's text is identical to 6) */
 };
 
-/* per-game error flag bits (mrts_error_flags) */
+/* per-game error flag bits (mrts_error_flags).  The step kernels cannot throw: where Java throws or prints they
+ * set a bit in the game's state header and go on.  The refused action leaves the map like one that completed
+ * (its unit is idle again) and has no other effect: nothing is produced, nothing is paid.  (The exception is
+ * MRTS_ERR_MOVE_COLLISION, where Java moves the unit without a word and so do the kernels: two units then share
+ * a cell, and what the game does from there is outside every contract.)
+ * A bit stays set through the game's in-step auto-resets (game over, max_steps); only mrts_reset / mrts_reset_dev
+ * (every game) and mrts_set_state_json (that game) clear it.  The host-pointer calls (mrts_step, mrts_step_rows,
+ * mrts_playout, mrts_trace_step) read the flags after the step and answer the first of: -EINVAL for
+ * MRTS_ERR_PRODUCE_TYPE, -ENOSPC for MRTS_ERR_CAPACITY, -EFAULT for MRTS_ERR_ADDUNIT or MRTS_ERR_MOVE_COLLISION
+ * in any game; the step has run and the responses are filled.  Such a call fails again, step after step, until
+ * the flag is cleared.  The flags Java only prints for (OLDER_CONFLICT, NEG_RESOURCES) fail no call.
+ * (tests/test_gpu_error_flags.py pins all of this.) */
 enum {
-    MRTS_ERR_CAPACITY = 1u << 0,      /* unit slots exhausted (no Java equivalent; env must be reset) */
+    MRTS_ERR_CAPACITY = 1u << 0,      /* unit slots exhausted: a birth past max_units + max(64, max_units / 4) units in
+                                         one step is refused (no Java equivalent; env must be reset) */
     MRTS_ERR_ADDUNIT = 1u << 1,       /* produce into an occupied cell: Java throws (PhysicalGameState.java:192) */
     MRTS_ERR_PRODUCE_TYPE = 1u << 2,  /* decoded produce type out of range: Java throws (UnitAction.java:697) */
     MRTS_ERR_OLDER_CONFLICT = 1u << 3,/* issue() older-conflict branch: Java prints (GameState.java:298-317) */
@@ -527,7 +539,8 @@ int mrts_get_state(mrts_env* env, int32_t slot, int32_t* buf, int32_t cap);
  * (JNIGridnetClient.java:225-233).  NUL-terminated; returns the length, or -(length + 1) when cap
  * is too small, or a negative errno for an invalid table. */
 int mrts_utt_json(int32_t utt_version, int32_t conflict_policy, const char* utt_json, char* buf, int32_t cap);
-/* per-game error flags (MRTS_ERR_*), one uint32 per slot; synchronous */
+/* per-game error flags (MRTS_ERR_*), one uint32 per slot (both slots of a self-play game read their game's);
+ * synchronous.  Sticky: see the enum for what clears them and what they do to the host-pointer calls. */
 int mrts_error_flags(mrts_env* env, uint32_t* flags);
 /* per-slot envSteps (JNIGridnetVecClient.envSteps, :27); synchronous */
 int mrts_env_steps(mrts_env* env, int32_t* out);

@@ -6,6 +6,8 @@
 //   * the three built-in tables under each conflict policy, and the table file, round-trip through JSON;
 //   * every proper prefix of the smallest map, of the table file and of the smallest map's state goes to its parser:
 //     each must end in a Fail or a clean parse;
+//   * a MOVE or PRODUCE under way that points off the map is refused, from each of the four edges; a HARVEST or
+//     RETURN that does, and any of them along the edge, is kept;
 //   * the packed observation rows' word count and every refusal of their argument checks.
 // Any other exception leaves main (std::terminate), a sanitizer report aborts: both fail the make target.
 #include <cstdio>
@@ -44,8 +46,11 @@ static std::string stateOf(const MapDef& m, const UttInfo& utt) {
         w << (i ? "," : "") << "{\"type\":\"" << utt.names[(size_t)u.type] << "\", \"ID\":" << i << ", \"player\":" << u.player
           << ", \"x\":" << u.x << ", \"y\":" << u.y << ", \"resources\":" << u.res << ", \"hitpoints\":" << u.hp << "}";
         if (u.player < 0 || acts.size() == 3) continue;
-        static const char* const kinds[3] = {"{\"type\":1, \"parameter\":2}", "{\"type\":5, \"x\":0,\"y\":0}",
-                                             "{\"type\":4, \"parameter\":1, \"unitType\":\"Worker\"}"};
+        // (the MOVE goes down and the PRODUCE right, or from the last row / column up and left: a target on the map)
+        const std::string kinds[3] = {std::string("{\"type\":1, \"parameter\":") + (u.y + 1 < m.H ? "2}" : "0}"),
+                                      "{\"type\":5, \"x\":0,\"y\":0}",
+                                      std::string("{\"type\":4, \"parameter\":") + (u.x + 1 < m.W ? "1" : "3") +
+                                          ", \"unitType\":\"Worker\"}"};
         acts.push_back("{\"ID\":" + std::to_string(i) + ", \"time\":" + std::to_string(3 + acts.size()) + ", \"action\":" +
                        kinds[acts.size()] + "}");
     }
@@ -136,6 +141,39 @@ int main(int argc, char** argv) {
         std::vector<int32_t> s((size_t)stateWords(smallShape.CAP, smallShape.HW), 0);
         jsonToBlock(smallShape, t, s);
     });
+    // an action under way whose target cell lies off the map: MOVE and PRODUCE are refused (UnitAction.execute writes
+    // that cell unguarded), HARVEST and RETURN are kept (execute tests the cell first), as is a move along the edge
+    {
+        StateShape sh;
+        sh.H = 3, sh.W = 3, sh.HW = 9, sh.maxUnits = 9, sh.CAP = 9 + 64;
+        sh.uttInfo = utt;
+        static const int at[4][2] = {{1, 0}, {2, 1}, {1, 2}, {0, 1}};  // a cell on the edge direction d leaves by
+        int refused = 0, kept = 0;
+        for (int d = 0; d < 4; d++)
+            for (int t = 1; t <= 4; t++)
+                for (int side = 0; side < 2; side++) {  // off the map, then along the edge
+                    const int dir = side ? (d + 1) % 4 : d;
+                    std::ostringstream w;
+                    w << "{\"time\":9,\"pgs\":{\"width\":3,\"height\":3,\"terrain\":\"000000000\",\"players\":[{\"ID\":0, "
+                         "\"resources\":5},{\"ID\":1, \"resources\":5}],\"units\":[{\"type\":\"" << (t == 4 ? "Base" : "Worker")
+                      << "\", \"ID\":0, \"player\":0, \"x\":" << at[d][0] << ", \"y\":" << at[d][1]
+                      << ", \"resources\":0, \"hitpoints\":1}]},\"actions\":[{\"ID\":0, \"time\":8, \"action\":{\"type\":" << t
+                      << ", \"parameter\":" << dir << (t == 4 ? ", \"unitType\":\"Worker\"" : "") << "}}]}";
+                    std::vector<int32_t> s((size_t)stateWords(sh.CAP, sh.HW), 0);
+                    int rc = 0;
+                    try {
+                        jsonToBlock(sh, w.str(), s);
+                    } catch (const Fail& e) {
+                        rc = e.code;
+                        expect(e.msg.rfind("state json:", 0) == 0, "off-map refusal's text");
+                    }
+                    const bool off = !side && (t == 1 || t == 4);
+                    expect(rc == (off ? -ENOTSUP : 0), "action type " + std::to_string(t) + " direction " + std::to_string(dir) +
+                                                           (side ? " along the edge" : " off the map"));
+                    (rc ? refused : kept)++;
+                }
+        std::printf("actions at the map's edge: %d off-map MOVE / PRODUCE refused, %d others kept\n", refused, kept);
+    }
     // packed observation rows: the word count and every refusal of the argument checks (no buffer is dereferenced)
     {
         static_assert(obsPackedWords(6, 256, 128) == 265 && obsPackedWords(8, 1024, 128) == 353 && obsPackedWords(6, 72, 72) == 148,

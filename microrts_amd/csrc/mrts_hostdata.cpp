@@ -493,6 +493,12 @@ void jsonToBlock(const StateShape& env, const std::string& text, std::vector<int
             if (t < 0 || t > 5) throw Fail{-EINVAL, "state json: bad action type"};
             if (t == 5 && (tx < 0 || ty < 0 || tx >= W || ty >= H)) throw Fail{-ENOTSUP, "state json: attack target off the map"};
             if (t >= 1 && t <= 4 && (prm < 0 || prm > 3)) throw Fail{-ENOTSUP, "state json: bad direction"};
+            if (t == 1 || t == 4) {  // UnitAction.execute writes the target cell unguarded (HARVEST / RETURN test it first)
+                static const int DX[4] = {0, 1, 0, -1}, DY[4] = {-1, 0, 1, 0};  // UP, RIGHT, DOWN, LEFT
+                const int nx = (int)(c & 0xFF) + DX[prm], ny = (int)((c >> 8) & 0xFF) + DY[prm];
+                if (nx < 0 || ny < 0 || nx >= W || ny >= H)
+                    throw Fail{-ENOTSUP, t == 1 ? "state json: move target off the map" : "state json: produce target off the map"};
+            }
             if (t == 0 && (prm < -1 || prm > 32767)) throw Fail{-ENOTSUP, "state json: bad NONE duration"};
             if (t == 4) {
                 ut = env.uttInfo.typeOf(utn);

@@ -46,6 +46,7 @@ def load():
         L.oref_last_error.restype = ctypes.c_char_p
         L.oref_trace_replay.argtypes = [ctypes.c_char_p, ctypes.c_char_p, ctypes.c_char_p, I]
         L.oref_trace_dumps.argtypes = [ctypes.c_char_p, ctypes.c_char_p, P, ctypes.c_int64, P, P, I, ctypes.c_char_p, I]
+        L.oref_trace_dumps_lenient.argtypes = [ctypes.c_char_p, ctypes.c_char_p, P, ctypes.c_int64, P, P, P, I, ctypes.c_char_p, I]
         L.oref_policy.argtypes = [P, I, I, I, U64, ctypes.c_uint32, ctypes.c_uint32, ctypes.c_uint32, P]
         L.oref_botclient_create.restype = P
         L.oref_botclient_create.argtypes = [ctypes.c_char_p, I, I, I, I, I, ctypes.c_int64, ctypes.c_char_p]
@@ -78,10 +79,12 @@ def load():
     return _lib
 
 
-def trace_dumps(map_path, fixture_text):
+def trace_dumps(map_path, fixture_text, lenient=False):
     """Replay one converted reference trace (tests/golden/make_trace_fixtures.py) on the oracle with the
     rule of TestTracesIntegrity.java:72-127: the canonical state dump at every entry (after catching up
-    with its time, before its actions) and issueSafe's combined return value per entry."""
+    with its time, before its actions) and issueSafe's combined return value per entry.  lenient (a
+    hand-written trace): an entry whose real actions were all refused does not end the replay, and the
+    game's error count after every entry's issue comes back as a third array."""
     L = load()
     n = int(fixture_text.split(None, 2)[1])
     cap = 1 << 22
@@ -89,10 +92,16 @@ def trace_dumps(map_path, fixture_text):
     off = np.zeros(n + 1, dtype=np.int32)
     iss = np.zeros(max(n, 1), dtype=np.int32)
     msg = ctypes.create_string_buffer(1024)
-    r = L.oref_trace_dumps(map_path.encode(), fixture_text.encode(), _ptr(buf), cap, _ptr(off), _ptr(iss), n, msg, 1024)
+    if lenient:
+        errs = np.zeros(max(n, 1), dtype=np.int32)
+        r = L.oref_trace_dumps_lenient(map_path.encode(), fixture_text.encode(), _ptr(buf), cap, _ptr(off), _ptr(iss), _ptr(errs),
+                                       n, msg, 1024)
+    else:
+        r = L.oref_trace_dumps(map_path.encode(), fixture_text.encode(), _ptr(buf), cap, _ptr(off), _ptr(iss), n, msg, 1024)
     if r != n:
         raise RuntimeError(f"oracle trace replay: {r}: {msg.value.decode()}")
-    return [buf[off[e]:off[e + 1]].copy() for e in range(n)], iss[:n].copy()
+    out = [buf[off[e]:off[e + 1]].copy() for e in range(n)], iss[:n].copy()
+    return out + (errs[:n].copy(),) if lenient else out
 
 
 def _ptr(a):

@@ -4,6 +4,7 @@ through, and crowded copies of them that hold every unit type, both owners and m
 tests/test_gpu_every_shape.py steps the kernels from them against the oracle on all 17 map sizes;
 tests/test_state_cases_cpu.py keeps the case list honest on the oracle alone.  Test infrastructure
 only (a plain helper module, no fixtures of its own)."""
+import ctypes
 import functools
 import gzip
 import json
@@ -128,6 +129,25 @@ def crowd(state_json, seed, per_window=None):
         due = sum(COST[TYPE_NAMES.index(a["action"]["unitType"])] for a in d["actions"] if a["action"]["type"] == 4 and owner[a["ID"]] == p["ID"])
         p["resources"] = due + int(rng.integers(0, 15))
     return json.dumps(d, separators=(",", ":"))
+
+
+def state_probe(name, size, max_units, text, cap=1 << 18, utt_version=1, crs=1, utt_json=None):
+    """The product's own state converters without a handle or a GPU (mrts_hostdata.cpp, beside jsonToBlock; not in
+    include/mrts.h): name = "mrts_internal_state_probe" (text -> a zeroed state block -> text) or
+    "mrts_internal_dump_probe" (... -> the canonical dump's words), for a handle of this size as mrts_create sizes it
+    -> (return value, the int32 buffer written: cap words, the refusal's text)."""
+    from microrts_amd import _lib
+
+    f = getattr(_lib.load(), name)
+    I, C, P = ctypes.c_int, ctypes.c_char_p, ctypes.c_void_p
+    f.argtypes, f.restype = [I, I, I, I, I, I, C, C, P, I, C, I], I
+    H, W = size
+    mu = min(max_units, H * W) if max_units else H * W
+    out = np.zeros(cap, np.int32)
+    err = ctypes.create_string_buffer(256)
+    n = f(H, W, mu + max(64, mu // 4), mu, utt_version, crs, utt_json, text.encode(), out.ctypes.data_as(ctypes.c_void_p),
+          cap * (4 if name == "mrts_internal_state_probe" else 1), err, 256)
+    return n, out, err.value.decode()
 
 
 def budget(size):

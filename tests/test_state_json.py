@@ -111,15 +111,21 @@ def test_gpu_set_state_json_rejects_invalid():
 
     env = DeviceVecEnv(2, 0, 2000, [M4] * 2)
     bad = invalid_states()  # (shared with the CPU test of the same converter, tests/test_state_json_cpu.py)
-    assert [what for what, _, _ in bad] == ["size differs", "two units in a cell", "unknown ID", "unknown unit type", "no JSON"]
+    assert [what for what, _, _ in bad] == ["size differs", "two units in a cell", "unknown ID", "unknown unit type",
+                                            "move off the top edge", "move off the right edge", "move off the bottom edge",
+                                            "move off the left edge", "produce off the right edge", "produce off the bottom edge",
+                                            "no JSON"]
+    assert [code for _, _, code in bad] == [-22] * 4 + [-95] * 6 + [-22]
     for what, text, code in bad[:4]:
         with pytest.raises(RuntimeError, match=f"mrts error {code}:"):
             env.set_state_json(0, text)
     env.set_state_json(0, BASE4X4_JSON)
     assert json.loads(env.state_json(0))["pgs"]["units"][3]["type"] == "Worker"
-    for what, text, code in bad[4:]:
+    for what, text, code in bad[4:]:  # refused by the host before anything reaches the device; the state stays
         with pytest.raises(RuntimeError, match=f"mrts error {code}:"):
             env.set_state_json(0, text)
+    assert json.loads(env.state_json(0))["pgs"]["units"][3]["type"] == "Worker"
+    assert not env.error_flags().any()
     env.close()
 
 

@@ -2,7 +2,6 @@
 reached without a handle through the two internal probes (mrts_internal_state_probe / mrts_internal_dump_probe, beside
 them in that file; not in include/mrts.h): a state JSON goes into a zeroed state block and comes back as text, or as
 the dump's words.  The reference is the CPU oracle taking in the same text.  No GPU call is made."""
-import ctypes
 import json
 
 import numpy as np
@@ -10,7 +9,7 @@ import pytest
 
 from tests import oracle_py
 from tests import state_cases as SC
-from tests.state_json_invalid import BASE4X4_JSON, invalid_states
+from tests.state_json_invalid import BASE4X4_JSON, EINVAL, ENOTSUP, edge_states, invalid_states
 from tests import dumps
 from tests.dumps import xy_free
 
@@ -21,22 +20,12 @@ _id = lambda size: f"{size[1]}x{size[0]}"  # noqa: E731
 def lib():
     from microrts_amd import _lib
 
-    L = _lib.load()
-    I, C, P = ctypes.c_int, ctypes.c_char_p, ctypes.c_void_p
-    for f in (L.mrts_internal_state_probe, L.mrts_internal_dump_probe):
-        f.argtypes, f.restype = [I, I, I, I, I, I, C, C, P, I, C, I], I
-    return L
+    return _lib.load()
 
 
 def probe(f, size, max_units, text, cap, utt_version=1, crs=1, utt_json=None):
     """-> (return value, the bytes / words written, the refusal's text) for a handle of this size as mrts_create sizes it"""
-    H, W = size
-    mu = min(max_units, H * W) if max_units else H * W
-    out = np.zeros(cap, np.int32)
-    err = ctypes.create_string_buffer(256)
-    n = f(H, W, mu + max(64, mu // 4), mu, utt_version, crs, utt_json, text.encode(), out.ctypes.data_as(ctypes.c_void_p),
-          cap * (4 if f.__name__ == "mrts_internal_state_probe" else 1), err, 256)
-    return n, out, err.value.decode()
+    return SC.state_probe(f.__name__, size, max_units, text, cap, utt_version, crs, utt_json)
 
 
 @pytest.mark.parametrize("size", SC.SIZES, ids=_id)
@@ -71,6 +60,61 @@ def test_invalid_states_are_refused_with_the_gpu_paths_codes(lib):
         for f in (lib.mrts_internal_state_probe, lib.mrts_internal_dump_probe):
             n, _, err = probe(f, (4, 4), 0, text, 4096)
             assert n == code and err.startswith("state json:"), (what, n, err)
+
+
+def test_every_invalid_state_keeps_its_own_code():
+    """The list's codes case by case: what Java would throw on is EINVAL, an off-map MOVE / PRODUCE target (what
+    this build cannot hold) ENOTSUP with a text that names it."""
+    bad = invalid_states()
+    assert [(what, code) for what, _, code in bad if not what.startswith(("move off", "produce off"))] == \
+        [("size differs", EINVAL), ("two units in a cell", EINVAL), ("unknown ID", EINVAL), ("unknown unit type", EINVAL),
+         ("no JSON", EINVAL)]
+    off = [(what, text) for what, text, code in bad if code == ENOTSUP]
+    assert [what for what, _ in off] == ["move off the top edge", "move off the right edge", "move off the bottom edge",
+                                         "move off the left edge", "produce off the right edge", "produce off the bottom edge"]
+    assert len(off) + 5 == len(bad)
+
+
+def test_off_map_targets_are_refused_by_both_sides(lib):
+    """An in-flight MOVE or PRODUCE whose target cell is off the map: jsonToBlock and the oracle's set_state_json
+    refuse the same states with the same words, and the oracle's game stays what it was."""
+    ref = oracle_py.OracleVecClient(2, 0, 2000, ["maps/4x4/base4x4.xml"] * 2)
+    ref.reset()
+    before = ref.state_json(0)
+    for what, text, code in invalid_states():
+        if code != ENOTSUP:
+            continue
+        kind = what.split()[0]
+        n, _, err = probe(lib.mrts_internal_state_probe, (4, 4), 0, text, 4096)
+        assert n == ENOTSUP and err == f"state json: {kind} target off the map", (what, n, err)
+        with pytest.raises(RuntimeError, match=f"state json: {kind} target off the map"):
+            ref.set_state_json(0, text)
+        assert ref.state_json(0) == before, what
+    ref.close()
+
+
+def test_edge_actions_that_stay_legal_round_trip(lib):
+    """HARVEST / RETURN pointing off the map and MOVE / PRODUCE along the edge are kept by both sides: the product's
+    text and dump after the round trip are the oracle's, and the oracle then runs the action to its end without an
+    error (the off-map HARVEST / RETURN does nothing, like Java's)."""
+    ref = oracle_py.OracleVecClient(2, 0, 2000, ["maps/4x4/base4x4.xml"] * 2)
+    ref.reset()
+    cases = edge_states()
+    assert {json.loads(t)["actions"][0]["action"]["type"] for _, t in cases} == {1, 2, 3, 4}
+    for what, text in cases:
+        ref.set_state_json(0, text)
+        want_json, want_dump = ref.state_json(0), ref.dump(0)
+        assert len(json.loads(want_json)["actions"]) == 1, what
+        n, out, err = probe(lib.mrts_internal_state_probe, (4, 4), 0, text, 4096)
+        assert n > 0, (what, err)
+        assert out.tobytes()[:n].decode() == want_json, what
+        n, out, err = probe(lib.mrts_internal_dump_probe, (4, 4), 0, text, 4096)
+        assert n == len(want_dump) and np.array_equal(xy_free(out[:n]), xy_free(want_dump)), (what, err)
+        for _ in range(60):  # past the longest of them, the Worker's production (50 cycles)
+            ref.step(np.zeros((2, 16, 7), np.int32))
+        assert not json.loads(ref.state_json(0))["actions"] or what.startswith("produce"), what
+        assert ref.L.oref_errors(ref.h, 0) == 0, what
+    ref.close()
 
 
 def test_probe_refuses_what_a_handle_could_not_be(lib):
