@@ -106,7 +106,13 @@ enum { AB_LOAD = 0, AB_OBS = 1, AB_STORE = 2, AB_MASKBITS = 3, AB_RECORD = 4, AB
        // else the steady instance's sampledDec + unpack), nextStep, the priority / SIMD-rank block at the top of
        // the iteration, writeMasksLanes' set-up before maskTables, and cycleLanes' execute loop WITHOUT the
        // executes (not idempotent): the pick of each ready item and its lane reads
-       AB_DECFWD = 24, AB_NEXTSTEP = 25, AB_PRIO = 26, AB_MASKSETUP = 27, AB_EXECLOOP = 28, AB_COUNT = 29 };
+       AB_DECFWD = 24, AB_NEXTSTEP = 25, AB_PRIO = 26, AB_MASKSETUP = 27, AB_EXECLOOP = 28, AB_COUNT = 29,
+       // round 11, the steady instance: cycleLanes' lane-parallel MOVE pass and the step's
+       // reward / done stores, each once more
+       AB_MOVEBATCH = 30, AB_REWARD = 31,
+       // compact() once more in a step with a death, on the steady instance only: the 32-bit word is full, and the
+       // steady instance (full observability) never reads the PO rows' bits, so it takes the first of them
+       AB_COMPACT_STEADY = AB_PO_NOSTORE };
 #endif
 enum { GT_SELFPLAY = 0, GT_AGENT_VS_BOT = 1, GT_BOT_VS_BOT = 2, GT_PLAYOUT = 3 };  // game_kind & 15
 // per-player counters of this step's issued pairs, as the TraceEntry holds them (after issueSafe's
@@ -255,6 +261,9 @@ struct Game {
     // steady instance: the index is carried from step to step of a launch (carryIndex); a present PRODUCE left
     // since the sums were last right (cycleLanes, kill), so they are walked again at the next step's start
     bool prodDirty = false;
+    // steady instance: the own idle units the last writeMasksLanes of this launch found (-1 = none ran): the next
+    // step's issue priority counts them, and nothing between the two changes a unit or an assignment
+    int idleOwn = -1;
     // the PRODUCE costs of the issue index, the batch and the candidates summed by a walk over their
     // lanes instead of whole-wave reductions (the masked-policy 16x16 instances: few PRODUCE lanes;
     // c2's uniform rows make many, where the reductions are cheaper; round 5)
@@ -2356,6 +2365,15 @@ struct Game {
             default: break;
         }
     }
+    // cycleLanes' lane-parallel MOVEs, after the movers' old cells are cleared and synced: lane = unit slot, `np` the
+    // new cell (x, y are the low bytes of the core word: direction prm adds -256, 1, 256, -1 to them)
+    DEV void moveBatch(bool mv, uint32_t cu, int prm, int np, bool check) {
+        if (!mv) return;
+        if (check && MRTS_UNLIKELY(cell[np] != EMPTY)) atomicOr(&hdr[H_ERR], (int32_t)E_COLLISION);
+        cell[np] = (uint16_t)lid();
+        const uint32_t step = (uint32_t)(0xFFFF01000001FF00ull >> (((uint32_t)prm & 3u) * 16u));
+        uc[lid()] = (cu & ~0xFFFFu) | ((cu + step) & 0xFFFFu);
+    }
     // GameState.cycle (rts/GameState.java:553-571): time++, snapshot the ready assignments
     // (ETA + issue time <= time) in insertion order, then remove + execute each in that order.
     DEV void cycle() {
@@ -2466,8 +2484,20 @@ struct Game {
         }
 #endif
         if (ready) ua[l] = a & ~(UA_READY | UA_PRESENT);
-        const bool wk = ready && ua_type(a) != T_NONE;
-        const uint64_t work = ballot(wk);
+        const bool wk0 = ready && ua_type(a) != T_NONE;
+        const uint64_t work0 = ballot(wk0);
+        // steady: the cycle's ready MOVEs execute in one lane-parallel pass (moveBatch below) unless an ATTACK is
+        // ready too; each mover's lane clears its old cell here, ahead of the wsync the ready pass needs anyway
+        bool mv = false;
+        uint64_t movers = 0;
+        if (steady) {
+            const bool attack = ballot(wk0 && ua_type(a) == T_ATTACK) != 0;
+            mv = wk0 && ua_type(a) == T_MOVE && !attack;
+            movers = ballot(mv);
+            if (mv) cell[uy(cu) * W + ux(cu)] = EMPTY;
+        }
+        const bool wk = wk0 && !mv;
+        const uint64_t work = work0 & ~movers;
         // steady, the carried issue index (carryIndex): a MOVE / PRODUCE that leaves the map gives its position back
         // (buildIndex's position; the unit stands where the assignment found it until its own execute).  A present
         // MOVE / PRODUCE holds a direction 0..3 (issueSafe's legality test turned any other into NONE), so the
@@ -2480,6 +2510,32 @@ struct Game {
             if (ballot(wk && ua_type(a) == T_PRODUCE)) prodDirty = true;
         }
         wsync();
+        if (!work0) return;
+        if (steady && movers) {
+            // The ready MOVEs of a cycle without a ready ATTACK, all at once (UnitAction.execute's TYPE_MOVE,
+            // rts/UnitAction.java:338-465, for each): the serial loop's order between them and the cycle's other
+            // assignments changes nothing, because
+            // * no mover is dead or dies here: only ATTACK and HARVEST kill (kill), no ATTACK is ready, and a HARVEST
+            //   kills a resource unit, which holds no assignment;
+            // * no two present MOVE / PRODUCE assignments share a target (the issue pass refuses the second;
+            //   carryIndex's `bits` rests on the same fact), and a target was free when its assignment was issued and
+            //   reserved since, while a mover stands on its old cell from before its MOVE was issued until now: no
+            //   other MOVE or PRODUCE reads or writes a mover's old or new cell;
+            // * HARVEST and RETURN act on the occupant of their target cell only if it is a resource / a stockpile,
+            //   which no mover is: they find a mover or an empty cell there, before its move or after, and do nothing
+            //   either way (the target's own resource or base gone earlier);
+            // * the other executes touch res / hp / the players' resources / a new unit's slot, never a mover's words.
+            // Old cells were cleared before the wsync above; E_COLLISION as the serial MOVE reports it.
+            moveBatch(mv, cu, prm, ipos - W, true);
+#ifdef MRTS_ABLATE
+            if (ab(AB_MOVEBATCH)) {  // once more (the same cells and words written again; no second collision test)
+                wsync();
+                if (mv) cell[launder(uy(cu) * W + ux(cu))] = EMPTY;
+                moveBatch(mv, launder(cu), launder(prm), launder(ipos - W), false);
+            }
+#endif
+            wsync();
+        }
         if (!work) return;
         int rank = 0;
         for (uint64_t m = work; m; m &= m - 1) rank += rl(sq, __builtin_ctzll(m)) < sq;
@@ -4346,6 +4402,7 @@ struct Game {
             }
         }
         const int c = uy(cu) * W + ux(cu);
+        if (steady) idleOwn = __popcll(ballot(si >= 0));  // (maskBitsQuads' own ballot, read once more)
         // steady: the row bitmaps only when an idle unit attacks at range > 1 (farAttackRowsDir, their one reader
         // there, returns at once otherwise)
         const bool rowF = rowB && (!steady || ballot(si >= 0 && ((uniu(U.mtAttackFar) >> utyp(cu)) & 1u)) != 0);
@@ -5565,6 +5622,7 @@ __global__ __launch_bounds__(HELP ? 128 : 64, (HELP || FIX == 16) ? 4 : 1) void 
     SimdRank srank;
     if (ranked) srank = simdRankInit(D.prio_tab, D.fwd_stamp);
     int oc = -1;  // steady: the carried outcome (MODE_STEP below)
+    int rwKey = -1;  // steady: what the reward / done values last stored in this launch were made from (-1: none yet)
     if (HELP && !FPO) __syncthreads();  // A_0: the helper drew step 0's rows
     for (int it = 0; it < niter; it++) {
     if (it > 0) {
@@ -5597,7 +5655,12 @@ __global__ __launch_bounds__(HELP ? 128 : 64, (HELP || FIX == 16) ? 4 : 1) void 
             // the c3 shape (four games per SIMD): units + own idle units (the step's decode / issue /
             // mask / policy work grows with the idle ones; against units alone at 24 / 30 / 36: c3 +1.8 % at
             // K = 200, +0.8 % at K = 20)
-            const int wq = G.nu + (int)__popcll(ballot(G.lid() < G.nu && !(G.lua & UA_PRESENT) && uplay(G.lcu) >= 0));
+            // (steady: the count the previous step's writeMasksLanes took, Game::idleOwn — a launch's first step
+            // and a step after one that wrote its masks the general way count here)
+            int idle = steady ? G.idleOwn : -1;
+            if (idle < 0) idle = (int)__popcll(ballot(G.lid() < G.nu && !(G.lua & UA_PRESENT) && uplay(G.lcu) >= 0));
+            if (steady) G.idleOwn = -1;
+            const int wq = G.nu + idle;
             q = wq >= PRIO_T3 ? 3 : wq >= PRIO_T2 ? 2 : wq >= PRIO_T1 ? 1 : 0;
             if (ranked) {  // from the second step on: the rank among the SIMD's waves by remaining work
 #ifdef MRTS_ABLATE
@@ -5800,10 +5863,33 @@ __global__ __launch_bounds__(HELP ? 128 : 64, (HELP || FIX == 16) ? 4 : 1) void 
         // reward/done and forcing done[0] (tests/JNIGridnetVecClient.java:214-287)
         const int steps = G.hget(H_STEPS) + 1;
         G.hset(H_STEPS, steps);
-        const bool done0 = G.writeRewards(slot0, nslots, selfplay ? 0 : side, selfplay ? 1 : side, gameover, winner, it);
-        const bool reset = done0 || steps >= D.max_steps;
-        if (reset && D_HAS(done) && lane_id() < nslots)
-            D.done[(size_t)((uint32_t)it * (uint32_t)D_ZERO(resp_stride)) + (size_t)(slot0 + lane_id()) * (steady ? 1 : D.n_rewards)] = 1;
+        bool reset;
+        if (steady) {
+            // WinLoss alone into the plain per-handle buffers (writeRewards' first branch and the forced done[0]
+            // below, in one store each): the values are a function of (gameover, winner, reset), and the buffers
+            // persist from step to step, so they are stored on the launch's first step (whatever the caller left
+            // there) and whenever that triple differs from the last one stored — a game over, an auto-reset, or the
+            // step after either.  After every step the buffers hold what a full write would.
+            reset = gameover || steps >= D.max_steps;
+            const int key = (gameover ? oc : 0) | (reset ? 8 : 0);
+            if (key != rwKey && lane_id() < 2) {
+                D.reward[slot0 + lane_id()] = gameover ? (winner == lane_id() ? 1.0 : -1.0) : 0.0;
+                D.done[slot0 + lane_id()] = reset ? 1 : 0;
+            }
+            rwKey = key;
+#ifdef MRTS_ABLATE
+            if (G.ab(AB_REWARD) && lane_id() < 2) {  // the full write once more
+                D.reward[slot0 + lane_id()] = gameover ? (winner == lane_id() ? 1.0 : -1.0) : 0.0;
+                D.done[slot0 + lane_id()] = reset ? 1 : 0;
+            }
+#endif
+        } else {
+            // (every other instance; writeRewards' own `steady` arms now serve the AB_OUTCOME ablation copy alone)
+            const bool done0 = G.writeRewards(slot0, nslots, selfplay ? 0 : side, selfplay ? 1 : side, gameover, winner, it);
+            reset = done0 || steps >= D.max_steps;
+            if (reset && D.done != nullptr && lane_id() < nslots)
+                D.done[(size_t)((uint32_t)it * (uint32_t)D.resp_stride) + (size_t)(slot0 + lane_id()) * D.n_rewards] = 1;
+        }
         if (MRTS_UNLIKELY(reset)) {
             G.hset(H_STEPS, 0);  // envSteps[i] = 0 (JNIGridnetVecClient.java:229,264-265,285)
             G.resetFromTemplate();
@@ -5883,6 +5969,9 @@ __global__ __launch_bounds__(HELP ? 128 : 64, (HELP || FIX == 16) ? 4 : 1) void 
     if (MODE == MODE_STEP && !freshObs && G.deaths) {
         if (MRTS_UNLIKELY(lr)) G.lrCompact();
         G.compact();
+#ifdef MRTS_ABLATE
+        if (steady && G.ab(AB_COMPACT_STEADY)) G.compact();  // once more: no dead slot is left, every unit keeps its place
+#endif
     }
     PHASE(7);
     if (HELP && FPO) {  // a packed step's mask records go to the helper (storeRecordsHelp)

@@ -28,7 +28,12 @@ NAMES = ["load", "obs", "store", "maskbits", "record", "policy", "accept", "lega
          "SKIP PO render record", "(snapshot)",
          # round 9, the step's glue: the forwarded row's decode (first step: decodeFwd; steady: sampledDec + unpack),
          # nextStep, the priority / SIMD-rank block, writeMasksLanes' set-up, cycleLanes' execute loop without the executes
-         "decodefwd", "nextstep", "prio+rank", "masksetup", "execloop (picks only)"]
+         "decodefwd", "nextstep", "prio+rank", "masksetup", "execloop (picks only)", "(render-item counters)",
+         # round 11, the steady instance: cycleLanes' lane-parallel MOVE pass, the step's reward / done stores
+         "movebatch", "rewardstores"]
+# bits that mean something else on the steady 16x16 instance (full observability: it never reads the PO rows' bits):
+# bit 18 there is compact() once more in a step with a death (AB_COMPACT_STEADY)
+STEADY_NAMES = {18: "compact (steps with a death)"}
 SEED = 0x5EEDC0DE
 
 

@@ -25,7 +25,7 @@ from microrts_amd import _lib  # noqa: E402
 L = _lib.load(os.path.join(ROOT, "microrts_amd", "libmrts_ablate.so"))
 L.mrts_set_ablate.argtypes = [ctypes.c_uint]
 from microrts_amd import DeviceVecEnv  # noqa: E402
-from tools.ablate_price import NAMES, SEED  # noqa: E402
+from tools.ablate_price import NAMES, SEED, STEADY_NAMES  # noqa: E402
 
 
 def main():
@@ -54,7 +54,9 @@ def main():
         env.actions.copy_(acts)
         roll(burn + 1, K)
         torch.cuda.synchronize()
-        order.append("baseline" if b is None else NAMES[b])
+        # (the fused full-observability 16x16 workload's multi-step launch is the steady instance)
+        steady = not PO and not UNI and "16x16" in MAP
+        order.append("baseline" if b is None else STEADY_NAMES[b] if steady and b in STEADY_NAMES else NAMES[b])
     L.mrts_set_ablate(0)
     json.dump({"order": order, "K": K, "games": E, "steps_per_multi_launch": K - 1 if not UNI else K}, open(sys.argv[1], "w"))
     env.close()
