@@ -261,7 +261,7 @@ struct Game {
     // steady instance: the index is carried from step to step of a launch (carryIndex); a present PRODUCE left
     // since the sums were last right (cycleLanes, kill), so they are walked again at the next step's start
     bool prodDirty = false;
-    // steady instance: the own idle units the last writeMasksLanes of this launch found (-1 = none ran): the next
+    // steady instance: the own idle units the last writeMasksSteady of this launch found (-1 = none ran): the next
     // step's issue priority counts them, and nothing between the two changes a unit or an assignment
     int idleOwn = -1;
     // the PRODUCE costs of the issue index, the batch and the candidates summed by a walk over their
@@ -667,7 +667,7 @@ struct Game {
             keepv(t2 + pr2 + ut2 + tx2 + ty2 + (int)bad2);
         }
 #endif
-        // steady, from the launch's second step on: writeMasksLanes left this row decoded in lfwd (sampledDec)
+        // steady, from the launch's second step on: writeMasksSteady left this row decoded in lfwd (sampledDec)
         const bool dec = steady && fwdOn && !firstIt;
         if (dec) {
             if (idle) {
@@ -4390,7 +4390,7 @@ struct Game {
         const bool rowP = !rowS && po && W <= 32 && W >= 16 && 2 * H <= 64;
         uint32_t* rows = rowS ? (uint32_t*)rslot : rowP ? scell + (HW - 2 * H) : nullptr;
         const bool rowB = rowS || rowP;
-        if (!steady && rowB && l < 2 * H) rows[l] = 0;
+        if (rowB && l < 2 * H) rows[l] = 0;
         int si = -1;  // slot index of this lane's unit record, -1 = none
         uint32_t cu = 0;
         if (l < nu) {
@@ -4402,19 +4402,14 @@ struct Game {
             }
         }
         const int c = uy(cu) * W + ux(cu);
-        if (steady) idleOwn = __popcll(ballot(si >= 0));  // (maskBitsQuads' own ballot, read once more)
-        // steady: the row bitmaps only when an idle unit attacks at range > 1 (farAttackRowsDir, their one reader
-        // there, returns at once otherwise)
-        const bool rowF = rowB && (!steady || ballot(si >= 0 && ((uniu(U.mtAttackFar) >> utyp(cu)) & 1u)) != 0);
-        if (steady && rowF && l < 2 * H) rows[l] = 0;
         wsync();
         if (si >= 0) atomicOr(&nb[si * MW + (c >> 5)], 1u << (c & 31));
-        if (rowF && l < nu && !(cu & UC_DEAD) && uplay(cu) >= 0) atomicOr(&rows[uplay(cu) * H + uy(cu)], 1u << ux(cu));
+        if (rowB && l < nu && !(cu & UC_DEAD) && uplay(cu) >= 0) atomicOr(&rows[uplay(cu) * H + uy(cu)], 1u << ux(cu));
 #ifdef MRTS_ABLATE
         if (ab(AB_MASKSETUP)) {  // the set-up once more: the same bitmaps cleared and filled again
             wsync();
             if (l < NW) nb[l] = 0;
-            if (rowF && l < 2 * H) rows[l] = 0;
+            if (rowB && l < 2 * H) rows[l] = 0;
             int si2 = -1;
             uint32_t cu2 = 0;
             if (l < nu) {
@@ -4428,7 +4423,7 @@ struct Game {
             const int c2 = uy(cu2) * W + ux(cu2);
             wsync();
             if (si2 >= 0) atomicOr(&nb[si2 * MW + (c2 >> 5)], 1u << (c2 & 31));
-            if (rowF && l < nu && !(cu2 & UC_DEAD) && uplay(cu2) >= 0) atomicOr(&rows[uplay(cu2) * H + uy(cu2)], 1u << ux(cu2));
+            if (rowB && l < nu && !(cu2 & UC_DEAD) && uplay(cu2) >= 0) atomicOr(&rows[uplay(cu2) * H + uy(cu2)], 1u << ux(cu2));
         }
 #endif
         uint32_t w0 = 0, w1 = 0, w2 = 0;
@@ -4544,9 +4539,8 @@ struct Game {
                 }
 #endif
                 uint32_t pk;
-                int picks[3];  // steady: the sampler's type, parameter and produce-type picks
                 sampleBitsRaw(D.pol_seed, polStep, D.pol_slot_base + (uint32_t)slot, NT, K, (lo >> 1) | ((uint64_t)w2 << 63),
-                              (uint64_t)(w2 >> 1), c, a, &pk, steady ? picks : nullptr);
+                              (uint64_t)(w2 >> 1), c, a, &pk);
                 if (recOut) {
                     recOut[256 + l] = pk;
                 } else {
@@ -4556,13 +4550,9 @@ struct Game {
                 }
                 if (fwdW) {
                     // packFwd(a): the next launch decodes from it, and so does the next iteration of a multi-step
-                    // launch — but the steady instance's, which takes the row decoded here (no cycle lies between
-                    // the sample and the decode: the unit stands where it stood)
+                    // launch (the steady instance's takes the row decoded: writeMasksSteady)
                     if (lastIt) st1<WT_STATE>(st() + stateFwdOff(CAP, HW) + l, (int32_t)pk);  // the next launch's
-                    lfwd = steady ? sampledDec(cu, picks[0], picks[1], picks[2]) : pk;
-#ifdef MRTS_ABLATE
-                    if (steady && ab(AB_DECFWD)) keepv(sampledDec(launder(cu), launder(picks[0]), launder(picks[1]), launder(picks[2])));
-#endif
+                    lfwd = pk;
                 }
             }
         }
@@ -4610,6 +4600,200 @@ struct Game {
             }
         }
         wsync();
+    }
+    static DEV int rowInclSum(int v) {  // wave_incl_sum inside each 16-lane row (its first four steps; whole wave)
+        LANE_AUDIT_WAVE(2);
+        v += __builtin_amdgcn_update_dpp(0, v, 0x111, 0xF, 0xF, false);  // row_shr:1
+        v += __builtin_amdgcn_update_dpp(0, v, 0x112, 0xF, 0xF, false);  // row_shr:2
+        v += __builtin_amdgcn_update_dpp(0, v, 0x114, 0xF, 0xF, false);  // row_shr:4
+        v += __builtin_amdgcn_update_dpp(0, v, 0x118, 0xF, 0xF, false);  // row_shr:8
+        return v;
+    }
+    // writeMasksLanes of the steady instance (self-play on 16x16, K = 79, delta masks and delta policy
+    // rows, nu <= 64): the same buffer contents from one list of quads.  An entry of the list (qb: 16 of 3 words a
+    // pass, rseq words 16..63) is an own idle unit — its core word, its resources | its lane << 16 — or, after the
+    // units, a cell whose idle unit is gone, as the core word of a unit of that player on that cell.  Lane 4 q + d
+    // computes direction d of entry q (maskBitsDir, farAttackRowsDir) and quadOr leaves the row on the quad's four
+    // lanes — zero for a vacated cell, whose lanes compute nothing.  From its registers lane d then stores 16 bytes
+    // of the record, lane 3 the last 12 as well and lanes 0..2 one head / tail byte each (storeRecordsLanes' bytes);
+    // lane 0 samples the row, stores it (a zero row for a vacated cell), on the launch's last step the forwarded word
+    // at the unit's lane index, and posts the decoded word in the entry's third word, where the unit's own lane
+    // takes it (lfwd) after the pass.  More than 16 entries take further passes.  Whole wave.
+    DEV void writeMasksSteady(int slot0) {
+        constexpr int MW = 8, NW = 16;  // maskWords(16 * 16), both slots
+        const int l = lid();
+        const int total = HW * K;
+        uint32_t* nb = (uint32_t*)rseq;          // [slot][MW] new row sets
+        uint32_t* qb = (uint32_t*)rseq + 16;      // the list
+        uint32_t* rows = (uint32_t*)rslot;        // per-player unit row bitmaps (farAttackRowsDir)
+        if (l < NW) nb[l] = 0;
+        int si = -1;
+        uint32_t cu = 0;
+        if (l < nu) {
+            cu = uc[l];
+            if (!(cu & UC_DEAD) && !(ua[l] & UA_PRESENT)) si = uplay(cu);  // (slot i is player i's; -1: a resource)
+        }
+        const int c = uy(cu) * W + ux(cu);
+        const uint64_t im = ballot(si >= 0);
+        const int RI = __popcll(im), r = lanes_below(im);
+        idleOwn = RI;
+        // the row bitmaps only when an idle unit attacks at range > 1 (farAttackRowsDir returns at once otherwise)
+        const bool rowF = ballot(si >= 0 && ((uniu(U.mtAttackFar) >> utyp(cu)) & 1u)) != 0;
+        if (rowF && l < 2 * H) rows[l] = 0;
+        wsync();
+        if (si >= 0) atomicOr(&nb[si * MW + (c >> 5)], 1u << (c & 31));
+        if (rowF && l < nu && !(cu & UC_DEAD) && uplay(cu) >= 0) atomicOr(&rows[uplay(cu) * H + uy(cu)], 1u << ux(cu));
+#ifdef MRTS_ABLATE
+        if (ab(AB_MASKSETUP)) {  // the set-up once more: the same bitmaps cleared and filled again
+            wsync();
+            if (l < NW) nb[l] = 0;
+            if (rowF && l < 2 * H) rows[l] = 0;
+            int si2 = -1;
+            uint32_t cu2 = 0;
+            if (l < nu) {
+                cu2 = launder(uc[l]);
+                if (!(cu2 & UC_DEAD) && !(launder(ua[l]) & UA_PRESENT)) si2 = uplay(cu2);
+            }
+            const int c2 = uy(cu2) * W + ux(cu2);
+            wsync();
+            if (si2 >= 0) atomicOr(&nb[si2 * MW + (c2 >> 5)], 1u << (c2 & 31));
+            if (rowF && l < nu && !(cu2 & UC_DEAD) && uplay(cu2) >= 0) atomicOr(&rows[uplay(cu2) * H + uy(cu2)], 1u << ux(cu2));
+        }
+#endif
+        MPHASE(16);
+        const MaskTables T = maskTables();
+#ifdef MRTS_ABLATE
+        if (ab(AB_TABLES)) {
+            const MaskTables T2 = maskTables();
+            keepv(T2.attack1 ^ T2.attackFar ^ T2.harvest ^ T2.move ^ T2.resource ^ T2.stockpile ^ T2.aff0 ^ T2.aff1 ^
+                  (uint32_t)T2.prod);
+        }
+#endif
+        MPHASE(17);
+        const uint32_t own = ((uint32_t)(l < nu ? res[l] : 0) & 0xFFFFu) | (uint32_t)l << 16;
+        wsync();
+        // the row sets: the source bits, the next step's / launch's base, the cells whose idle unit is gone
+        uint32_t gone = 0;
+        if (l < NW) {
+            const uint32_t cur = nb[l], old = mprev[l];  // (player i's words are slot i's)
+            D.source[(size_t)slot0 * MW + l] = cur;
+            if (lastIt) prevG()[l] = cur;
+            mprev[l] = cur;
+            gone = old & ~cur;
+        }
+        const int n = __popc(gone);
+        const int incl = rowInclSum(n);  // (lanes 0..15 hold the words)
+        const int NR = RI + rl(incl, 15);
+#ifdef MRTS_ABLATE
+        if (ab(AB_GONE)) keepv(rl(rowInclSum(launder(n)), 15));  // the scan alone: the zero records ride the unit pass
+#endif
+        MPHASE(12);
+        const uint32_t mbLo = (uint32_t)(uintptr_t)(D.masks + (size_t)slot0 * total);
+        const __amdgpu_buffer_rsrc_t mrs = bufRsrc((void*)(D.masks + (size_t)slot0 * total), (uint32_t)(2 * total));
+        const int q = l >> 2, d = l & 3;
+        // the quad's lanes store the record (w0:w1:w2) of the entry with core word ecu
+        auto storeQuad = [&](uint32_t ecu, uint32_t w0, uint32_t w1, uint32_t w2) {
+            const uint32_t s = (uint32_t)uplay(ecu) * (uint32_t)total + (uint32_t)(uy(ecu) * W + ux(ecu)) * 79u;
+            const uint32_t h = (0u - (mbLo + s)) & 3u;  // head bytes before the first aligned dword
+            // bits h + 16 d .. + 15 of the record: the low half of the funnel shift of two of its words
+            const uint32_t x = __builtin_amdgcn_alignbit(d < 2 ? w1 : w2, d < 2 ? w0 : w1, h + 16u * (uint32_t)(d & 1));
+            const i32x4v v = {(int)expand4(x), (int)expand4(x >> 4), (int)expand4(x >> 8), (int)expand4(x >> 12)};
+            __builtin_amdgcn_raw_buffer_store_b128(v, mrs, (int)(s + h) + 16 * d, 0, SC1_MASK ? 16 : 0);
+            if (d == 3) {  // bits h + 64 .. h + 75
+                typedef int32_t i32x3v __attribute__((ext_vector_type(3)));
+                const uint32_t y = w2 >> h;
+                const i32x3v t = {(int)expand4(y), (int)expand4(y >> 4), (int)expand4(y >> 8)};
+                __builtin_amdgcn_raw_buffer_store_b96(t, mrs, (int)(s + h) + 64, 0, SC1_MASK ? 16 : 0);
+            } else {  // byte d of the 3 outside the 19 dwords: head byte d, else tail byte 76 + d
+                const bool head = (uint32_t)d < h;
+                const uint32_t b = head ? (uint32_t)d : 76u + (uint32_t)d;
+                const uint32_t bit = ((head ? w0 : (w2 >> 12)) >> d) & 1u;
+                __builtin_amdgcn_raw_buffer_store_b8((char)bit, mrs, (int)(s + b), 0, SC1_MASK ? 16 : 0);
+            }
+        };
+        for (int p0 = 0; p0 < NR; p0 += 16) {
+            const bool mine = si >= 0 && (uint32_t)(r - p0) < 16u;
+            if (mine) {
+                qb[3 * (r - p0)] = cu;
+                qb[3 * (r - p0) + 1] = own;
+            }
+            int k = RI - p0 + incl - n;
+            for (uint32_t m = gone; m; m &= m - 1, k++) {
+                const uint32_t cz = 32u * (uint32_t)(l & 7) + (uint32_t)__builtin_ctz(m);
+                if ((uint32_t)k < 16u) qb[3 * k] = (cz & 15u) | (cz >> 4) << 8 | (uint32_t)((l >> 3) + 1) << 20;
+            }
+            wsync();
+            const bool qa = p0 + q < RI, qr = p0 + q < NR;
+            uint32_t qcu = 0, qown = 0, v0 = 0, v1 = 0, v2 = 0;
+            if (qr) qcu = qb[3 * q];
+            if (qa) {
+                qown = qb[3 * q + 1];
+                maskBitsDir(T, qcu, (int)(int16_t)qown, d, v0, v1, v2);
+            }
+            const bool far = qa && ((T.attackFar >> utyp(qcu)) & 1u);
+            farAttackRowsDir(far, qcu, d, rows, v0, v1, v2);
+            v0 = quadOr(v0);
+            v1 = quadOr(v1);
+            v2 = quadOr(v2);
+            // produce-type bits 23 + ut, when a direction of the quad found a free cell (produce direction bits)
+            const uint32_t canProd =
+                (uint32_t)(T.prod >> (8 * utyp(qcu))) & 0xFFu & (uplay(qcu) == 0 ? T.aff0 : T.aff1);
+            if (((v0 >> (1 + 6 + 12)) & 0xFu) != 0u) v0 |= canProd << (1 + 6 + 16);
+#ifdef MRTS_ABLATE
+            if (ab(AB_MASKBITS)) {  // the quad's bits once more
+                uint32_t u0 = 0, u1 = 0, u2 = 0;
+                const uint32_t qcu2 = launder(qcu);
+                if (qa) maskBitsDir(T, qcu2, (int)(int16_t)launder(qown), d, u0, u1, u2);
+                farAttackRowsDir(far, qcu2, d, rows, u0, u1, u2);
+                keepv(quadOr(u0) ^ quadOr(u1) ^ quadOr(u2));
+            }
+#endif
+            MPHASE(19);
+            if (qr && d == 0) {
+                const int qc = uy(qcu) * W + ux(qcu), slot = slot0 + uplay(qcu);
+                int32_t a[7] = {0, 0, 0, 0, 0, 0, 0};
+                if (qa) {
+                    const uint64_t lo = (uint64_t)v0 | ((uint64_t)v1 << 32);
+#ifdef MRTS_ABLATE
+                    if (ab(AB_POLICY)) {
+                        int32_t a2[7];
+                        sampleBitsRaw(D.pol_seed, polStep, D.pol_slot_base + (uint32_t)launder(slot), NT, K,
+                                      launder((lo >> 1) | ((uint64_t)v2 << 63)), launder((uint64_t)(v2 >> 1)), launder(qc), a2);
+                        keepv(a2[0] + a2[1] + a2[2] + a2[3] + a2[4] + a2[5] + a2[6]);
+                    }
+#endif
+                    uint32_t pk;
+                    int picks[3];  // the sampler's type, parameter and produce-type picks
+                    sampleBitsRaw(D.pol_seed, polStep, D.pol_slot_base + (uint32_t)slot, NT, K, (lo >> 1) | ((uint64_t)v2 << 63),
+                                  (uint64_t)(v2 >> 1), qc, a, &pk, picks);
+                    // packFwd(a) for the next launch's decode; the next step of this launch takes the row decoded
+                    // here (no cycle lies between the sample and the decode: the unit stands where it stood)
+                    if (lastIt) st1<WT_STATE>(st() + stateFwdOff(CAP, HW) + (int)(qown >> 16), (int32_t)pk);
+                    qb[3 * q + 2] = sampledDec(qcu, picks[0], picks[1], picks[2]);
+#ifdef MRTS_ABLATE
+                    if (ab(AB_DECFWD)) keepv(sampledDec(launder(qcu), launder(picks[0]), launder(picks[1]), launder(picks[2])));
+#endif
+                }
+                int32_t* dst = D.pol_actions + ((size_t)slot * HW + qc) * 7;
+                st4u<WT_MASK>(dst, a[0], a[1], a[2], a[3]);
+                st3u<WT_MASK>(dst + 4, a[4], a[5], a[6]);
+            }
+            MPHASE(13);
+            if (qr) {
+#ifdef MRTS_ABLATE
+                if (!ab(AB_SKIP_RECORD))
+#endif
+                storeQuad(qcu, v0, v1, v2);
+#ifdef MRTS_ABLATE
+                if (ab(AB_RECORD)) storeQuad(launder(qcu), launder(v0), launder(v1), launder(v2));
+#endif
+            }
+            wsync();
+            if (mine) lfwd = qb[3 * (r - p0) + 2];
+            wsync();  // read before the next pass lists its entries
+        }
+        fwdWritten = true;
+        MPHASE(14);
     }
     // the fused random policy's action row of cell c of slot (slot0 + i): masked-uniform sample from
     // the parked mask bits (bit k = mask slot k) of an own idle unit, else a zero row
@@ -5655,7 +5839,7 @@ __global__ __launch_bounds__(HELP ? 128 : 64, (HELP || FIX == 16) ? 4 : 1) void 
             // the c3 shape (four games per SIMD): units + own idle units (the step's decode / issue /
             // mask / policy work grows with the idle ones; against units alone at 24 / 30 / 36: c3 +1.8 % at
             // K = 200, +0.8 % at K = 20)
-            // (steady: the count the previous step's writeMasksLanes took, Game::idleOwn — a launch's first step
+            // (steady: the count the previous step's writeMasksSteady took, Game::idleOwn — a launch's first step
             // and a step after one that wrote its masks the general way count here)
             int idle = steady ? G.idleOwn : -1;
             if (idle < 0) idle = (int)__popcll(ballot(G.lid() < G.nu && !(G.lua & UA_PRESENT) && uplay(G.lcu) >= 0));
@@ -5982,7 +6166,8 @@ __global__ __launch_bounds__(HELP ? 128 : 64, (HELP || FIX == 16) ? 4 : 1) void 
         const int nsl = selfplay ? 2 : 1;
         if (MRTS_LIKELY(D_ON(mask_delta) && G.nu <= 64 && nsl * maskWords(G.HW) <= 64 && G.K <= 96)) {
             PHASE(8);
-            if (selfplay) G.writeMasksLanes(slot0, 2, 0, 1);
+            if constexpr (steady) G.writeMasksSteady(slot0);
+            else if (selfplay) G.writeMasksLanes(slot0, 2, 0, 1);
             else G.writeMasksLanes(slot0, 1, D.mask_player, D.mask_player);
         } else {
         wsync();

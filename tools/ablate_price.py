@@ -32,8 +32,14 @@ NAMES = ["load", "obs", "store", "maskbits", "record", "policy", "accept", "lega
          # round 11, the steady instance: cycleLanes' lane-parallel MOVE pass, the step's reward / done stores
          "movebatch", "rewardstores"]
 # bits that mean something else on the steady 16x16 instance (full observability: it never reads the PO rows' bits):
-# bit 18 there is compact() once more in a step with a death (AB_COMPACT_STEADY)
-STEADY_NAMES = {18: "compact (steps with a death)"}
+# bit 18 there is compact() once more in a step with a death (AB_COMPACT_STEADY).  The steady instance's mask pass
+# (writeMasksSteady) is one list of quads for own idle units and vacated cells, so three rows price
+# something else there: `record` / `SKIP records` are the quad stores of every entry, vacated cells' zero records
+# included; `gone` is the scan that counts the vacated cells alone — their listing, records and zero rows ride the unit
+# pass and cannot be doubled apart from it; `maskbits` doubles the quads' bits (four lanes per entry) without the
+# hand-off into the quads
+STEADY_NAMES = {18: "compact (steps with a death)", 3: "maskbits (quads, no hand-off)", 4: "record (units + vacated cells)",
+                10: "gone (the count alone)", 17: "SKIP records (units + vacated cells)"}
 SEED = 0x5EEDC0DE
 
 

@@ -60,7 +60,7 @@ WHY = {
              "for lanes k < R and read only from lanes of work ⊂ {k < R}",
     "cycleLanes": "sq / cu / a / prm written for lanes l < nu under `if (l < nu)`; read only from lanes of "
                   "work = ballot(wk) ⊂ {l < nu}, in a uniform loop",
-    "quadOr": "helper: DPP quad_perm OR within each quad — called by maskBitsQuads in uniform flow (outside its lane "
+    "quadOr": "helper: DPP quad_perm OR within each quad — called by maskBitsQuads / writeMasksSteady in uniform flow (outside their lane "
               "tests) with v defined on every lane (0 for lanes without a unit)",
     "maskBitsQuads": "quadOr of v0..v2, each set on every lane (0 unless the lane's quad has a unit) before the calls, in "
                      "the uniform pass loop",
@@ -69,6 +69,12 @@ WHY = {
                      "caller's unit word of every lane < nu (owned ⊂ {l < nu})",
     "writeMasksUnits": "wave_incl_sum / lane-63 read of a count defined on every lane (0 beyond the row-set words)",
     "writeMasksLanes": "as writeMasksUnits: n = popc(gone) on every lane, uniform flow",
+    "rowInclSum": "helper: wave_incl_sum's four row_shr steps (a prefix sum inside each 16-lane row) — called by "
+                  "writeMasksSteady in uniform flow with the operand defined on every lane",
+    "writeMasksSteady": "steady instance: n = popc(gone) is set on every lane (0 beyond the 16 row-set words) before "
+                        "rowInclSum, and lane 15, read for the total, is a lane of the wave; quadOr of v0..v2, each "
+                        "set on every lane (0 unless the lane's quad has a unit) in the uniform pass loop; the "
+                        "ablation copies sit under wave-uniform tests of the ablation word",
     "balancePerm": "the last wave of an XCD class sorts in uniform flow (`if (ballot(!ok)) return` is uniform); "
                    "sum is each lane's 4-bin total",
     "k_policy_delta": "kernel level, before any divergence: every lane's popc(dirty)",
