@@ -49,9 +49,9 @@ def mixed_maps(tmp_path, n_slots):
     return [ar[s] if (s // 2) % 2 == 0 else MELEE16 for s in range(n_slots)]
 
 
-def in_range(dx, dy):
-    """Ranged's attack range 3 in the rule of Unit.getUnitActions (Unit.java:424-431)."""
-    return dx * dx + dy * dy <= 9
+def in_range(dx, dy, r=3):
+    """Attack range r (Ranged's 3 in the built-in tables) in the rule of Unit.getUnitActions (Unit.java:424-431)."""
+    return dx * dx + dy * dy <= r * r
 
 
 def window_enemy(dx, dy, flip):
@@ -59,14 +59,15 @@ def window_enemy(dx, dy, flip):
     return bool(((dx + 4) * 3 + (dy + 4) * 5 + ((dx + 4) * (dy + 4)) // 3) & 1) != bool(flip)
 
 
-def ranged_window(path, W, H, cx, cy, flip):
-    """A Ranged unit of player 0 at (cx, cy); every other in-map cell of the 9x9 block around it holds
-    an enemy Worker, an own Light or a Resource unit.  `flip` exchanges the enemy cells and the
-    non-enemy cells, so over the two layouts each of the 28 offsets in range is set once and clear once.
+def ranged_window(path, W, H, cx, cy, flip, r=3):
+    """A Ranged unit of player 0 (attack range r) at (cx, cy); every other in-map cell of the block of
+    2r + 3 cells a side around it (9x9 for r = 3) holds an enemy Worker, an own Light or a Resource unit.
+    `flip` exchanges the enemy cells and the non-enemy cells, so over the two layouts each of the offsets
+    in range (28 for r = 3, 12 for r = 2) is set once and clear once.
     -> (path, layout): layout[(x, y)] = (type, player)."""
     layout = {(cx, cy): (RANGED, 0)}
-    for dy in range(-4, 5):
-        for dx in range(-4, 5):
+    for dy in range(-r - 1, r + 2):
+        for dx in range(-r - 1, r + 2):
             x, y = cx + dx, cy + dy
             if (dx, dy) == (0, 0) or not (0 <= x < W and 0 <= y < H):
                 continue

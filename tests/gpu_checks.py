@@ -22,11 +22,11 @@ def oracle_threads():
 
 
 def rollout(maps, n_sp, n_bot=0, steps=200, max_steps=2000, utt=1, crs=1, policy="masked", dump_every=10, seed=3,
-            players=None, partial_obs=False, bots=None, rfs=None, utt_json=None, max_units=0):
+            players=None, partial_obs=False, bots=None, rfs=None, utt_json=None, max_units=0, reach=None):
     """One launch per step against the oracle, the same int32 action rows on both sides: masks before every step,
     the policy kernel's rows (masked policy), observations, rewards and dones after it, every slot's state dump
     every dump_every steps.  -> the handle's error flags; rollout.nonzero (set by the caller, one bool per reward
-    function) collects which reward functions fired."""
+    function) collects which reward functions fired; reach (tests.table_cases.Reach) is shown the oracle's masks of every step."""
     torch = torch_gpu()
     from microrts_amd import DeviceVecEnv, UnitTypeTable
 
@@ -50,6 +50,8 @@ def rollout(maps, n_sp, n_bot=0, steps=200, max_steps=2000, utt=1, crs=1, policy
         m_ref = ref.get_masks(0)
         env.synchronize()
         same(env.masks, m_ref, "masks", f"step {step}")
+        if reach is not None:
+            reach.add(m_ref)
         if policy == "masked":
             env.random_policy(SEED, step)
             env.synchronize()
@@ -75,7 +77,7 @@ def rollout(maps, n_sp, n_bot=0, steps=200, max_steps=2000, utt=1, crs=1, policy
     return flags
 
 
-def encode_obs_np(obs, ntypes=7):
+def encode_obs_np(obs, ntypes):
     """numpy restatement of MicroRTS-Py's GridnetVecEnv `_encode_obs` (gym_microrts, external to the
     reference — parity unpinned): per env, planes clipped to [0, n-1] and one-hot encoded, channels
     last, plane sizes [5, 5, 3, ntypes + 1, 6, 2] (+ [2] per extra partial-observability plane)."""
@@ -103,7 +105,7 @@ def onehot_encoder(mp, po):
         if step % 10 == 9:
             got = env.onehot_obs()
             env.synchronize()
-            ref = encode_obs_np(env.obs.cpu().numpy())
+            ref = encode_obs_np(env.obs.cpu().numpy(), 7)
             assert got.shape[-1] == (33 if po else 29), f"step {step}: {got.shape[-1]} one-hot channels"
             same(got, ref, "one-hot observation", f"step {step}")
     env.close()

@@ -91,7 +91,8 @@ def synthetic_rows(HW, K, nt, seed):
     rng = np.random.default_rng(seed)
     fr = _field_ranges(K, nt)
     last = HW - 1
-    rows = [("none", []), ("one", [min(5, last)]), ("four", [1, 7, 20, min(41, last)]), ("five", [0, 3, 9, 10, min(33, last)]),
+    at = lambda c: c % HW  # noqa: E731 (a 4x4 map: cells 20, 41 and 33 fold onto 4, 9 and 1, the counts stay 4 and 5)
+    rows = [("none", []), ("one", [min(5, last)]), ("four", [1, 7, at(20), at(41)]), ("five", [0, 3, 9, 10, at(33)]),
             ("chunk0", list(range(min(64, HW)))), ("all", list(range(HW))), ("empty_field", [2, min(50, last)]),
             ("off_mask", [4, 11]), ("minus_one_and_huge", [6, 12, 13]), ("tail", sorted({0, max(last - 1, 0), last}))]
     if HW > 64:

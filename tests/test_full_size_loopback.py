@@ -156,7 +156,7 @@ def _shard(cfg, g0, g1, points):
                 js, twin, got = oh
                 mine = np.nonzero((js == j) & (twin >= 2 * g0) & (twin < 2 * g1))[0]
                 if len(mine):
-                    want = encode_obs_np(ref.obs[twin[mine] - 2 * g0])
+                    want = encode_obs_np(ref.obs[twin[mine] - 2 * g0], 7)
                     for i, w in zip(mine, want):
                         if not np.array_equal(got[i], w):
                             bad["one-hot sample"] = bad.get("one-hot sample", 0) + 1

@@ -54,7 +54,7 @@ def _check_injected(A, ref, tag):
 
 def _check_onehot(A, po, tag):
     got = A.onehot_obs()
-    want = encode_obs_np(A.obs.cpu().numpy())
+    want = encode_obs_np(A.obs.cpu().numpy(), 7)
     assert got.shape == want.shape and got.shape[-1] == (33 if po else 29)
     same(got, want, "one-hot observation", tag)
 

@@ -2,6 +2,9 @@
 against the float64 reference and numpy Philox of tests/policy_head_ref.py.
 
 Shapes: 4x4 (16 cells: less than a wave), 9x8 (72 cells: a tail past 64), basesWorkers16x16 (the workload's).
+Tables: the built-in one (K = 79) on every shape; tests/table_cases.py's r3, r5, t5r3 and t8r5 (K = 39, 55, 37, 56:
+attack fields of 9 and 25 logits that leave most lanes of the field empty, 5 and 8 produce types that move every
+later logit) on 4x4 and 9x8, as cases "4x4-r3" ...  nt and K come from the handle.
 Masks: the environment's after 50 random steps (with its source bits), and synthetic ones (a slot without a
 candidate, a slot with every bit of every cell set, empty / single-bit / scattered fields, scattered attack windows).
 
@@ -13,7 +16,7 @@ import math
 import numpy as np
 import pytest
 
-from tests import policy_head_ref as R
+from tests import policy_head_ref as R, table_cases as TC
 from tests.defs import SEED
 from tests.gpu_support import assert_same_outputs, ptr, torch_gpu
 
@@ -26,6 +29,15 @@ HSEED, HSTEP = 0x0123456789ABCDEF, 17
 # MEASURED on an MI355X (fp32 CPU reference's deviation -> bound; the kernels' deviation):
 #   log-probability / entropy  4x4: 1.2e-5 -> 4.9e-5; 5.6e-6    9x8: 5.5e-5 -> 2.2e-4; 2.2e-5    16x16: 1.7e-4 -> 6.7e-4; 8.0e-5
 #   gradient                   4x4: 7.2e-7 -> 2.9e-6; 7.2e-7    9x8: 1.3e-6 -> 5.1e-6; 7.2e-7    16x16: 1.3e-6 -> 5.2e-6; 7.2e-7
+# the tables of tests/table_cases.py, the same three figures, 4x4 then 9x8:
+#   log-probability / entropy  r5:   1.2e-5 -> 4.9e-5; 5.9e-6    5.6e-5 -> 2.2e-4; 2.0e-5
+#                              r3:   7.7e-6 -> 3.1e-5; 5.2e-6    5.3e-5 -> 2.1e-4; 2.1e-5
+#                              t5r3: 8.8e-6 -> 3.5e-5; 5.2e-6    5.2e-5 -> 2.1e-4; 2.1e-5
+#                              t8r5: 1.3e-5 -> 5.1e-5; 4.6e-6    5.5e-5 -> 2.2e-4; 2.2e-5
+#   gradient                   r5:   4.2e-7 -> 1.7e-6; 5.1e-7    7.2e-7 -> 2.9e-6; 4.8e-7
+#                              r3:   4.8e-7 -> 1.9e-6; 7.2e-7    4.8e-7 -> 1.9e-6; 3.6e-7
+#                              t5r3: 4.2e-7 -> 1.7e-6; 3.6e-7    4.8e-7 -> 1.9e-6; 4.8e-7
+#                              t8r5: 7.7e-7 -> 3.1e-6; 4.2e-7    6.6e-7 -> 2.6e-6; 4.8e-7
 # (the sums run over up to 256 cells x 7 fields, magnitude ~3e3 in the every-bit-set rows; the kernels keep their
 # per-lane partial sums in double — with fp32 partial sums the 16x16 figure was 3.5e-4)
 TOL_FACTOR = 4.0
@@ -44,20 +56,30 @@ def _sample(env, logits, masks, source, seed, step):
     return out, lp, ent
 
 
+CASES = list(MAPS) + [f"{shape}-{t}" for t in TC.IDS for shape in ("4x4", "9x8")]
+
+
 class Case:
-    """one shape: an env stepped 50 times, its masks / source bits, synthetic masks, logits, the float64 reference"""
+    """one shape and table ("9x8", "9x8-r5"): an env stepped 50 times, its masks / source bits, synthetic masks,
+    logits, the float64 reference"""
 
-    def __init__(self, shape):
+    def __init__(self, name):
         torch = torch_gpu()
-        from microrts_amd import DeviceVecEnv
+        from microrts_amd import DeviceVecEnv, UnitTypeTable
 
-        self.env = env = DeviceVecEnv(S, 0, 2000, [MAPS[shape]] * S, seed=3)
+        shape, _, table = name.partition("-")
+        utt = UnitTypeTable.fromJSON(TC.utt_json(table)) if table else UnitTypeTable()
+        self.env = env = DeviceVecEnv(S, 0, 2000, [MAPS[shape]] * S, seed=3, utt=utt)
         env.reset()
         for k in range(50):
             env.random_policy(SEED, k)
             env.step()
         _, H, W, _, K = env.dims
-        self.HW, self.K, self.nt = H * W, K, 7
+        # the handle's own type count: its one-hot observation has 5 + 5 + 3 + (nt + 1) + 6 + 2 features
+        self.HW, self.K, self.nt = H * W, K, env._h.L.mrts_onehot_features(env._h.h) - 22
+        assert (self.nt, K) == ((TC.TABLES[table].nt, TC.TABLES[table].K) if table else (7, 79))
+        assert not (table and env.multi_step_capable), "only the K = 79 instances run several steps per launch"
+        assert K == 23 + self.nt + (2 * utt.getMaxAttackRange() + 1) ** 2
         g = torch.Generator().manual_seed(H * W)
         self.logits_cpu = 3 * torch.randn((S, H * W, K - 1), generator=g)
         self.logits = self.logits_cpu.to(env.device)
@@ -83,7 +105,15 @@ def _case(shape):
     return _CASES[shape]
 
 
-@pytest.fixture(params=list(MAPS))
+@pytest.fixture(scope="module", autouse=True)
+def _close_table_cases():
+    """the table cases' handles end with the module; the three built-in ones stay, as before"""
+    yield
+    for name in [n for n in _CASES if "-" in n]:
+        _CASES.pop(name).env.close()
+
+
+@pytest.fixture(params=CASES)
 def case(request):
     return _case(request.param)
 

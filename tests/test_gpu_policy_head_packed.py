@@ -3,6 +3,8 @@ DeviceVecEnv.pack_step / unpack, evaluate_actions_packed) against the numpy pack
 and, for the score and the gradient, against the dense kernels: the same bytes, compared as int32.
 
 Shapes: 8x8 (one 64-cell chunk), NoWhereToRun9x8 (72 cells: a short last chunk), basesWorkers16x16 (four chunks).
+Tables: the built-in one (K = 79) on these; tests/table_cases.py's r3, r5, t5r3 and t8r5 (K = 39, 55, 37, 56) on 4x4
+and 9x8, as cases "4x4-r3" ...  nt and K come from the handle.
 Rows: a 16-slot rollout of 50 steps driven by sample_actions (its last T steps with a candidate kept dense and
 packed), and the synthetic rows of policy_head_packed_ref.synthetic_rows (no candidate; 1, 4, 5, 64 candidates in a chunk; both sides of a chunk
 boundary; every cell; an empty field; components off the mask, -1 and 2^30; junk at non-candidate cells)."""
@@ -12,12 +14,14 @@ import math
 import numpy as np
 import pytest
 
-from tests import policy_head_packed_ref as PR
+from tests import policy_head_packed_ref as PR, table_cases as TC
 from tests.gpu_support import ptr, torch_gpu
 
 pytestmark = pytest.mark.gpu
 
 MAPS = {"8x8": "maps/8x8/basesWorkers8x8.xml", "9x8": "maps/NoWhereToRun9x8.xml", "16x16": "maps/16x16/basesWorkers16x16.xml"}
+TABLE_MAPS = {"4x4": "maps/4x4/basesWorkers4x4.xml", "9x8": MAPS["9x8"]}
+CASES = list(MAPS) + [f"{shape}-{t}" for t in TC.IDS for shape in TABLE_MAPS]
 S, T, STEPS = 16, 4, 50
 HSEED = 0x0123456789ABCDEF
 
@@ -37,15 +41,21 @@ def _np32(t):
 
 
 class Case:
-    """one shape: a rollout under sample_actions whose last T steps are kept dense and packed, and the synthetic rows"""
+    """one shape and table ("9x8", "9x8-r5"): a rollout under sample_actions whose last T steps are kept dense and
+    packed, and the synthetic rows"""
 
-    def __init__(self, shape):
+    def __init__(self, name):
         torch = torch_gpu()
-        from microrts_amd import DeviceVecEnv
+        from microrts_amd import DeviceVecEnv, UnitTypeTable
 
-        self.env = env = DeviceVecEnv(S, 0, 2000, [MAPS[shape]] * S, seed=3)
+        shape, _, table = name.partition("-")
+        utt = UnitTypeTable.fromJSON(TC.utt_json(table)) if table else UnitTypeTable()
+        self.env = env = DeviceVecEnv(S, 0, 2000, [(TABLE_MAPS if table else MAPS)[shape]] * S, seed=3, utt=utt)
         _, H, W, _, K = env.dims
-        self.HW, self.K, self.nt = H * W, K, 7
+        # the handle's own type count: its one-hot observation has 5 + 5 + 3 + (nt + 1) + 6 + 2 features
+        self.HW, self.K, self.nt = H * W, K, env._h.L.mrts_onehot_features(env._h.h) - 22
+        assert (self.nt, K) == ((TC.TABLES[table].nt, TC.TABLES[table].K) if table else (7, 79))
+        assert not (table and env.multi_step_capable), "only the K = 79 instances run several steps per launch"
         dev = env.device
         g = torch.Generator().manual_seed(H * W)
         self.buf = env.packed_buffer(T)
@@ -53,7 +63,10 @@ class Case:
         # the last T steps that had a candidate (on the small maps every unit is busy on most steps), in ring order
         ring, kept = [None] * T, 0
         env.reset()
-        for k in range(STEPS):
+        # (under a table's costs and times STEPS steps can hold fewer than T steps with a candidate: go on, up to 8x)
+        for k in range(8 * STEPS if table else STEPS):
+            if k >= STEPS and kept >= T:
+                break
             logits = (3 * torch.randn((S, H * W, K - 1), generator=g)).to(dev)
             _, lp, _ = env.sample_actions(logits, HSEED, k)
             if bool(env.source.any()):
@@ -106,7 +119,15 @@ def _case(shape):
     return _CASES[shape]
 
 
-@pytest.fixture(params=list(MAPS))
+@pytest.fixture(scope="module", autouse=True)
+def _close_table_cases():
+    """the table cases' handles end with the module; the three built-in ones stay, as before"""
+    yield
+    for name in [n for n in _CASES if "-" in n]:
+        _CASES.pop(name).env.close()
+
+
+@pytest.fixture(params=CASES)
 def case(request):
     return _case(request.param)
 

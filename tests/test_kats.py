@@ -14,6 +14,7 @@ unit type or -1, issue time) * n_assign].  Unit type ids (UnitTypeTable.java:104
 Base 1, Barracks 2, Worker 3, Light 4, Heavy 5, Ranged 6.  Action types (UnitAction.java:31-60):
 NONE 0, MOVE 1, HARVEST 2, RETURN 3, PRODUCE 4, ATTACK 5.  Directions: up 0, right 1, down 2, left 3.
 Attack index = (3 + dy) * 7 + (3 + dx) (maxAttackRadius 7, JNIGridnetClient.java:125).
+Under a table of tests.table_cases (R = 2 * maxAttackRange + 1 = 3 or 5): (R // 2 + dy) * R + (R // 2 + dx).
 """
 
 import numpy as np
@@ -34,18 +35,20 @@ def parse(d):
 class Runner:
     """Self-play pair (slots 0 = player 0, 1 = player 1) on the oracle or on the GPU."""
 
-    def __init__(self, backend, map_path, partial_obs=False, max_steps=2000, rfs=None):
+    def __init__(self, backend, map_path, partial_obs=False, max_steps=2000, rfs=None, utt_json=None):
         self.backend = backend
         self.po = partial_obs
         if backend == "oracle":
             self.e = oracle_py.OracleVecClient(2, 0, max_steps, [map_path] * 2, partial_obs=partial_obs,
-                                               rewards=[oracle_py.REWARD_IDS[r] for r in rfs] if rfs else None)
+                                               rewards=[oracle_py.REWARD_IDS[r] for r in rfs] if rfs else None,
+                                               utt_json=utt_json)
             self.e.reset()
         else:
-            from microrts_amd import DeviceVecEnv
+            from microrts_amd import DeviceVecEnv, UnitTypeTable
 
             self.torch = torch_gpu()
-            self.e = DeviceVecEnv(2, 0, max_steps, [map_path] * 2, partial_obs=partial_obs, rfs=rfs)
+            self.e = DeviceVecEnv(2, 0, max_steps, [map_path] * 2, partial_obs=partial_obs, rfs=rfs,
+                                  utt=UnitTypeTable.fromJSON(utt_json) if utt_json else None)
             self.e.reset()
 
     def step(self, rows0=(), rows1=()):
@@ -446,60 +449,69 @@ def _expected_view(layout, W, H, player, po):
     return hp, owner, typ, vis
 
 
-def _ranged_window_kat(tmp, backend, W, H, po=False, max_units=0):
+def _ranged_window_kat(tmp, backend, W, H, po=False, max_units=0, table=None):
     """a12 — the attack slots of a unit with attackRange > 1.  Unit.getUnitActions (Unit.java:424-434):
     one ATTACK_LOCATION for every unit u of the other player (u.player >= 0, so no Resource) with
-    (u.x - x)^2 + (u.y - y)^2 <= attackRange^2 — Ranged: 3 (UnitTypeTable.java:270), so the 28 offsets
-    with dx^2 + dy^2 <= 9 — over the whole unit list, no window and no map-border test of its own.
-    UnitAction.getValidActionArray (UnitAction.java:742-747) sets slot 30 + (3 + dy) * 7 + (3 + dx) and the
-    attack type bit 1 + 5; slot 0 marks an own unit without an action (JNIGridnetClientSelfPlay.java:196-209).
+    (u.x - x)^2 + (u.y - y)^2 <= attackRange^2 — Ranged: r = 3 in the built-in tables (UnitTypeTable.java:270),
+    so the 28 offsets with dx^2 + dy^2 <= 9; r = 2 in tests.table_cases' r5 and t8r5, so 12 offsets — over the
+    whole unit list, no window and no map-border test of its own.  UnitAction.getValidActionArray
+    (UnitAction.java:742-747) sets slot 23 + nt + (r_max + dy) * R + (r_max + dx), with r_max the table's largest
+    range and R = 2 * r_max + 1 (30 + (3 + dy) * 7 + (3 + dx) for the built-in tables), and the attack type bit
+    1 + 5; slot 0 marks an own unit without an action (JNIGridnetClientSelfPlay.java:196-209).
     The masks always come from the full state, partially observable or not (:205).
     One handle, one game per (position, flip) of tests.combat_maps.ranged_window: in every game the
-    Ranged cell's 49 attack slots, attack type bit and slot 0 equal the rule applied to the layout; over
+    Ranged cell's R * R attack slots, attack type bit and slot 0 equal the rule applied to the layout; over
     the two flips every in-range offset is set once and clear once.  Every other mask row equals the
-    oracle's.  The reset observations of both players equal _expected_view of the layout."""
+    oracle's.  The reset observations of both players equal _expected_view of the layout.
+    table: an id of tests.table_cases (None: the built-in table)."""
+    from tests import table_cases as T
     from tests.combat_maps import in_range, ranged_window
 
+    c = T.TABLES[table] if table else T.Table("v1", 1, 1, 7, 7, 79, ("Ranged",))
+    js = T.utt_json(table) if table else None
+    r = T.attack_range(table, "Ranged") if table else 3
+    nt, R, ctr, base = c.nt, c.R, c.R // 2, 23 + c.nt
     games = [(cx, cy, flip) for cx, cy in window_positions(W, H) for flip in (0, 1)]
     maps, layouts = [], []
     for g, (cx, cy, flip) in enumerate(games):
-        m, lay = ranged_window(tmp / f"rw{W}x{H}_{g}.xml", W, H, cx, cy, flip)
+        m, lay = ranged_window(tmp / f"rw{W}x{H}_{g}.xml", W, H, cx, cy, flip, r)
         maps += [m, m]
         layouts.append(lay)
     S = len(maps)
-    ref = oracle_py.OracleVecClient(S, 0, 2000, maps, partial_obs=po)
+    ref = oracle_py.OracleVecClient(S, 0, 2000, maps, partial_obs=po, utt_version=c.version, crs=c.crs, utt_json=js)
     ref_obs, _, _ = ref.reset()
     ref_masks = ref.get_masks(0)
     if backend == "oracle":
         obs, masks = ref_obs, ref_masks
     else:
         torch_gpu()
-        from microrts_amd import DeviceVecEnv
+        from microrts_amd import DeviceVecEnv, UnitTypeTable
 
-        e = DeviceVecEnv(S, 0, 2000, maps, partial_obs=po, max_units=max_units)
+        e = DeviceVecEnv(S, 0, 2000, maps, partial_obs=po, max_units=max_units,
+                         utt=UnitTypeTable.fromJSON(js) if js else UnitTypeTable())
         e.reset()
         e.synchronize()
         obs, masks = e.obs.cpu().numpy(), e.masks.cpu().numpy()
         assert not e.error_flags().any()
         e.close()
     ref.close()
-    assert masks.shape == (S, H, W, 79)
-    hit = np.zeros((7, 7), np.int32)
+    assert masks.shape == (S, H, W, c.K) and c.K == 1 + 22 + nt + R * R
+    hit = np.zeros((R, R), np.int32)
     for g, (cx, cy, flip) in enumerate(games):
         lay = layouts[g]
-        if (cx, cy) == (W // 2, H // 2) and min(W, H) >= 9:
-            assert len(lay) == 81  # more than one wave of units: the multi-block mask path
-        want = np.zeros(49, np.uint8)
-        for dy in range(-3, 4):
-            for dx in range(-3, 4):
+        if (cx, cy) == (W // 2, H // 2) and min(W, H) >= 2 * r + 3:
+            assert len(lay) == (2 * r + 3) ** 2  # r = 3: more than one wave of units, the multi-block mask path
+        want = np.zeros(R * R, np.uint8)
+        for dy in range(-ctr, ctr + 1):
+            for dx in range(-ctr, ctr + 1):
                 t, p = lay.get((cx + dx, cy + dy), (None, -1))
-                if (dx, dy) != (0, 0) and in_range(dx, dy) and p == 1:
-                    want[atk(dx, dy)] = 1
-        hit += want.reshape(7, 7) if (cx, cy) == (W // 2, H // 2) else 0
+                if (dx, dy) != (0, 0) and in_range(dx, dy, r) and p == 1:
+                    want[(ctr + dy) * R + (ctr + dx)] = 1
+        hit += want.reshape(R, R) if (cx, cy) == (W // 2, H // 2) else 0
         k = masks[2 * g, cy, cx]
         tag = f"{W}x{H} Ranged at ({cx},{cy}) flip {flip}"
-        assert k[30:79].tolist() == want.tolist(), \
-            f"{tag}: attack slots\n got {k[30:79].reshape(7, 7)}\nwant {want.reshape(7, 7)}"
+        assert k[base:c.K].tolist() == want.tolist(), \
+            f"{tag}: attack slots\n got {k[base:c.K].reshape(R, R)}\nwant {want.reshape(R, R)}"
         assert k[0] == 1 and k[1 + ATTACK] == int(want.any()), tag
         rest = np.ones((H, W), bool)
         rest[cy, cx] = False
@@ -511,9 +523,10 @@ def _ranged_window_kat(tmp, backend, W, H, po=False, max_units=0):
             for name, plane, exp in (("hp", 0, hp), ("owner", 2, owner), ("type", 3, typ)) + \
                     ((("own sight", 6, vis[0]), ("opponent sight", 7, vis[1])) if po else ()):
                 assert np.array_equal(o[plane], exp), f"{tag}: {name} plane of player {player}\n got {o[plane]}\nwant {exp}"
-    if min(W, H) >= 7:  # the centre window is whole: over the two flips every in-range offset was set once
-        disk = np.array([[int(in_range(dx, dy) and (dx, dy) != (0, 0)) for dx in range(-3, 4)] for dy in range(-3, 4)])
-        assert np.array_equal(hit, disk) and disk.sum() == 28
+    if min(W, H) >= 2 * r + 1:  # the centre window is whole: over the two flips every in-range offset was set once
+        disk = np.array([[int(in_range(dx, dy, r) and (dx, dy) != (0, 0)) for dx in range(-ctr, ctr + 1)]
+                         for dy in range(-ctr, ctr + 1)])
+        assert np.array_equal(hit, disk) and disk.sum() == {3: 28, 2: 12}[r]
 
 
 def kat_ranged_window_16x16(tmp, backend):
@@ -538,11 +551,83 @@ def kat_ranged_window_32x32_po(tmp, backend):
     _ranged_window_kat(tmp, backend, 32, 32, po=True, max_units=256)
 
 
+def kat_ranged_window_r5_8x8(tmp, backend):
+    """_ranged_window_kat under table r5 (Ranged range 2: R = 5, K = 55) on 8x8, a square map that only the
+    built-in layout sends to the specialised step kernel."""
+    _ranged_window_kat(tmp, backend, 8, 8, table="r5")
+
+
+def kat_ranged_window_r5_14x12(tmp, backend):
+    """_ranged_window_kat under table r5 on a non-square map."""
+    _ranged_window_kat(tmp, backend, 14, 12, table="r5")
+
+
+def kat_ranged_window_r5_16x16(tmp, backend):
+    """_ranged_window_kat under table r5 on 16x16."""
+    _ranged_window_kat(tmp, backend, 16, 16, table="r5")
+
+
+def kat_ranged_window_r5_32x32_po(tmp, backend):
+    """_ranged_window_kat under table r5 on 32x32, partially observable, max_units 256."""
+    _ranged_window_kat(tmp, backend, 32, 32, po=True, max_units=256, table="r5")
+
+
+def kat_ranged_window_t8r5_14x12(tmp, backend):
+    """_ranged_window_kat under table t8r5 (8 types, Ranged range 2: the attack slots start at 31, K = 56)."""
+    _ranged_window_kat(tmp, backend, 14, 12, table="t8r5")
+
+
+def _attack_decode_kat(tmp, backend, table, a_off, b_off):
+    """UnitAction.fromVectorAction (UnitAction.java:700-705): relative_x = a[7] % R - r_max, relative_y = a[7] / R - r_max
+    with R = 2 * r_max + 1 of the table (JNIGridnetClient.java:125).  Ranged U of player 0 at (3,1) on 7x7, enemy
+    Bases A at offset a_off and B at offset b_off, both within U's range.  The index of a_off in a 7-wide window,
+    (3 + dy) * 7 + (3 + dx), names another cell under this table (an empty one, or none U can reach), so issueSafe
+    turns the row into NONE(attackTime 5) (GameState.java:347-354) and nothing is hit.  The table's own index
+    (r_max + dy) * R + (r_max + dx) gives ATTACK_LOCATION on A; at issue time + 5 A alone loses Ranged's damage 1."""
+    from tests import table_cases as T
+
+    c = T.TABLES[table]
+    ux, uy = 3, 1
+    (ax, ay), (bx, by) = (ux + a_off[0], uy + a_off[1]), (ux + b_off[0], uy + b_off[1])
+    m = write_map(tmp / f"dec_{table}.xml", 7, 7, [(RANGED, 0, ux, uy), (BASE, 1, ax, ay), (BASE, 1, bx, by), (BASE, 0, 0, 6)])
+    r = Runner(backend, m, utt_json=T.utt_json(table))
+    pos = uy * 7 + ux
+    r.step([row(pos, ATTACK, attack=atk(*a_off))])
+    assert r.state()["assign"] == [(0, NONE, 5, 0, 0, -1, 0)]
+    r.idle(5)
+    s = r.state()
+    assert s["time"] == 6 and s["assign"] == [] and [u[4] for u in s["units"]] == [1, 10, 10, 10]
+    r.step([row(pos, ATTACK, attack=T.atk_index(c, *a_off))])
+    assert r.state()["assign"] == [(0, ATTACK, -1, ax, ay, -1, 6)]
+    r.idle(4)
+    s = r.state()
+    assert s["time"] == 11 and s["assign"] == []
+    assert s["units"] == [(RANGED, 0, ux, uy, 1, 0), (BASE, 1, ax, ay, 9, 0), (BASE, 1, bx, by, 10, 0), (BASE, 0, 0, 6, 10, 0)]
+    r.close()
+
+
+def kat_attack_decode_r5(tmp, backend):
+    """_attack_decode_kat with R = 5 (table r5, Ranged range 2): A at (+2,0) is index 2 * 5 + 4 = 14 (an offset
+    that is not its own transpose: a decode with dx and dy exchanged names the empty cell (0,+2)); the 7-wide
+    index 3 * 7 + 5 = 26 is past the 25 slots of the window and decodes as 26 % 5 - 2 = -1, 26 / 5 - 2 = +3: the
+    empty cell (2,4), out of range.  B at (-1,-1)."""
+    _attack_decode_kat(tmp, backend, "r5", (2, 0), (-1, -1))
+
+
+def kat_attack_decode_r3(tmp, backend):
+    """_attack_decode_kat with R = 3 (table r3, Ranged range 1): A at (0,-1) is index 0 * 3 + 1 = 1; the 7-wide
+    index 2 * 7 + 3 = 17 is past the 9 slots of the window and decodes as 17 % 3 - 1 = +1, 17 / 3 - 1 = +4: the empty
+    cell (4,5), out of range.  B at (+1,0)."""
+    _attack_decode_kat(tmp, backend, "r3", (0, -1), (1, 0))
+
+
 KATS = [kat_illegal_becomes_none_eta, kat_resource_quirk_row_order, kat_rows_that_do_not_count,
         kat_player1_sees_player0_reservations, kat_dead_unit_still_executes, kat_simultaneous_kill_is_a_draw,
         kat_harvest_deplete_return, kat_duplicate_row_keeps_map_position, kat_po_killed_unit_in_view, kat_mask_record,
         kat_reward_functions, kat_env_steps_survive_reset, kat_selfplay_reset_keeps_slots_from_two,
-        kat_ranged_window_16x16, kat_ranged_window_8x8, kat_ranged_window_14x12, kat_ranged_window_32x32_po]
+        kat_ranged_window_16x16, kat_ranged_window_8x8, kat_ranged_window_14x12, kat_ranged_window_32x32_po,
+        kat_ranged_window_r5_8x8, kat_ranged_window_r5_14x12, kat_ranged_window_r5_16x16, kat_ranged_window_r5_32x32_po,
+        kat_ranged_window_t8r5_14x12, kat_attack_decode_r5, kat_attack_decode_r3]
 
 
 @pytest.mark.parametrize("kat", KATS, ids=[k.__name__ for k in KATS])
