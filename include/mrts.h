@@ -438,6 +438,37 @@ int mrts_policy_head_score_packed_dev(mrts_env* env, int32_t n_rows, const float
 int mrts_policy_head_grad_packed_dev(mrts_env* env, int32_t n_rows, const float* d_logits, const uint32_t* d_packed,
                                      int32_t n_packed, int32_t cap, const int32_t* d_index, const float* d_g_logprob,
                                      const float* d_g_entropy, float* d_grad_logits, void* stream);
+/* Logits in the network's own type: the five calls above that read logits, with the element type of d_logits (and of
+ * d_grad_logits) as an argument; every other argument is the float32 call's.  MRTS_LOGITS_F32 through a typed entry
+ * point is the float32 call.  A 16-bit logit (bfloat16, or IEEE float16, subnormals included) is converted to fp32
+ * exactly when it is loaded, and every arithmetic step after the load is the float32 call's, so
+ *   - action rows, log-probability and entropy (int32 / float32, as above) are byte for byte what the float32 call
+ *     gives on the logits converted to float32, with the same masks, source bits, seed and step;
+ *   - d_grad_logits has the logits' type, every element written: the float32 call's value rounded once, to nearest
+ *     even (a float32 gradient cast to the type gives the same bits); cleared bits and cells that are no candidates
+ *     are exact +0; the NaN rows of the packed gradient (a count above cap, an index outside the packed rows) are NaN
+ *     of some payload;
+ *   - logits at cleared bits and of other cells are dropped before any arithmetic, as above (they may be NaN / inf).
+ * A 16-bit d_logits / d_grad_logits needs 2-byte alignment only (float32: 4).
+ * -EINVAL: logits_type outside the enum, a misaligned buffer ("misaligned buffer"), a NULL required pointer ("null
+ * argument"), and what the float32 calls refuse; -ENOTSUP: a bot-only or forward-model handle. */
+enum { MRTS_LOGITS_F32 = 0, MRTS_LOGITS_BF16 = 1, MRTS_LOGITS_F16 = 2 };
+int mrts_policy_head_sample_typed_dev(mrts_env* env, int32_t logits_type, const void* d_logits, const uint8_t* d_masks,
+                                      const uint32_t* d_source, uint64_t seed, uint32_t step, int32_t* d_actions,
+                                      float* d_logprob, float* d_entropy, void* stream);
+int mrts_policy_head_score_typed_dev(mrts_env* env, int32_t n_rows, int32_t logits_type, const void* d_logits,
+                                     const uint8_t* d_masks, const int32_t* d_actions, float* d_logprob, float* d_entropy,
+                                     void* stream);
+int mrts_policy_head_grad_typed_dev(mrts_env* env, int32_t n_rows, int32_t logits_type, const void* d_logits,
+                                    const uint8_t* d_masks, const int32_t* d_actions, const float* d_g_logprob,
+                                    const float* d_g_entropy, void* d_grad_logits, void* stream);
+int mrts_policy_head_score_packed_typed_dev(mrts_env* env, int32_t n_rows, int32_t logits_type, const void* d_logits,
+                                            const uint32_t* d_packed, int32_t n_packed, int32_t cap, const int32_t* d_index,
+                                            float* d_logprob, float* d_entropy, void* stream);
+int mrts_policy_head_grad_packed_typed_dev(mrts_env* env, int32_t n_rows, int32_t logits_type, const void* d_logits,
+                                           const uint32_t* d_packed, int32_t n_packed, int32_t cap, const int32_t* d_index,
+                                           const float* d_g_logprob, const float* d_g_entropy, void* d_grad_logits,
+                                           void* stream);
 /* Optional compact output of every mask write: mask slot 0 ("own unit without an action here") as
  * bits, uint32 [n_slots][ceil(H*W/32)] (sticky; NULL disables).  mrts_policy_dev uses it, when
  * given, to read only the candidate cells' mask rows. */

@@ -8,6 +8,7 @@ LIB_PATH = os.environ.get("MRTS_LIB_PATH") or os.path.join(HERE, "libmrts.so")  
 
 MRTS_BOT_PASSIVE, MRTS_BOT_RANDOM_BIASED, MRTS_BOT_LIGHT_RUSH = 0, 1, 2
 MRTS_MAX_HORIZON = 65536
+MRTS_LOGITS_F32, MRTS_LOGITS_BF16, MRTS_LOGITS_F16 = 0, 1, 2  # the logits' element type of the policy head's typed calls
 # a_rfs names (src/ai/reward/*.java) -> MRTS_RF_* ids
 REWARD_FUNCTIONS = {"WinLossRewardFunction": 0, "ResourceGatherRewardFunction": 1, "ProduceWorkerRewardFunction": 2,
                     "ProduceBuildingRewardFunction": 3, "AttackRewardFunction": 4, "ProduceCombatUnitRewardFunction": 5,
@@ -179,6 +180,11 @@ SIGNATURES = {
     "mrts_policy_head_unpack_dev": ([_P, _I32, _P, _I32, _I32, _P, _P, _P, _P], _INT),
     "mrts_policy_head_score_packed_dev": ([_P, _I32, _P, _P, _I32, _I32, _P, _P, _P, _P], _INT),
     "mrts_policy_head_grad_packed_dev": ([_P, _I32, _P, _P, _I32, _I32, _P, _P, _P, _P, _P], _INT),
+    "mrts_policy_head_sample_typed_dev": ([_P, _I32, _P, _P, _P, _U64, _U32, _P, _P, _P, _P], _INT),
+    "mrts_policy_head_score_typed_dev": ([_P, _I32, _I32, _P, _P, _P, _P, _P, _P], _INT),
+    "mrts_policy_head_grad_typed_dev": ([_P, _I32, _I32, _P, _P, _P, _P, _P, _P, _P], _INT),
+    "mrts_policy_head_score_packed_typed_dev": ([_P, _I32, _I32, _P, _P, _I32, _I32, _P, _P, _P, _P], _INT),
+    "mrts_policy_head_grad_packed_typed_dev": ([_P, _I32, _I32, _P, _P, _I32, _I32, _P, _P, _P, _P, _P], _INT),
     "mrts_set_source_output": ([_P, _P], _INT),
     "mrts_onehot_features": ([_P], _INT),
     "mrts_onehot_dev": ([_P, _P, _P, _P], _INT),

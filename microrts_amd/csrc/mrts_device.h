@@ -370,6 +370,24 @@ DEV void headFlush(const int32_t* lds, int32_t* gp, int a, int nw, int lane, int
         }
     }
 }
+// nh halfwords of a chunk: LDS halfword t <-> gp[t], the chunk at t in [a, a + nh) with gp 16-byte aligned (a = the
+// chunk's halfword offset 0..7 in its vector).  Whole vectors inside the chunk leave as dwordx4, the edges as 16-bit
+// stores — never a dword: the halfword next to an edge is another wave's, or lies past the tensor.  lds null: zeros.
+DEV void headFlush(const uint16_t* lds, uint16_t* gp, int a, int nh, int lane, int nl = 64) {
+    const int nv = (a + nh + 7) >> 3;
+    for (int v = lane; v < nv; v += nl) {
+        const int t = 8 * v;
+        const int4 x = lds ? ((const int4*)lds)[v] : make_int4(0, 0, 0, 0);
+        if (t >= a && t + 8 <= a + nh) {
+            ((int4*)gp)[v] = x;
+        } else {
+            const int xs[4] = {x.x, x.y, x.z, x.w};
+#pragma unroll
+            for (int k = 0; k < 8; k++)
+                if (t + k >= a && t + k < a + nh) gp[t + k] = (uint16_t)((uint32_t)xs[k >> 1] >> (16 * (k & 1)));
+        }
+    }
+}
 // nb bytes of a chunk to global memory as dwordx4 where whole vectors lie inside it: LDS byte t <-> gp[t], the chunk
 // at t in [a, a + nb) with gp 16-byte aligned.  lds null: zeros.
 DEV void headFlushBytes(const uint8_t* lds, uint8_t* gp, int a, int nb, int lane, int nl = 64) {

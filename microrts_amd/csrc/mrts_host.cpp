@@ -1142,13 +1142,23 @@ int mrts_policy_dev(mrts_env* env, const uint8_t* d_masks, const uint32_t* d_sou
 }
 
 namespace {
-// the policy head's shared argument checks; n_rows rows of the handle's H*W cells
-HeadParams headParams(mrts_env* env, int32_t n_rows, const float* d_logits, const uint8_t* d_masks, const int32_t* d_actions) {
+static_assert(HEAD_LT_F32 == MRTS_LOGITS_F32 && HEAD_LT_BF16 == MRTS_LOGITS_BF16 && HEAD_LT_F16 == MRTS_LOGITS_F16,
+              "the kernels' element types are include/mrts.h's");
+// the logits' element type of a typed call: its alignment mask (a 16-bit buffer needs 2-byte alignment only)
+uintptr_t headLogitAlign(int32_t ltype) {
+    if (ltype != HEAD_LT_F32 && ltype != HEAD_LT_BF16 && ltype != HEAD_LT_F16)
+        throw Fail{-EINVAL, "logits_type: MRTS_LOGITS_F32, MRTS_LOGITS_BF16 or MRTS_LOGITS_F16"};
+    return (uintptr_t)headLogitBytes(ltype) - 1;
+}
+// the policy head's shared argument checks; n_rows rows of the handle's H*W cells, logits of element type ltype
+HeadParams headParams(mrts_env* env, int32_t n_rows, int32_t ltype, const void* d_logits, const uint8_t* d_masks,
+                      const int32_t* d_actions) {
+    const uintptr_t lmask = headLogitAlign(ltype);
     if (env->botOnly || env->forwardModel)
         throw Fail{-ENOTSUP, "the policy head needs a handle that writes masks (not a bot-only or forward-model handle)"};
     if (!d_logits || !d_masks || !d_actions) throw Fail{-EINVAL, "null argument"};
     if (n_rows < 0 || (int64_t)n_rows * env->HW >= ((int64_t)1 << 31)) throw Fail{-EINVAL, "n_rows: 0 <= n_rows * H*W < 2^31"};
-    if (((uintptr_t)d_logits & 3) || ((uintptr_t)d_actions & 3)) throw Fail{-EINVAL, "misaligned buffer"};
+    if (((uintptr_t)d_logits & lmask) || ((uintptr_t)d_actions & 3)) throw Fail{-EINVAL, "misaligned buffer"};
     const int nt = env->utt.ntypes, natt = env->K - 23 - nt;
     if (env->K - 1 > HEAD_MAX_LOGITS || nt > 16 || natt < 0 || natt > 64)
         throw Fail{-ENOTSUP, "the policy head: at most 16 unit types, 64 attack-window cells and 80 logits per cell"};
@@ -1160,17 +1170,17 @@ HeadParams headParams(mrts_env* env, int32_t n_rows, const float* d_logits, cons
     Q.n_rows = n_rows;
     Q.slot_id_base = env->slotIdBase;
     Q.logits = d_logits;
+    Q.ltype = ltype;
     Q.masks = d_masks;
     Q.actions = const_cast<int32_t*>(d_actions);
     return Q;
 }
-}  // namespace
 
-int mrts_policy_head_sample_dev(mrts_env* env, const float* d_logits, const uint8_t* d_masks, const uint32_t* d_source,
-                                uint64_t seed, uint32_t step, int32_t* d_actions, float* d_logprob, float* d_entropy,
-                                void* stream) {
+// the three dense calls, for the float32 entry points (ltype MRTS_LOGITS_F32) and the typed ones alike
+int headSample(mrts_env* env, int32_t ltype, const void* d_logits, const uint8_t* d_masks, const uint32_t* d_source,
+               uint64_t seed, uint32_t step, int32_t* d_actions, float* d_logprob, float* d_entropy, void* stream) {
     return guarded(env, [&] {
-        HeadParams Q = headParams(env, env->nSlots, d_logits, d_masks, d_actions);
+        HeadParams Q = headParams(env, env->nSlots, ltype, d_logits, d_masks, d_actions);
         if (((uintptr_t)d_source & 3) || ((uintptr_t)d_logprob & 3) || ((uintptr_t)d_entropy & 3)) throw Fail{-EINVAL, "misaligned buffer"};
         HIPCHK(hipSetDevice(env->device));
         Q.source = d_source;
@@ -1186,10 +1196,10 @@ int mrts_policy_head_sample_dev(mrts_env* env, const float* d_logits, const uint
     });
 }
 
-int mrts_policy_head_score_dev(mrts_env* env, int32_t n_rows, const float* d_logits, const uint8_t* d_masks,
-                               const int32_t* d_actions, float* d_logprob, float* d_entropy, void* stream) {
+int headScore(mrts_env* env, int32_t n_rows, int32_t ltype, const void* d_logits, const uint8_t* d_masks,
+              const int32_t* d_actions, float* d_logprob, float* d_entropy, void* stream) {
     return guarded(env, [&] {
-        HeadParams Q = headParams(env, n_rows, d_logits, d_masks, d_actions);
+        HeadParams Q = headParams(env, n_rows, ltype, d_logits, d_masks, d_actions);
         if (((uintptr_t)d_logprob & 3) || ((uintptr_t)d_entropy & 3)) throw Fail{-EINVAL, "misaligned buffer"};
         HIPCHK(hipSetDevice(env->device));
         Q.logprob = d_logprob;
@@ -1199,13 +1209,12 @@ int mrts_policy_head_score_dev(mrts_env* env, int32_t n_rows, const float* d_log
     });
 }
 
-int mrts_policy_head_grad_dev(mrts_env* env, int32_t n_rows, const float* d_logits, const uint8_t* d_masks,
-                              const int32_t* d_actions, const float* d_g_logprob, const float* d_g_entropy,
-                              float* d_grad_logits, void* stream) {
+int headGrad(mrts_env* env, int32_t n_rows, int32_t ltype, const void* d_logits, const uint8_t* d_masks,
+             const int32_t* d_actions, const float* d_g_logprob, const float* d_g_entropy, void* d_grad_logits, void* stream) {
     return guarded(env, [&] {
-        HeadParams Q = headParams(env, n_rows, d_logits, d_masks, d_actions);
+        HeadParams Q = headParams(env, n_rows, ltype, d_logits, d_masks, d_actions);
         if (!d_grad_logits) throw Fail{-EINVAL, "null argument"};
-        if (((uintptr_t)d_g_logprob & 3) || ((uintptr_t)d_g_entropy & 3) || ((uintptr_t)d_grad_logits & 3))
+        if (((uintptr_t)d_g_logprob & 3) || ((uintptr_t)d_g_entropy & 3) || ((uintptr_t)d_grad_logits & headLogitAlign(ltype)))
             throw Fail{-EINVAL, "misaligned buffer"};
         HIPCHK(hipSetDevice(env->device));
         Q.g_logprob = d_g_logprob;
@@ -1214,6 +1223,39 @@ int mrts_policy_head_grad_dev(mrts_env* env, int32_t n_rows, const float* d_logi
         HIPCHK(launchHead(HEAD_GRAD, Q, pickStream(env, stream)));
         return 0;
     });
+}
+}  // namespace
+
+int mrts_policy_head_sample_dev(mrts_env* env, const float* d_logits, const uint8_t* d_masks, const uint32_t* d_source,
+                                uint64_t seed, uint32_t step, int32_t* d_actions, float* d_logprob, float* d_entropy,
+                                void* stream) {
+    return headSample(env, MRTS_LOGITS_F32, d_logits, d_masks, d_source, seed, step, d_actions, d_logprob, d_entropy, stream);
+}
+int mrts_policy_head_sample_typed_dev(mrts_env* env, int32_t logits_type, const void* d_logits, const uint8_t* d_masks,
+                                      const uint32_t* d_source, uint64_t seed, uint32_t step, int32_t* d_actions,
+                                      float* d_logprob, float* d_entropy, void* stream) {
+    return headSample(env, logits_type, d_logits, d_masks, d_source, seed, step, d_actions, d_logprob, d_entropy, stream);
+}
+
+int mrts_policy_head_score_dev(mrts_env* env, int32_t n_rows, const float* d_logits, const uint8_t* d_masks,
+                               const int32_t* d_actions, float* d_logprob, float* d_entropy, void* stream) {
+    return headScore(env, n_rows, MRTS_LOGITS_F32, d_logits, d_masks, d_actions, d_logprob, d_entropy, stream);
+}
+int mrts_policy_head_score_typed_dev(mrts_env* env, int32_t n_rows, int32_t logits_type, const void* d_logits,
+                                     const uint8_t* d_masks, const int32_t* d_actions, float* d_logprob, float* d_entropy,
+                                     void* stream) {
+    return headScore(env, n_rows, logits_type, d_logits, d_masks, d_actions, d_logprob, d_entropy, stream);
+}
+
+int mrts_policy_head_grad_dev(mrts_env* env, int32_t n_rows, const float* d_logits, const uint8_t* d_masks,
+                              const int32_t* d_actions, const float* d_g_logprob, const float* d_g_entropy,
+                              float* d_grad_logits, void* stream) {
+    return headGrad(env, n_rows, MRTS_LOGITS_F32, d_logits, d_masks, d_actions, d_g_logprob, d_g_entropy, d_grad_logits, stream);
+}
+int mrts_policy_head_grad_typed_dev(mrts_env* env, int32_t n_rows, int32_t logits_type, const void* d_logits,
+                                    const uint8_t* d_masks, const int32_t* d_actions, const float* d_g_logprob,
+                                    const float* d_g_entropy, void* d_grad_logits, void* stream) {
+    return headGrad(env, n_rows, logits_type, d_logits, d_masks, d_actions, d_g_logprob, d_g_entropy, d_grad_logits, stream);
 }
 
 namespace {
@@ -1307,16 +1349,19 @@ int mrts_policy_head_unpack_dev(mrts_env* env, int32_t n_rows, const uint32_t* d
     });
 }
 
-int mrts_policy_head_score_packed_dev(mrts_env* env, int32_t n_rows, const float* d_logits, const uint32_t* d_packed,
-                                      int32_t n_packed, int32_t cap, const int32_t* d_index, float* d_logprob,
-                                      float* d_entropy, void* stream) {
+namespace {
+// the two calls that score packed rows, for the float32 entry points and the typed ones alike
+int headScorePacked(mrts_env* env, int32_t n_rows, int32_t ltype, const void* d_logits, const uint32_t* d_packed,
+                    int32_t n_packed, int32_t cap, const int32_t* d_index, float* d_logprob, float* d_entropy, void* stream) {
     return guarded(env, [&] {
+        const uintptr_t lmask = headLogitAlign(ltype);
         HeadPackedParams P = headPackedParams(env, n_rows, cap);
         headPackedSource(P, d_packed, n_packed, d_index);
         if (!d_logits) throw Fail{-EINVAL, "null argument"};
-        if (((uintptr_t)d_logits & 3) || ((uintptr_t)d_logprob & 3) || ((uintptr_t)d_entropy & 3)) throw Fail{-EINVAL, "misaligned buffer"};
+        if (((uintptr_t)d_logits & lmask) || ((uintptr_t)d_logprob & 3) || ((uintptr_t)d_entropy & 3)) throw Fail{-EINVAL, "misaligned buffer"};
         HIPCHK(hipSetDevice(env->device));
         P.H.logits = d_logits;
+        P.H.ltype = ltype;
         P.H.logprob = d_logprob;
         P.H.entropy = d_entropy;
         HIPCHK(launchHeadPacked(HEAD_SCORE, P, pickStream(env, stream)));
@@ -1324,23 +1369,51 @@ int mrts_policy_head_score_packed_dev(mrts_env* env, int32_t n_rows, const float
     });
 }
 
-int mrts_policy_head_grad_packed_dev(mrts_env* env, int32_t n_rows, const float* d_logits, const uint32_t* d_packed,
-                                     int32_t n_packed, int32_t cap, const int32_t* d_index, const float* d_g_logprob,
-                                     const float* d_g_entropy, float* d_grad_logits, void* stream) {
+int headGradPacked(mrts_env* env, int32_t n_rows, int32_t ltype, const void* d_logits, const uint32_t* d_packed,
+                   int32_t n_packed, int32_t cap, const int32_t* d_index, const float* d_g_logprob, const float* d_g_entropy,
+                   void* d_grad_logits, void* stream) {
     return guarded(env, [&] {
+        const uintptr_t lmask = headLogitAlign(ltype);
         HeadPackedParams P = headPackedParams(env, n_rows, cap);
         headPackedSource(P, d_packed, n_packed, d_index);
         if (!d_logits || !d_grad_logits) throw Fail{-EINVAL, "null argument"};
-        if (((uintptr_t)d_logits & 3) || ((uintptr_t)d_g_logprob & 3) || ((uintptr_t)d_g_entropy & 3) || ((uintptr_t)d_grad_logits & 3))
+        if (((uintptr_t)d_logits & lmask) || ((uintptr_t)d_g_logprob & 3) || ((uintptr_t)d_g_entropy & 3) || ((uintptr_t)d_grad_logits & lmask))
             throw Fail{-EINVAL, "misaligned buffer"};
         HIPCHK(hipSetDevice(env->device));
         P.H.logits = d_logits;
+        P.H.ltype = ltype;
         P.H.g_logprob = d_g_logprob;
         P.H.g_entropy = d_g_entropy;
         P.H.grad = d_grad_logits;
         HIPCHK(launchHeadPacked(HEAD_GRAD, P, pickStream(env, stream)));
         return 0;
     });
+}
+}  // namespace
+
+int mrts_policy_head_score_packed_dev(mrts_env* env, int32_t n_rows, const float* d_logits, const uint32_t* d_packed,
+                                      int32_t n_packed, int32_t cap, const int32_t* d_index, float* d_logprob,
+                                      float* d_entropy, void* stream) {
+    return headScorePacked(env, n_rows, MRTS_LOGITS_F32, d_logits, d_packed, n_packed, cap, d_index, d_logprob, d_entropy, stream);
+}
+int mrts_policy_head_score_packed_typed_dev(mrts_env* env, int32_t n_rows, int32_t logits_type, const void* d_logits,
+                                            const uint32_t* d_packed, int32_t n_packed, int32_t cap, const int32_t* d_index,
+                                            float* d_logprob, float* d_entropy, void* stream) {
+    return headScorePacked(env, n_rows, logits_type, d_logits, d_packed, n_packed, cap, d_index, d_logprob, d_entropy, stream);
+}
+
+int mrts_policy_head_grad_packed_dev(mrts_env* env, int32_t n_rows, const float* d_logits, const uint32_t* d_packed,
+                                     int32_t n_packed, int32_t cap, const int32_t* d_index, const float* d_g_logprob,
+                                     const float* d_g_entropy, float* d_grad_logits, void* stream) {
+    return headGradPacked(env, n_rows, MRTS_LOGITS_F32, d_logits, d_packed, n_packed, cap, d_index, d_g_logprob, d_g_entropy,
+                          d_grad_logits, stream);
+}
+int mrts_policy_head_grad_packed_typed_dev(mrts_env* env, int32_t n_rows, int32_t logits_type, const void* d_logits,
+                                           const uint32_t* d_packed, int32_t n_packed, int32_t cap, const int32_t* d_index,
+                                           const float* d_g_logprob, const float* d_g_entropy, void* d_grad_logits,
+                                           void* stream) {
+    return headGradPacked(env, n_rows, logits_type, d_logits, d_packed, n_packed, cap, d_index, d_g_logprob, d_g_entropy,
+                          d_grad_logits, stream);
 }
 
 // ---- packed observation rows (include/mrts.h; the argument checks are mrts_hostdata.cpp's)

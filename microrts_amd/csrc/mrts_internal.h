@@ -261,11 +261,15 @@ struct PolicyParams {
 // `actions` (source optional: the candidate bits), SCORE reads them, GRAD writes `grad` [n_rows][HW][K-1].
 enum : int32_t { HEAD_SAMPLE = 0, HEAD_SCORE = 1, HEAD_GRAD = 2, HEAD_PACK = 3, HEAD_UNPACK = 4 };
 constexpr int HEAD_MAX_LOGITS = 80;  // K - 1 of the largest table create accepts (8 types, attack range 3)
+// the logits' element type, MRTS_LOGITS_* of include/mrts.h (mrts_host.cpp holds the two lists together): float32,
+// or bfloat16 / float16 converted to fp32 exactly at the load, the gradient rounded once (to nearest even) at its store
+enum : int32_t { HEAD_LT_F32 = 0, HEAD_LT_BF16 = 1, HEAD_LT_F16 = 2 };
+constexpr int headLogitBytes(int ltype) { return ltype == HEAD_LT_F32 ? 4 : 2; }
 struct HeadParams {
     int32_t HW, K, ntypes, n_rows;
     uint32_t slot_id_base, step;
     uint64_t seed;
-    const float* logits;           // [n_rows][HW][K-1]
+    const void* logits;            // [n_rows][HW][K-1], elements of ltype
     const uint8_t* masks;          // [n_rows][HW][K]
     const uint32_t* source;        // SAMPLE, optional: [n_rows][maskWords(HW)] candidate bits
     int32_t* actions;              // [n_rows][HW][7]: written by SAMPLE, read by SCORE / GRAD
@@ -273,7 +277,8 @@ struct HeadParams {
     float* entropy;                // SAMPLE / SCORE, optional: [n_rows]
     const float* g_logprob;        // GRAD, optional (zeros): [n_rows]
     const float* g_entropy;        // GRAD, optional (zeros): [n_rows]
-    float* grad;                   // GRAD: [n_rows][HW][K-1], every element written
+    void* grad;                    // GRAD: [n_rows][HW][K-1], elements of ltype, every element written
+    int32_t ltype;                 // HEAD_LT_*: the element type of logits and grad (the launchers pick the instance)
 };
 
 // The packed rollout row (include/mrts.h, "Packed policy rows"): word 0 the candidate count, then per candidate

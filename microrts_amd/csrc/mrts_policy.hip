@@ -3,6 +3,8 @@
 #include <hip/hip_runtime.h>
 #include <stdint.h>
 
+#include <type_traits>
+
 #define MRTS_UNIT 1
 #include "mrts_device.h"
 
@@ -202,6 +204,49 @@ __global__ __launch_bounds__(64) void k_policy(PolicyParams Q) {
 // and running sum are DPP operations inside it.
 constexpr uint32_t HEAD_TAG = 0x48454144u;  // "HEAD": Philox counter word 3 (and HEAD_TAG + 1), apart from 0 / UNIFORM_TAG
 
+// The logits' element type E (HEAD_LT_*): float, or one of the two 16-bit types.  A 16-bit logit becomes fp32 exactly at
+// its load (a 16-bit load: with an odd K - 1 a cell's row is only 2-byte aligned) and every step after that is the
+// float instance's; a gradient element is the float instance's value rounded once, to nearest even, at its LDS store.
+struct Bf16 {
+    uint16_t v;
+};
+struct F16 {
+    _Float16 v;
+};
+DEV float headLoad(const float* p, int j) { return p[j]; }
+DEV float headLoad(const Bf16* p, int j) { return __uint_as_float((uint32_t)p[j].v << 16); }
+// v_cvt_f32_f16: exact, subnormals included (fp16 denormals are on in the default float mode, and this unit is
+// compiled with it)
+DEV float headLoad(const F16* p, int j) { return (float)p[j].v; }
+DEV void headStore(float* p, float v) { *p = v; }
+// integer round to nearest even, a NaN to the quiet NaN: what torch's float -> bfloat16 cast does
+DEV void headStore(Bf16* p, float v) {
+    const uint32_t u = __float_as_uint(v);
+    p->v = v != v ? (uint16_t)0x7FC0u : (uint16_t)((u + 0x7FFFu + ((u >> 16) & 1u)) >> 16);
+}
+DEV void headStore(F16* p, float v) { p->v = (_Float16)v; }  // v_cvt_f16_f32 in the default mode: nearest even, subnormals kept
+template <typename E>
+DEV E headNaN();
+template <>
+DEV float headNaN<float>() { return __int_as_float(0x7FC00000); }
+template <>
+DEV Bf16 headNaN<Bf16>() { return Bf16{(uint16_t)0x7FC0u}; }
+template <>
+DEV F16 headNaN<F16>() { return F16{__builtin_bit_cast(_Float16, (uint16_t)0x7E00u)}; }
+// what a chunk of E leaves through (headFlush): words for float, halfwords for the 16-bit types
+template <typename E>
+struct HeadOut {
+    using T = int32_t;
+    static constexpr int LG = 2;  // log2 of the elements per 16-byte vector
+};
+template <>
+struct HeadOut<Bf16> {
+    using T = uint16_t;
+    static constexpr int LG = 3;
+};
+template <>
+struct HeadOut<F16> : HeadOut<Bf16> {};
+
 template <int CTRL, int ROWS = 0xF>
 DEV float dppF(float old, float v) {
     return __int_as_float(__builtin_amdgcn_update_dpp(__float_as_int(old), __float_as_int(v), CTRL, ROWS, 0xF, false));
@@ -270,14 +315,15 @@ DEV double waveSumD(double v) {
     return __longlong_as_double((long long)(((uint64_t)hi << 32) | lo));
 }
 
-// one candidate cell as its 16-lane row sees it
+// one candidate cell as its 16-lane row sees it (E: the logits' element type)
+template <typename E>
 struct HeadCell {
     bool act;             // the row has a cell this round
-    const float* lrow;    // its K-1 logits
+    const E* lrow;        // its K-1 logits
     const uint8_t* mrec;  // its K mask bytes
     const int32_t* arow;  // SCORE / GRAD: its given action row
     int32_t* srow;        // SAMPLE: its action row in LDS (zeroed)
-    float* grow;          // GRAD: its gradient row in LDS (zeroed)
+    E* grow;              // GRAD: its gradient row in LDS (zeroed)
     float glp, gent;      // GRAD: the row's upstream gradients
     double lp, ent;       // per-lane partial sums of the row's log-probability and entropy (fp32 terms)
     uint32_t w0, wd, w5, w6;  // SAMPLE: the Philox words of the lane's fields (type, its direction field, produce type, attack)
@@ -285,8 +331,8 @@ struct HeadCell {
 
 // One field, NE logits per lane (l / set: the lane's logits and mask bits, 0 / false outside the field), the field
 // spanning a W-lane segment.  idx0: the field-local index of l[0]; a: the given component (SCORE / GRAD).
-template <int MODE, int NE, int W>
-DEV void headField(HeadCell& X, int lane, const float* l, const bool* set, int j0, int idx0, int field, uint32_t word, int a) {
+template <int MODE, int NE, int W, typename E>
+DEV void headField(HeadCell<E>& X, int lane, const float* l, const bool* set, int j0, int idx0, int field, uint32_t word, int a) {
 #pragma clang fp contract(off)
     const int ql = lane & (W - 1), segbase = lane - ql;
     const uint32_t segmask = (1u << W) - 1u;
@@ -365,14 +411,14 @@ DEV void headField(HeadCell& X, int lane, const float* l, const bool* set, int j
                     const float p = e[k] / S, logp = (l[k] - mx) - logS;
                     float gv = X.gent * (-p * (logp + H));
                     if (hasA) gv += X.glp * ((match[k] ? 1.f : 0.f) - p);
-                    X.grow[j0 + k] = gv;
+                    headStore(X.grow + j0 + k, gv);
                 }
         }
     }
 }
 
-template <int MODE>
-DEV void headCell(HeadCell& X, const HeadParams& Q, int lane) {
+template <int MODE, typename E>
+DEV void headCell(HeadCell<E>& X, const HeadParams& Q, int lane) {
     const int q = lane & 15, nt = Q.ntypes, natt = Q.K - 23 - nt;
     // the lane's seven logits: 0 type, 1 a direction (quad = field), 2 produce type, 3..6 attack window 4q..4q+3
     int j[7];
@@ -391,7 +437,7 @@ DEV void headCell(HeadCell& X, const HeadParams& Q, int lane) {
     for (int i = 0; i < 7; i++) {
         const int jj = in[i] ? j[i] : 0;
         const uint32_t mb = X.mrec[1 + jj];
-        const float lv = X.lrow[jj];
+        const float lv = headLoad(X.lrow, jj);
         set[i] = X.act && in[i] && mb != 0;
         l[i] = set[i] ? lv : 0.f;
     }
@@ -408,15 +454,19 @@ DEV void headCell(HeadCell& X, const HeadParams& Q, int lane) {
 // compose the chunk's action / gradient rows in zeroed LDS and store them with dwordx4, a chunk without a
 // candidate as plain zero stores.  The row's log-probability and entropy are per-lane partial sums added up by one
 // DPP chain at the end: a fixed order, no atomics.
-template <int MODE>
+template <int MODE, typename E>
 __global__ __launch_bounds__(64) void k_head(HeadParams Q) {
-    __shared__ __align__(16) int32_t sbuf[(MODE == HEAD_GRAD ? 64 * HEAD_MAX_LOGITS : MODE == HEAD_SAMPLE ? 64 * 7 : 0) + 8];
+    // what this mode writes: action rows as words, gradient rows as elements of E (words for float); LG: log2 of the
+    // elements per 16-byte vector
+    using O = typename std::conditional<MODE == HEAD_GRAD, typename HeadOut<E>::T, int32_t>::type;
+    constexpr int LG = MODE == HEAD_GRAD ? HeadOut<E>::LG : 2;
+    __shared__ __align__(16) int32_t sbuf[(MODE == HEAD_GRAD ? 64 * HEAD_MAX_LOGITS * (int)sizeof(O) / 4 : MODE == HEAD_SAMPLE ? 64 * 7 : 0) + 8];
     const int lane = (int)threadIdx.x, row = (int)blockIdx.x, KL = Q.K - 1;
-    const int RW = MODE == HEAD_GRAD ? KL : 7;  // words per cell of what this mode writes
+    const int RW = MODE == HEAD_GRAD ? KL : 7;  // elements per cell of what this mode writes
     const size_t cell0 = (size_t)row * Q.HW;
     const uint32_t* src = (MODE == HEAD_SAMPLE && Q.source) ? Q.source + (size_t)row * ((Q.HW + 31) / 32) : nullptr;
-    int32_t* out = MODE == HEAD_GRAD ? (int32_t*)Q.grad : Q.actions;
-    HeadCell X;
+    O* out = MODE == HEAD_GRAD ? (O*)Q.grad : (O*)Q.actions;
+    HeadCell<E> X;
     X.lp = X.ent = 0.0;
     X.glp = X.gent = 0.f;
     if (MODE == HEAD_GRAD) {
@@ -428,18 +478,18 @@ __global__ __launch_bounds__(64) void k_head(HeadParams Q) {
         bool cand = false;
         if (c < Q.HW) cand = src ? ((src[c >> 5] >> (c & 31)) & 1u) != 0 : Q.masks[(cell0 + c) * Q.K] != 0;
         uint64_t m = ballot(cand);
-        int32_t* gp = nullptr;
+        O* gp = nullptr;
         int a = 0, nw = 0;
         if (MODE != HEAD_SCORE) {
-            int32_t* p = out + (cell0 + c0) * RW;
-            a = (int)(((uintptr_t)p >> 2) & 3);
+            O* p = out + (cell0 + c0) * RW;
+            a = (int)(((uintptr_t)p / sizeof(O)) & ((1 << LG) - 1));
             gp = p - a;
             nw = ncell * RW;
             if (m == 0) {
-                headFlush(nullptr, gp, a, nw, lane);
+                headFlush((const O*)nullptr, gp, a, nw, lane);
                 continue;
             }
-            for (int v = lane; v < ((a + nw + 3) >> 2); v += 64) ((int4*)sbuf)[v] = make_int4(0, 0, 0, 0);
+            for (int v = lane; v < ((a + nw + (1 << LG) - 1) >> LG); v += 64) ((int4*)sbuf)[v] = make_int4(0, 0, 0, 0);
             __syncthreads();
         } else if (m == 0) {
             continue;
@@ -455,11 +505,11 @@ __global__ __launch_bounds__(64) void k_head(HeadParams Q) {
                 }
             X.act = cl >= 0;
             const size_t cell = cell0 + c0 + (cl >= 0 ? cl : 0);
-            X.lrow = Q.logits + cell * KL;
+            X.lrow = (const E*)Q.logits + cell * KL;
             X.mrec = Q.masks + cell * Q.K;
             X.arow = Q.actions + cell * 7;
             X.srow = sbuf + a + (cl >= 0 ? cl : 0) * 7;
-            X.grow = (float*)sbuf + a + (cl >= 0 ? cl : 0) * KL;
+            X.grow = (E*)sbuf + a + (cl >= 0 ? cl : 0) * KL;
             if (MODE == HEAD_SAMPLE) {
                 const uint32_t sid = Q.slot_id_base + (uint32_t)row, cc = (uint32_t)(c0 + (cl >= 0 ? cl : 0));
                 uint32_t c1[4] = {sid, Q.step, cc, HEAD_TAG}, c2[4] = {sid, Q.step, cc, HEAD_TAG + 1u};
@@ -477,7 +527,7 @@ __global__ __launch_bounds__(64) void k_head(HeadParams Q) {
         }
         if (MODE != HEAD_SCORE) {
             __syncthreads();
-            headFlush(sbuf, gp, a, nw, lane);
+            headFlush((const O*)sbuf, gp, a, nw, lane);
             __syncthreads();
         }
     }
@@ -637,10 +687,12 @@ __global__ __launch_bounds__(64) void k_head_unpack(HeadPackedParams P) {
 // LDS, where headCell reads them as it reads the dense tensors.  The count and the candidate words are read at
 // wave-uniform addresses inside the row (clamped to cap), so the first round's words load with the count.  A row
 // whose count exceeds cap, or whose index is outside the packed rows, is NaN: logprob, entropy, gradient row.
-template <int MODE>
+template <int MODE, typename E>
 __global__ __launch_bounds__(64) void k_head_packed(HeadPackedParams P) {
+    using O = typename HeadOut<E>::T;  // the gradient rows' elements, as k_head stores them
+    constexpr int LG = HeadOut<E>::LG;
     constexpr int XW = (HEAD_MAX_LOGITS + 1 + 3) / 4 + 7;  // per DPP row: the mask bytes, then the action row
-    __shared__ __align__(16) int32_t sbuf[(MODE == HEAD_GRAD ? 64 * HEAD_MAX_LOGITS : 0) + 8];
+    __shared__ __align__(16) int32_t sbuf[(MODE == HEAD_GRAD ? 64 * HEAD_MAX_LOGITS * (int)sizeof(O) / 4 : 0) + 8];
     __shared__ __align__(16) uint32_t sexp[4 * XW];
     const HeadParams& Q = P.H;
     const int lane = (int)threadIdx.x, row = (int)blockIdx.x, KL = Q.K - 1, g = lane >> 4, q = lane & 15;
@@ -652,14 +704,14 @@ __global__ __launch_bounds__(64) void k_head_packed(HeadPackedParams P) {
     if (!ok || n > (uint32_t)P.cap) {
         const float nan = __int_as_float(0x7FC00000);
         if (MODE == HEAD_GRAD) {
-            for (size_t t = lane; t < (size_t)Q.HW * KL; t += 64) Q.grad[cell0 * KL + t] = nan;
+            for (size_t t = lane; t < (size_t)Q.HW * KL; t += 64) ((E*)Q.grad)[cell0 * KL + t] = headNaN<E>();
         } else if (lane == 0) {
             if (Q.logprob) Q.logprob[row] = nan;
             if (Q.entropy) Q.entropy[row] = nan;
         }
         return;
     }
-    HeadCell X;
+    HeadCell<E> X;
     X.lp = X.ent = 0.0;
     X.glp = X.gent = 0.f;
     X.srow = nullptr;
@@ -672,18 +724,18 @@ __global__ __launch_bounds__(64) void k_head_packed(HeadPackedParams P) {
     for (int c0 = 0; c0 < Q.HW; c0 += 64) {
         const uint32_t chunk = (uint32_t)(c0 >> 6);
         const bool has = i0 < n && (cc >> 6) == chunk;
-        int32_t* gp = nullptr;
+        O* gp = nullptr;
         int a = 0, nw = 0;
         if (MODE == HEAD_GRAD) {
-            int32_t* p = (int32_t*)Q.grad + (cell0 + c0) * KL;
-            a = (int)(((uintptr_t)p >> 2) & 3);
+            O* p = (O*)Q.grad + (cell0 + c0) * KL;
+            a = (int)(((uintptr_t)p / sizeof(O)) & ((1 << LG) - 1));
             gp = p - a;
             nw = min(64, Q.HW - c0) * KL;
             if (!has) {
-                headFlush(nullptr, gp, a, nw, lane);
+                headFlush((const O*)nullptr, gp, a, nw, lane);
                 continue;
             }
-            for (int v = lane; v < ((a + nw + 3) >> 2); v += 64) ((int4*)sbuf)[v] = make_int4(0, 0, 0, 0);
+            for (int v = lane; v < ((a + nw + (1 << LG) - 1) >> LG); v += 64) ((int4*)sbuf)[v] = make_int4(0, 0, 0, 0);
         } else if (!has) {
             if (i0 >= n) break;
             continue;
@@ -704,17 +756,17 @@ __global__ __launch_bounds__(64) void k_head_packed(HeadPackedParams P) {
             for (int w = q; w < (Q.K + 3) / 4; w += 16) xr[w] = headSpread4(headBits4(b0, b1, b2, w));
             if (q < 7) xr[XW - 7 + q] = (uint32_t)headActComp(aw, q);
             __syncthreads();
-            X.lrow = Q.logits + (cell0 + cs) * KL;
+            X.lrow = (const E*)Q.logits + (cell0 + cs) * KL;
             X.mrec = (const uint8_t*)xr;
             X.arow = (const int32_t*)(xr + XW - 7);
-            X.grow = (float*)sbuf + a + (cs & 63u) * KL;
+            X.grow = (E*)sbuf + a + (cs & 63u) * KL;
             headCell<MODE>(X, Q, lane);
             i0 += take;
             cc = take == 1 ? cl[1] : take == 2 ? cl[2] : take == 3 ? cl[3] : cl[4];
         }
         if (MODE == HEAD_GRAD) {
             __syncthreads();
-            headFlush(sbuf, gp, a, nw, lane);
+            headFlush((const O*)sbuf, gp, a, nw, lane);
             __syncthreads();
         }
     }
@@ -725,6 +777,18 @@ __global__ __launch_bounds__(64) void k_head_packed(HeadPackedParams P) {
             if (Q.entropy) Q.entropy[row] = ent;
         }
     }
+}
+// the instances of one element type (the host checked ltype)
+template <typename E>
+void headLaunch(int mode, const HeadParams& Q, dim3 grid, dim3 block, hipStream_t stream) {
+    if (mode == HEAD_SAMPLE) hipLaunchKernelGGL((k_head<HEAD_SAMPLE, E>), grid, block, 0, stream, Q);
+    else if (mode == HEAD_SCORE) hipLaunchKernelGGL((k_head<HEAD_SCORE, E>), grid, block, 0, stream, Q);
+    else hipLaunchKernelGGL((k_head<HEAD_GRAD, E>), grid, block, 0, stream, Q);
+}
+template <typename E>
+void headPackedLaunch(int mode, const HeadPackedParams& P, dim3 grid, dim3 block, hipStream_t stream) {
+    if (mode == HEAD_SCORE) hipLaunchKernelGGL((k_head_packed<HEAD_SCORE, E>), grid, block, 0, stream, P);
+    else hipLaunchKernelGGL((k_head_packed<HEAD_GRAD, E>), grid, block, 0, stream, P);
 }
 }  // namespace
 
@@ -770,9 +834,9 @@ hipError_t launchPolicy(const PolicyParams& Q, hipStream_t stream, bool* prevWri
 hipError_t launchHead(int mode, const HeadParams& Q, hipStream_t stream) {
     if (Q.n_rows <= 0) return hipSuccess;
     const dim3 grid((unsigned)Q.n_rows), block(64);
-    if (mode == HEAD_SAMPLE) hipLaunchKernelGGL(k_head<HEAD_SAMPLE>, grid, block, 0, stream, Q);
-    else if (mode == HEAD_SCORE) hipLaunchKernelGGL(k_head<HEAD_SCORE>, grid, block, 0, stream, Q);
-    else hipLaunchKernelGGL(k_head<HEAD_GRAD>, grid, block, 0, stream, Q);
+    if (Q.ltype == HEAD_LT_F32) headLaunch<float>(mode, Q, grid, block, stream);
+    else if (Q.ltype == HEAD_LT_BF16) headLaunch<Bf16>(mode, Q, grid, block, stream);
+    else headLaunch<F16>(mode, Q, grid, block, stream);
     return hipGetLastError();
 }
 
@@ -782,8 +846,9 @@ hipError_t launchHeadPacked(int mode, const HeadPackedParams& P, hipStream_t str
     const dim3 grid((unsigned)P.H.n_rows), block(64);
     if (mode == HEAD_PACK) hipLaunchKernelGGL(k_head_pack, grid, block, 0, stream, P);
     else if (mode == HEAD_UNPACK) hipLaunchKernelGGL(k_head_unpack, grid, block, 0, stream, P);
-    else if (mode == HEAD_SCORE) hipLaunchKernelGGL(k_head_packed<HEAD_SCORE>, grid, block, 0, stream, P);
-    else hipLaunchKernelGGL(k_head_packed<HEAD_GRAD>, grid, block, 0, stream, P);
+    else if (P.H.ltype == HEAD_LT_F32) headPackedLaunch<float>(mode, P, grid, block, stream);
+    else if (P.H.ltype == HEAD_LT_BF16) headPackedLaunch<Bf16>(mode, P, grid, block, stream);
+    else headPackedLaunch<F16>(mode, P, grid, block, stream);
     return hipGetLastError();
 }
 }  // namespace mrts

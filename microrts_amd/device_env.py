@@ -352,7 +352,7 @@ class DeviceVecEnv(DeviceHandle):
 
     def sample_actions(self, logits, seed, step, out=None, stream=None):
         """The masked policy head (mrts_policy_head_sample_dev; policy_head.py): action rows drawn from `logits`
-        (float32 [slots][H*W][K-1]) under env.masks, the candidate cells taken from env.source when it exists.
+        (float32, bfloat16 or float16 [slots][H*W][K-1]; 16-bit logits draw what `logits.float()` draws) under env.masks, the candidate cells taken from env.source when it exists.
         Returns (actions, logprob, entropy): `out` (default env.actions, every row written) and float32 [slots]
         sums over each slot's candidate cells.  Philox counters (slot id, step, cell): the same seed, step and
         logits give the same rows."""
@@ -363,8 +363,14 @@ class DeviceVecEnv(DeviceHandle):
         policy_head.check_head_args(self, logits, self.masks, out, n=h.S, actions_name="out")
         logprob = T.empty(h.S, dtype=T.float32, device=self.device)
         entropy = T.empty(h.S, dtype=T.float32, device=self.device)
-        _lib.check(h.L.mrts_policy_head_sample_dev(h.h, self._p(logits), self._p(self.masks), self._p(self.source), seed, step,
-                                                   self._p(out), self._p(logprob), self._p(entropy), self._s(stream)))
+        lt = policy_head.logits_type(logits)
+        if lt == _lib.MRTS_LOGITS_F32:
+            _lib.check(h.L.mrts_policy_head_sample_dev(h.h, self._p(logits), self._p(self.masks), self._p(self.source), seed,
+                                                       step, self._p(out), self._p(logprob), self._p(entropy), self._s(stream)))
+        else:
+            _lib.check(h.L.mrts_policy_head_sample_typed_dev(h.h, lt, self._p(logits), self._p(self.masks), self._p(self.source),
+                                                             seed, step, self._p(out), self._p(logprob), self._p(entropy),
+                                                             self._s(stream)))
         # the library dropped its delta bases (as mrts_policy_invalidate): no tensor holds a tracked policy output
         self._policy_stamp(None)
         return out, logprob, entropy

@@ -12,9 +12,31 @@ from . import _lib
 from ._packed import PackedLayout, check_rows, check_tensor, ptr as _p
 
 
+def logits_type(logits):
+    """The MRTS_LOGITS_* code of a logits tensor: float32 0, bfloat16 1, float16 2; None for any other dtype.  A
+    16-bit tensor goes through the typed entry points (mrts_policy_head_*_typed_dev): its logits are converted to
+    fp32 exactly as they are loaded, the forward outputs are those of `logits.float()`, and the gradient comes back
+    in the logits' dtype, rounded once from the float32 value."""
+    import torch
+
+    return {torch.float32: _lib.MRTS_LOGITS_F32, torch.bfloat16: _lib.MRTS_LOGITS_BF16,
+            torch.float16: _lib.MRTS_LOGITS_F16}.get(getattr(logits, "dtype", None))
+
+
+def check_logits(env, logits, rows):
+    """logits: float32, bfloat16 or float16 [rows][H*W][K-1], contiguous on the env's device (any other dtype is
+    refused as not float32)"""
+    import torch
+
+    _, H, W, _, K = env.dims
+    dtype = logits.dtype if logits_type(logits) is not None else torch.float32
+    check_tensor("logits", logits, dtype, [(rows, H * W, K - 1)], env.device)
+
+
 def check_head_args(env, logits, masks, actions, n=None, actions_name="actions"):
-    """The argument checks of the head's calls (no GPU call): logits float32 [n][H*W][K-1], masks uint8
-    [n][H][W][K] (or [n][H*W][K]), actions int32 [n][H*W][7], all contiguous on the env's device.  Returns n."""
+    """The argument checks of the head's calls (no GPU call): logits float32, bfloat16 or float16 [n][H*W][K-1],
+    masks uint8 [n][H][W][K] (or [n][H*W][K]), actions int32 [n][H*W][7], all contiguous on the env's device.
+    Returns n."""
     import torch
 
     _, H, W, _, K = env.dims
@@ -22,7 +44,7 @@ def check_head_args(env, logits, masks, actions, n=None, actions_name="actions")
         if not isinstance(logits, torch.Tensor) or logits.dim() != 3:
             raise ValueError("logits: expected a float32 tensor [rows][H*W][K-1]")
         n = logits.shape[0]
-    check_tensor("logits", logits, torch.float32, [(n, H * W, K - 1)], env.device)
+    check_logits(env, logits, n)
     check_tensor("masks", masks, torch.uint8, [(n, H, W, K), (n, H * W, K)], env.device)
     check_tensor(actions_name, actions, torch.int32, [(n, H * W, 7)], env.device)
     check_rows(env, "logits", n)
@@ -38,9 +60,13 @@ def _evaluate_fn():
             n = logits.shape[0]
             logprob = torch.empty(n, dtype=torch.float32, device=logits.device)
             entropy = torch.empty(n, dtype=torch.float32, device=logits.device)
-            h = env._h
-            _lib.check(h.L.mrts_policy_head_score_dev(h.h, n, _p(logits), _p(masks), _p(actions), _p(logprob), _p(entropy),
-                                                      env._s(None)))
+            h, lt = env._h, logits_type(logits)
+            if lt == _lib.MRTS_LOGITS_F32:
+                _lib.check(h.L.mrts_policy_head_score_dev(h.h, n, _p(logits), _p(masks), _p(actions), _p(logprob), _p(entropy),
+                                                          env._s(None)))
+            else:
+                _lib.check(h.L.mrts_policy_head_score_typed_dev(h.h, n, lt, _p(logits), _p(masks), _p(actions), _p(logprob),
+                                                                _p(entropy), env._s(None)))
             ctx.save_for_backward(logits, masks, actions)
             ctx.env = env
             ctx.set_materialize_grads(False)
@@ -52,10 +78,14 @@ def _evaluate_fn():
             if not ctx.needs_input_grad[0]:
                 return None, None, None, None
             g = [None if t is None else t.to(torch.float32).contiguous() for t in (g_logprob, g_entropy)]
-            grad = torch.empty_like(logits)
-            h = ctx.env._h
-            _lib.check(h.L.mrts_policy_head_grad_dev(h.h, logits.shape[0], _p(logits), _p(masks), _p(actions), _p(g[0]),
-                                                     _p(g[1]), _p(grad), ctx.env._s(None)))
+            grad = torch.empty_like(logits)  # the logits' dtype: the kernel writes it, no float32 intermediate
+            h, lt = ctx.env._h, logits_type(logits)
+            if lt == _lib.MRTS_LOGITS_F32:
+                _lib.check(h.L.mrts_policy_head_grad_dev(h.h, logits.shape[0], _p(logits), _p(masks), _p(actions), _p(g[0]),
+                                                         _p(g[1]), _p(grad), ctx.env._s(None)))
+            else:
+                _lib.check(h.L.mrts_policy_head_grad_typed_dev(h.h, logits.shape[0], lt, _p(logits), _p(masks), _p(actions),
+                                                               _p(g[0]), _p(g[1]), _p(grad), ctx.env._s(None)))
             return grad, None, None, None
 
     return EvaluateActions
@@ -66,8 +96,9 @@ _EVALUATE = None
 
 def evaluate_actions(env, logits, masks, actions):
     """(logprob, entropy), float32 [rows] each, of the given action rows under the masked categoricals of
-    `logits` — differentiable in `logits` (the backward is one mrts_policy_head_grad_dev launch on the current
-    stream).  rows is free: an update minibatch is T x slots rows.  env: the DeviceVecEnv whose map and unit-type
+    `logits` (float32, bfloat16 or float16 [rows][H*W][K-1]) — differentiable in `logits` (the backward is one
+    mrts_policy_head_grad_dev launch on the current stream).  16-bit logits give the bytes of `logits.float()` and
+    get their gradient in their own dtype, the float32 gradient rounded once (mrts_policy_head_*_typed_dev).  rows is free: an update minibatch is T x slots rows.  env: the DeviceVecEnv whose map and unit-type
     table fix H*W, K and the fields.  A component off its field's mask gives logprob -inf."""
     global _EVALUATE
     check_head_args(env, logits, masks, actions)
@@ -122,9 +153,13 @@ def _evaluate_packed_fn():
             n = logits.shape[0]
             logprob = torch.empty(n, dtype=torch.float32, device=logits.device)
             entropy = torch.empty(n, dtype=torch.float32, device=logits.device)
-            h = env._h
-            _lib.check(h.L.mrts_policy_head_score_packed_dev(h.h, n, _p(logits), _p(packed), n_packed, cap, _p(index),
-                                                             _p(logprob), _p(entropy), env._s(None)))
+            h, lt = env._h, logits_type(logits)
+            if lt == _lib.MRTS_LOGITS_F32:
+                _lib.check(h.L.mrts_policy_head_score_packed_dev(h.h, n, _p(logits), _p(packed), n_packed, cap, _p(index),
+                                                                 _p(logprob), _p(entropy), env._s(None)))
+            else:
+                _lib.check(h.L.mrts_policy_head_score_packed_typed_dev(h.h, n, lt, _p(logits), _p(packed), n_packed, cap,
+                                                                       _p(index), _p(logprob), _p(entropy), env._s(None)))
             ctx.save_for_backward(logits, packed, index)
             ctx.env, ctx.n_packed, ctx.cap = env, n_packed, cap
             ctx.set_materialize_grads(False)
@@ -136,10 +171,16 @@ def _evaluate_packed_fn():
             if not ctx.needs_input_grad[0]:
                 return None, None, None, None, None, None
             g = [None if t is None else t.to(torch.float32).contiguous() for t in (g_logprob, g_entropy)]
-            grad = torch.empty_like(logits)
-            h = ctx.env._h
-            _lib.check(h.L.mrts_policy_head_grad_packed_dev(h.h, logits.shape[0], _p(logits), _p(packed), ctx.n_packed, ctx.cap,
-                                                            _p(index), _p(g[0]), _p(g[1]), _p(grad), ctx.env._s(None)))
+            grad = torch.empty_like(logits)  # the logits' dtype, written by the kernel
+            h, lt = ctx.env._h, logits_type(logits)
+            if lt == _lib.MRTS_LOGITS_F32:
+                _lib.check(h.L.mrts_policy_head_grad_packed_dev(h.h, logits.shape[0], _p(logits), _p(packed), ctx.n_packed,
+                                                                ctx.cap, _p(index), _p(g[0]), _p(g[1]), _p(grad),
+                                                                ctx.env._s(None)))
+            else:
+                _lib.check(h.L.mrts_policy_head_grad_packed_typed_dev(h.h, logits.shape[0], lt, _p(logits), _p(packed),
+                                                                      ctx.n_packed, ctx.cap, _p(index), _p(g[0]), _p(g[1]),
+                                                                      _p(grad), ctx.env._s(None)))
             return grad, None, None, None, None, None
 
     return EvaluateActionsPacked
@@ -151,19 +192,19 @@ _EVALUATE_PACKED = None
 def evaluate_actions_packed(env, logits, packed, index=None):
     """evaluate_actions on packed rows (DeviceVecEnv.pack_step): (logprob, entropy), float32 [rows], byte for byte
     what evaluate_actions gives on the dense masks and action rows that were packed, differentiable in `logits`
-    (float32 [rows][H*W][K-1]; the backward is one launch and writes the dense gradient).  packed: uint32
-    [N][words], or any leading shape (a [T][slots][words] rollout buffer), flattened.  Row r is scored against
+    (float32, bfloat16 or float16 [rows][H*W][K-1]; the backward is one launch and writes the dense gradient, in the
+    logits' dtype).  packed: uint32 [N][words], or any leading shape (a [T][slots][words] rollout buffer), flattened.
+    Row r is scored against
     packed row index[r] (int32 [rows] on the device, repeats allowed: a minibatch needs no copy), or against packed
     row r without an index (then N = rows).  A packed row that overflowed its cap (DeviceVecEnv.pack_overflow) and
     an index outside [0, N) give NaN for that row only."""
     global _EVALUATE_PACKED
     import torch
 
-    _, H, W, _, K = env.dims
     if not isinstance(logits, torch.Tensor) or logits.dim() != 3:
         raise ValueError("logits: expected a float32 tensor [rows][H*W][K-1]")
     rows = logits.shape[0]
-    check_tensor("logits", logits, torch.float32, [(rows, H * W, K - 1)], env.device)
+    check_logits(env, logits, rows)
     n_packed, cap = check_packed_args(env, packed, index, rows)
     if _EVALUATE_PACKED is None:
         _EVALUATE_PACKED = _evaluate_packed_fn()

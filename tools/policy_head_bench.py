@@ -24,7 +24,17 @@ timed once more with the two launches alone (score, gradient; the C entry points
 of the loss do not bound the figure.  The packed results are
 checked to equal the dense ones byte for byte.  Also the bytes per step a rollout keeps in either form.
 
+--dtype bfloat16 / float16 gives the kernels' legs (dense and --packed) the logits in that type: the
+typed entry points, the gradient written in the type.  The built-in check is then bit equality: action rows,
+log-probability and entropy equal the float32 entry points' on logits.float() as int32, the gradient equals their
+gradient cast to the type as int16; the PyTorch head (float32, on logits.float()) stays the baseline and is still
+checked against the float32 entry points.  --cast-from bfloat16 / float16 (with --dtype float32) is what a learner pays
+without that: the network's logits are 16-bit, and every timed kernel leg includes logits.float() and, in the update,
+autograd's cast of the float32 gradient back.  The same 16-bit values feed both, so a --cast-from run of one library
+and a --dtype run of another compare like for like.
+
 Usage (GPU box): python tools/policy_head_bench.py [--slots 4096] [--rollout 1000] [--repeats 20] [--packed]
+                 [--dtype float32|bfloat16|float16] [--cast-from bfloat16|float16]
 Prints one JSON line.
 """
 import argparse
@@ -113,8 +123,9 @@ def sectors(np, starts, length):
     return int(np.unique(s).size)
 
 
-def packed_leg(torch, env, evaluate_actions, evaluate_actions_packed, a, logits, masks, acts, g_lp, g_ent, k_update, lk):
-    """the --packed figures; env.actions holds `acts` (sample_actions wrote them) and env.source the masks' bits"""
+def packed_leg(torch, env, evaluate_actions, evaluate_actions_packed, a, logits, masks, acts, g_lp, g_ent, k_update, lk, feed):
+    """the --packed figures; env.actions holds `acts` (sample_actions wrote them) and env.source the masks' bits.
+    logits: the network's; feed(logits): what the kernels get (the cast of --cast-from, else the tensor itself)"""
     S, HW, K = masks.shape
     assert torch.equal(env.actions, acts)
     buf = env.packed_buffer(1)
@@ -129,12 +140,12 @@ def packed_leg(torch, env, evaluate_actions, evaluate_actions_packed, a, logits,
 
     def p_update():
         lp_.grad = None
-        lp, ent = evaluate_actions_packed(env, lp_, rows)
+        lp, ent = evaluate_actions_packed(env, feed(lp_), rows)
         ((lp * g_lp).sum() + (ent * g_ent).sum()).backward()
         return lp, ent
 
     with torch.no_grad():
-        d = evaluate_actions(env, logits, masks, acts)
+        d = evaluate_actions(env, feed(logits), masks, acts)
     p = p_update()
     k_update()
     i32 = torch.int32
@@ -145,15 +156,29 @@ def packed_leg(torch, env, evaluate_actions, evaluate_actions_packed, a, logits,
     from microrts_amd import _lib
 
     h, P = env._h, env._p
+    logits = feed(logits)  # the launches alone: no cast inside the window
     lp, ent, grad = torch.empty(S, device=env.device), torch.empty(S, device=env.device), torch.empty_like(logits)
+    code = {torch.float32: 0, torch.bfloat16: 1, torch.float16: 2}[logits.dtype]  # MRTS_LOGITS_*
 
     def d_launches():
-        _lib.check(h.L.mrts_policy_head_score_dev(h.h, S, P(logits), P(masks), P(acts), P(lp), P(ent), env._s(None)))
-        _lib.check(h.L.mrts_policy_head_grad_dev(h.h, S, P(logits), P(masks), P(acts), P(g_lp), P(g_ent), P(grad), env._s(None)))
+        if code == 0:
+            _lib.check(h.L.mrts_policy_head_score_dev(h.h, S, P(logits), P(masks), P(acts), P(lp), P(ent), env._s(None)))
+            _lib.check(h.L.mrts_policy_head_grad_dev(h.h, S, P(logits), P(masks), P(acts), P(g_lp), P(g_ent), P(grad), env._s(None)))
+        else:
+            _lib.check(h.L.mrts_policy_head_score_typed_dev(h.h, S, code, P(logits), P(masks), P(acts), P(lp), P(ent), env._s(None)))
+            _lib.check(h.L.mrts_policy_head_grad_typed_dev(h.h, S, code, P(logits), P(masks), P(acts), P(g_lp), P(g_ent), P(grad),
+                                                           env._s(None)))
 
     def p_launches():
-        _lib.check(h.L.mrts_policy_head_score_packed_dev(h.h, S, P(logits), P(buf), S, cap, None, P(lp), P(ent), env._s(None)))
-        _lib.check(h.L.mrts_policy_head_grad_packed_dev(h.h, S, P(logits), P(buf), S, cap, None, P(g_lp), P(g_ent), P(grad), env._s(None)))
+        if code == 0:
+            _lib.check(h.L.mrts_policy_head_score_packed_dev(h.h, S, P(logits), P(buf), S, cap, None, P(lp), P(ent), env._s(None)))
+            _lib.check(h.L.mrts_policy_head_grad_packed_dev(h.h, S, P(logits), P(buf), S, cap, None, P(g_lp), P(g_ent), P(grad),
+                                                            env._s(None)))
+        else:
+            _lib.check(h.L.mrts_policy_head_score_packed_typed_dev(h.h, S, code, P(logits), P(buf), S, cap, None, P(lp), P(ent),
+                                                                   env._s(None)))
+            _lib.check(h.L.mrts_policy_head_grad_packed_typed_dev(h.h, S, code, P(logits), P(buf), S, cap, None, P(g_lp), P(g_ent),
+                                                                  P(grad), env._s(None)))
 
     t.update(timed_interleaved(torch, {"launches_dense_a": d_launches, "launches_packed": p_launches, "launches_dense_b": d_launches},
                                a.warmup, a.repeats, 20))
@@ -186,7 +211,12 @@ def main():
     ap.add_argument("--warmup", type=int, default=3)
     ap.add_argument("--repeats", type=int, default=20)
     ap.add_argument("--packed", action="store_true", help="also the packed rollout rows against the dense update")
+    ap.add_argument("--dtype", choices=["float32", "bfloat16", "float16"], default="float32", help="the logits the kernels get")
+    ap.add_argument("--cast-from", choices=["bfloat16", "float16"], default=None,
+                    help="with --dtype float32: the network's logits have this type, the timed kernel legs include the casts")
     a = ap.parse_args()
+    if a.cast_from and a.dtype != "float32":
+        raise SystemExit("--cast-from goes with --dtype float32")
     if not torch.cuda.is_available():
         raise SystemExit("policy_head_bench needs an MI355X")
     S = a.slots
@@ -201,6 +231,11 @@ def main():
     dev = env.device
     masks = env.masks.reshape(S, HW, K)
     logits = 3 * torch.randn((S, HW, KL), generator=torch.Generator(device=dev).manual_seed(1), device=dev)
+    # net: the network's logits; feed(net): what the kernels get; logits: their float32 values (the PyTorch head's input)
+    net = logits.to(getattr(torch, a.cast_from or a.dtype))
+    feed = (lambda t: t.float()) if a.cast_from else (lambda t: t)
+    logits = net.float()
+    esize = feed(net).element_size()
     cand = masks[..., 0] != 0
     mbool = (masks[..., 1:] != 0) & cand[..., None]  # MicroRTS-Py masks every field of a cell without a unit
     n_cand = int(cand.sum())
@@ -209,15 +244,35 @@ def main():
     acts, lp_k, ent_k = env.sample_actions(logits, SEED, 7)
     acts = acts.clone()
     g_lp, g_ent = torch.randn(S, device=dev), torch.randn(S, device=dev)
-    lk = logits.clone().requires_grad_(True)
+    lk = net.clone().requires_grad_(True)
 
     def k_sample():
-        env.sample_actions(logits, SEED, 7)
+        env.sample_actions(feed(net), SEED, 7)
 
     def k_update():
         lk.grad = None
-        lp, ent = evaluate_actions(env, lk, masks, acts)
+        lp, ent = evaluate_actions(env, feed(lk), masks, acts)
         ((lp * g_lp).sum() + (ent * g_ent).sum()).backward()
+
+    # the float32 entry points on the float32 values: what the PyTorch head is checked against, and what 16-bit
+    # logits must reproduce bit for bit
+    l32 = logits.clone().requires_grad_(True)
+    lp32, ent32 = evaluate_actions(env, l32, masks, acts)
+    ((lp32 * g_lp).sum() + (ent32 * g_ent).sum()).backward()
+    bits = None
+    if a.dtype != "float32":
+        i32, i16 = torch.int32, torch.int16
+        acts16, lp16, ent16 = env.sample_actions(net, SEED, 7)
+        with torch.no_grad():
+            s16 = evaluate_actions(env, net, masks, acts)
+        k_update()
+        bits = {
+            "sample_equal": bool(torch.equal(acts16, acts) and torch.equal(lp16.view(i32), lp_k.view(i32))
+                                 and torch.equal(ent16.view(i32), ent_k.view(i32))),
+            "score_equal": bool(torch.equal(s16[0].view(i32), lp32.detach().view(i32)) and torch.equal(s16[1].view(i32), ent32.detach().view(i32))),
+            "grad_equal": bool(lk.grad.dtype == net.dtype and torch.equal(lk.grad.view(i16), l32.grad.to(net.dtype).view(i16))),
+        }
+        assert all(bits.values()), bits
 
     # the PyTorch head on the same tensors
     a64 = acts.long()
@@ -239,9 +294,8 @@ def main():
         const = sum((~mbool[..., lo:hi].any(-1)).sum(-1).float() * math.log(hi - lo) for lo, hi in fl)
         d_lp = float((lp_t + const - lp_k).abs().max())
         d_ent = float((ent_t - const - ent_k).abs().max())
-    k_update()
     t_update()
-    d_grad = float((lk.grad - lt.grad).abs().max())
+    d_grad = float((l32.grad - lt.grad).abs().max())
     scale = float(lp_t.abs().max())
     assert d_lp <= 1e-5 * scale + 1e-2 and d_ent <= 1e-5 * scale + 1e-2 and d_grad <= 1e-4, (d_lp, d_ent, d_grad)
 
@@ -259,20 +313,22 @@ def main():
     read = {
         "source_bits": S * ((HW + 31) // 32) * 4,
         "mask_records": n_cand * K, "mask_sector_bytes": 32 * sectors(np, cells * K, K),
-        "logit_rows": n_cand * KL * 4, "logit_sector_bytes": 32 * sectors(np, cells * KL * 4, KL * 4),
+        "logit_rows": n_cand * KL * esize, "logit_sector_bytes": 32 * sectors(np, cells * KL * esize, KL * esize),
     }
-    dense = S * HW * KL * 4
+    dense = S * HW * KL * esize
     res.update({
         "shape": {"slots": S, "map": MAP, "cells": HW, "logits_per_cell": KL, "rollout_steps": a.rollout},
         "candidate_cells": n_cand, "candidate_density": n_cand / (S * HW),
         "sample_bytes_read": read,
         "sample_sector_bytes_read": read["source_bits"] + read["mask_sector_bytes"] + read["logit_sector_bytes"],
-        "dense_logit_bytes": dense,
+        "dtype": a.dtype, "cast_from": a.cast_from, "bit_equal_to_float32": bits,
+        "dense_logit_bytes": dense, "gradient_bytes_written": dense,
         "sample_read_share_of_dense": (read["source_bits"] + read["mask_sector_bytes"] + read["logit_sector_bytes"]) / dense,
         "check": {"logprob_max_abs_diff": d_lp, "entropy_max_abs_diff": d_ent, "grad_max_abs_diff": d_grad, "logprob_scale": scale},
     })
     if a.packed:
-        res["packed"] = packed_leg(torch, env, evaluate_actions, evaluate_actions_packed, a, logits, masks, acts, g_lp, g_ent, k_update, lk)
+        res["packed"] = packed_leg(torch, env, evaluate_actions, evaluate_actions_packed, a, net, masks, acts, g_lp, g_ent, k_update, lk,
+                                   feed)
     print(json.dumps(res))
     env.close()
 
