@@ -1940,8 +1940,24 @@ int mrts_lane_audit_probe(void) {
 }
 #endif
 #ifdef MRTS_ABLATE
-// diagnostic build only: g_ablate (tools/ablate_price.py)
-int mrts_set_ablate(unsigned v) { return mrts::setAblate(v) == hipSuccess ? 0 : -EIO; }
+#include "mrts_ablate.h"
+// diagnostic build only: g_ablate (tools/ablate_price.py), bit b = the row of mrts_ablate.h with that bit
+int mrts_set_ablate(unsigned long long v) { return mrts::setAblate(v) == hipSuccess ? 0 : -EIO; }
+// that table, row by row: the row whose bit is `bit` — its enum name, kind ("AGAIN" / "SKIP" / "COUNT"), the name the
+// tools print and its name on the steady instance (NULL where it is the same) — or -ENOENT when no row has that bit
+int mrts_ablate_phase(int bit, const char** enum_name, const char** kind, const char** name, const char** steady_name) {
+    static const struct { int bit; const char *en, *kind, *name, *steady; } rows[] = {
+#define X(n, bit, kind, name, steadyName) {bit, "AB_" #n, #kind, name, steadyName},
+        MRTS_AB_PHASES(X)
+#undef X
+    };
+    for (const auto& r : rows)
+        if (r.bit == bit) {
+            *enum_name = r.en, *kind = r.kind, *name = r.name, *steady_name = r.steady;
+            return 0;
+        }
+    return -ENOENT;
+}
 int mrts_get_dbg(unsigned long long* out, int reset) { return mrts::getDbg(out, reset) == hipSuccess ? 0 : -EIO; }
 #endif
 #ifdef MRTS_PHASE_TIMING

@@ -77,11 +77,14 @@ constexpr int mileOf(int ph) {
     do {          \
     } while (0)
 #endif
-// Diagnostic build only (-DMRTS_ABLATE, tools/ablate_price.py): g_ablate bit b runs phase b twice
-// (idempotently, inputs laundered so the copies cannot be merged) — the marginal cost of a phase in
-// the real, contended kernel.  Never loaded by the package.
+// Diagnostic build only (-DMRTS_ABLATE, `make ablate`; tools/ablate_price.py, tools/ablate_sq.py): a set bit of
+// g_ablate runs its phase twice (idempotently, inputs laundered so the copies cannot be merged) — the marginal cost of
+// a phase in the real, contended kernel — or leaves something out, or counts.  Never loaded by the package.  The bits,
+// their kinds and names are the rows of mrts_ablate.h; a site in the step is one line of one of the three macros below,
+// and a second copy longer than its line is a member of Game's last section (abl...).
 #ifdef MRTS_ABLATE
-__device__ uint32_t g_ablate;
+#include "mrts_ablate.h"
+__device__ uint64_t g_ablate;
 __device__ unsigned long long g_dbg[4];  // diagnostics: [0] PO render items, [1] PO renders, [2] delta renders
 template <class T>
 DEV T launder(T v) {
@@ -92,27 +95,20 @@ template <class T>
 DEV void keepv(T v) {
     asm volatile("" ::"v"(v));
 }
-#define ABL(b) ((G_AB >> (b)) & 1u)
-enum { AB_LOAD = 0, AB_OBS = 1, AB_STORE = 2, AB_MASKBITS = 3, AB_RECORD = 4, AB_POLICY = 5, AB_ACCEPT = 6,
-       AB_LEGAL = 7, AB_OUTCOME = 8, AB_INDEX = 9, AB_GONE = 10, AB_TABLES = 11, AB_RANK = 12, AB_DECODE = 13,
-       AB_ISSUE = 14, AB_CYCLERANK = 15,
-       // skips (outputs nothing in the step reads back): the observation, the mask record stores
-       AB_SKIP_OBS = 16, AB_SKIP_RECORD = 17,
-       // PO observation split: everything but the stores (values kept alive) / only the stores (zeros)
-       AB_PO_NOSTORE = 18, AB_PO_ZEROSTORE = 19,
-       // PO observation pieces skipped: sight-disk painting, the last-writer cell map, the render record
-       AB_PO_NOPAINT = 20, AB_PO_NOSCELL = 21, AB_PO_NORECORD = 22, AB_PO_NOSNAPSHOT = 23,
-       // round 9, the step's glue: the forwarded row's decode (decodeFwd on a launch's first step,
-       // else the steady instance's sampledDec + unpack), nextStep, the priority / SIMD-rank block at the top of
-       // the iteration, writeMasksLanes' set-up before maskTables, and cycleLanes' execute loop WITHOUT the
-       // executes (not idempotent): the pick of each ready item and its lane reads
-       AB_DECFWD = 24, AB_NEXTSTEP = 25, AB_PRIO = 26, AB_MASKSETUP = 27, AB_EXECLOOP = 28, AB_COUNT = 29,
-       // round 11, the steady instance: cycleLanes' lane-parallel MOVE pass and the step's
-       // reward / done stores, each once more
-       AB_MOVEBATCH = 30, AB_REWARD = 31,
-       // compact() once more in a step with a death, on the steady instance only: the 32-bit word is full, and the
-       // steady instance (full observability) never reads the PO rows' bits, so it takes the first of them
-       AB_COMPACT_STEADY = AB_PO_NOSTORE };
+#define X(n, bit, kind, name, steadyName) AB_##n = bit,
+enum { MRTS_AB_PHASES(X) };
+#undef X
+#endif
+// A site tests its bit through ab(b): Game's member, and in k_env a local of the same name.  Without MRTS_ABLATE
+// AB_ON expands to nothing and the two prefixes to the bare statement that follows them.
+#ifdef MRTS_ABLATE
+#define AB_ON(b, ...) if (ab(b)) { __VA_ARGS__; } else (void)0  // the statement(s) if bit b: a phase once more; snapshot*()'s return
+#define AB_SKIP(b) if (!ab(b))                                  // prefix: not the next statement if bit b
+#define AB_TWICE(b) for (int rep_ = 0; rep_ < (ab(b) ? 2 : 1); rep_++)  // prefix: the next statement twice if bit b
+#else
+#define AB_ON(b, ...) (void)0
+#define AB_SKIP(b)
+#define AB_TWICE(b)
 #endif
 enum { GT_SELFPLAY = 0, GT_AGENT_VS_BOT = 1, GT_BOT_VS_BOT = 2, GT_PLAYOUT = 3 };  // game_kind & 15
 // per-player counters of this step's issued pairs, as the TraceEntry holds them (after issueSafe's
@@ -233,8 +229,10 @@ struct Game {
 #endif
 #endif
 #ifdef MRTS_ABLATE
+    // g_ablate's low word, read once by k_env and held through the step as before.  A row past bit 31 reads the high
+    // word where it tests it (b is a constant at every site), so the wider word costs the step no register.
     uint32_t G_AB = 0;
-    DEV bool ab(int b) const { return (G_AB >> b) & 1u; }
+    DEV bool ab(int b) const { return ((b < 32 ? G_AB : (uint32_t)(g_ablate >> 32)) >> (b & 31)) & 1u; }
 #endif
     // lane id for the step code: threadIdx.x passed through an opaque (volatile asm) copy at the start
     // of every iteration of a multi-step launch, so that lane-derived values are recomputed per
@@ -652,21 +650,18 @@ struct Game {
         // being rebuilt after each view's acceptance chain
         const int NBv = (HW + 2 * W + 31) / 32;
         uint32_t* const vres = (MRTS_PO_VRES && po && NBv <= 64 && HW - NBv >= (HW == 1024 ? 896 : 0)) ? scell + (HW - NBv) : nullptr;
-#ifdef MRTS_ABLATE
-        if (useIx && ab(AB_INDEX)) buildIndex();
-#endif
+        if (useIx) AB_ON(AB_INDEX, buildIndex());
         MPHASE(22);
         int t = 0, pr = -1, ut = 0, tx = 0, ty = 0;
         bool bad = false;
-#ifdef MRTS_ABLATE
-        if (ab(AB_DECODE) && idle) {
+        // (in place: as a member of the copies' section it cost the 8x8 helper instance two more spilled VGPRs)
+        AB_ON(AB_DECODE, if (idle) {
             int32_t b2[7];
             for (int k = 0; k < 7; k++) b2[k] = launder(a[k]);
             int t2 = 0, pr2 = -1, ut2 = 0, tx2 = 0, ty2 = 0;
             const bool bad2 = decodeFields(launder(cu), b2, t2, pr2, ut2, tx2, ty2);
             keepv(t2 + pr2 + ut2 + tx2 + ty2 + (int)bad2);
-        }
-#endif
+        });
         // steady, from the launch's second step on: writeMasksSteady left this row decoded in lfwd (sampledDec)
         const bool dec = steady && fwdOn && !firstIt;
         if (dec) {
@@ -680,18 +675,7 @@ struct Game {
         } else if (idle) {
             bad = fwdOn ? decodeFwd(cu, lfwd, t, pr, ut, tx, ty) : decodeFields(cu, a, t, pr, ut, tx, ty);
         }
-#ifdef MRTS_ABLATE
-        if (ab(AB_DECFWD) && idle && fwdOn) {
-            if (dec) {
-                const uint32_t w = launder(lfwd);
-                keepv(ua_type(w) + ua_ut(w) + ua_tx(w) + ua_ty(w) + ((int)(w >> 24) - 1) + (int)(w & 0xFFFFFFu));
-            } else {
-                int t2 = 0, pr2 = -1, ut2 = 0, tx2 = 0, ty2 = 0;
-                const bool bad2 = decodeFwd(launder(cu), launder(lfwd), t2, pr2, ut2, tx2, ty2);
-                keepv((int)pack_ua(t2, ut2, tx2, ty2) + pr2 + (int)bad2);
-            }
-        }
-#endif
+        AB_ON(AB_DECFWD, ablDecFwd(idle, dec, cu));
         if (ballot(bad)) addErr(E_PRODUCE_TYPE);
         const uint32_t adec = dec ? (idle ? lfwd & 0xFFFFFFu : 0u) : pack_ua(t, ut, tx, ty);
         const int c = uy(cu) * W + ux(cu);
@@ -711,16 +695,7 @@ struct Game {
 #endif
             MPHASE(2);
             if (both) {
-#ifdef MRTS_ABLATE
-                if (ab(AB_ISSUE)) {  // the merged pass once more: the test (scratch only), then the writes (idempotent)
-                    int q0, q1, d0, d1;
-                    keepv((int)issueBothTest(idle && !bad, launder(cu), launder(adec), launder(pr), q0, q1, d0, d1));
-                    const int seqS = seq, sp0 = sumProd0, sp1 = sumProd1, mp0 = maxProd0, mp1 = maxProd1;
-                    const bool amp = anyMP;
-                    issueBothWrite(idle && !bad, bad, launder(cu), launder(adec), launder(pr), q0, q1, d0, d1);
-                    seq = seqS, sumProd0 = sp0, sumProd1 = sp1, maxProd0 = mp0, maxProd1 = mp1, anyMP = amp;
-                }
-#endif
+                AB_ON(AB_ISSUE, ablIssueBoth(idle && !bad, bad, cu, adec, pr));
                 issueBothWrite(idle && !bad, bad, cu, adec, pr, s0, s1, mc0, mc1);
                 MPHASE(3);
                 merged = true;
@@ -752,15 +727,8 @@ struct Game {
             bool isPA = false;
             if (m) {
                 const int rank = cellRank(m, cand, c);
-#ifdef MRTS_ABLATE
-                if (ab(AB_RANK)) keepv(cellRank(m, cand, launder(c)));
-                if (ab(AB_ACCEPT)) {
-                    int r0 = run0, r1 = run1, ir = 0;
-                    const uint64_t a2 = acceptChain(p, r0, r1, cand, launder(rank), __popcll(m), launder(t), launder(pr),
-                                                    launder(c), launder(adec), true, ir);
-                    keepv(ir + (int)a2 + r0 + r1);
-                }
-#endif
+                AB_ON(AB_RANK, keepv(cellRank(m, cand, launder(c))));
+                AB_ON(AB_ACCEPT, ablAccept(p, run0, run1, cand, rank, __popcll(m), t, pr, c, adec));
                 MPHASE(23);
                 int irank = 0;
                 const uint64_t acc = acceptChain(p, run0, run1, cand, rank, __popcll(m), t, pr, c, adec, useIx || vres, irank, vres);
@@ -773,13 +741,7 @@ struct Game {
                     ttx = tx;
                     tty = ty;
                     tut = ut;
-#ifdef MRTS_ABLATE
-                    if (ab(AB_LEGAL)) {
-                        int a1 = launder(t), a2 = launder(pr), a3 = launder(tx), a4 = launder(ty), a5 = launder(ut);
-                        legality(l, launder(cu), a1, a2, a3, a4, a5);
-                        keepv(a1 + a2 + a3 + a4 + a5);
-                    }
-#endif
+                    AB_ON(AB_LEGAL, ablLegal(l, cu, t, pr, tx, ty, ut));
                     // A forwarded row was sampled by the fused policy from this unit's mask record, which
                     // the previous step wrote from this same state (no cycle in between): its type bit
                     // and parameter bits are members of getUnitActions' list (a PRODUCE's free
@@ -2162,9 +2124,7 @@ struct Game {
     // units inside the sight of player p's (live) units, with the assignments they hold now.  Lane =
     // unit, a uniform loop over the observers (few; painting disks costs more here).
     DEV void snapshot(int p) {
-#ifdef MRTS_ABLATE
-        if (ab(AB_PO_NOSNAPSHOT)) return;
-#endif
+        AB_ON(AB_PO_NOSNAPSHOT, return);
         for (int o0 = 0; o0 < nu; o0 += 64) {
             const int o = o0 + lid();
             uint32_t cu = 0;
@@ -2218,9 +2178,7 @@ struct Game {
     // (the render clears it).
     DEV bool snapBothOk() const { return W <= 32 && H <= 32 && nu <= 64 && U.maxSight <= 15; }
     DEV void snapshotBoth() {
-#ifdef MRTS_ABLATE
-        if (ab(AB_PO_NOSNAPSHOT)) return;
-#endif
+        AB_ON(AB_PO_NOSNAPSHOT, return);
         const int l = lid();
         uint32_t* const r0 = vis;
         uint32_t* const r1 = vis + H;
@@ -2244,9 +2202,7 @@ struct Game {
         wsync();
     }
     DEV void snapshotActions(int p) {  // view p's assignment bits now (membership from snapshotBoth)
-#ifdef MRTS_ABLATE
-        if (ab(AB_PO_NOSNAPSHOT)) return;
-#endif
+        AB_ON(AB_PO_NOSNAPSHOT, return);
         const int l = lid();
         if (l < nu) {
             uint32_t b = snap[l] & ~(7u << (2 + 3 * p));
@@ -2471,18 +2427,7 @@ struct Game {
             const int t0 = at[l];
             if (a & UA_PRESENT) ready = etaFlat(ua_type(a), prm, ua_ut(a), utyp(cu)) + t0 <= time;
         }
-#ifdef MRTS_ABLATE
-        if (ab(AB_CYCLERANK)) {  // the ready test and the rank by sequence number once more (nothing written)
-            bool rd = false;
-            const uint32_t a2 = launder(a), c2 = launder(cu);
-            const int p2 = launder(prm), q2 = launder(sq);
-            if (l < nu && (a2 & UA_PRESENT))
-                rd = etaFlat(ua_type(a2), p2, ua_ut(a2), utyp(c2)) + launder(at[l]) <= time;
-            int rk = 0;
-            for (uint64_t m = ballot(rd && ua_type(a2) != T_NONE); m; m &= m - 1) rk += rl(q2, __builtin_ctzll(m)) < q2;
-            keepv(rk);
-        }
-#endif
+        AB_ON(AB_CYCLERANK, ablCycleRank(l, a, cu, prm, sq));
         if (ready) ua[l] = a & ~(UA_READY | UA_PRESENT);
         const bool wk0 = ready && ua_type(a) != T_NONE;
         const uint64_t work0 = ballot(wk0);
@@ -2527,13 +2472,7 @@ struct Game {
             // * the other executes touch res / hp / the players' resources / a new unit's slot, never a mover's words.
             // Old cells were cleared before the wsync above; E_COLLISION as the serial MOVE reports it.
             moveBatch(mv, cu, prm, ipos - W, true);
-#ifdef MRTS_ABLATE
-            if (ab(AB_MOVEBATCH)) {  // once more (the same cells and words written again; no second collision test)
-                wsync();
-                if (mv) cell[launder(uy(cu) * W + ux(cu))] = EMPTY;
-                moveBatch(mv, launder(cu), launder(prm), launder(ipos - W), false);
-            }
-#endif
+            AB_ON(AB_MOVEBATCH, ablMoveBatch(mv, cu, prm, ipos - W));
             wsync();
         }
         if (!work) return;
@@ -2542,17 +2481,7 @@ struct Game {
         killedLanes = 0;
         readySlot = wk ? l : -1;
         const int nw = __popcll(work);
-#ifdef MRTS_ABLATE
-        if (ab(AB_EXECLOOP)) {  // the loop without its executes: each ready item's pick and lane reads
-            const int rk2 = launder(rank);
-            for (int r = 0; r < nw; r++) {
-                const int k = __builtin_ctzll(ballot(wk && rk2 == r));
-                uint32_t c = uniu((uint32_t)rl((int)cu, k));
-                if ((launder(killedLanes) >> k) & 1ull) c |= UC_DEAD;
-                keepv(c + (uniu((uint32_t)rl((int)a, k)) & ~(UA_READY | UA_PRESENT)) + (uint32_t)rl(prm, k) + (uint32_t)k);
-            }
-        }
-#endif
+        AB_ON(AB_EXECLOOP, ablExecLoop(wk, rank, nw, cu, a, prm));
         for (int r = 0; r < nw; r++) {
             const int k = __builtin_ctzll(ballot(wk && rank == r));
             uint32_t c = uniu((uint32_t)rl((int)cu, k));
@@ -2683,35 +2612,35 @@ struct Game {
     // ProduceWorkerRewardFunction.java:20-30 (the other two: the same lines of their files); Attack:
     // AttackRewardFunction.java:20-36 (a legal attack always targets a minplayer unit of the pre-cycle
     // pgs).  Constants are float 1.
-    // it: this launch's iteration (the step's place in the Responses ring, KDyn.resp_reward)
+    // it: this launch's iteration (the step's place in the Responses ring, KDyn.resp_reward); never the steady instance
     DEV bool writeRewards(int slot0, int nslots, int pl0, int pl1, bool gameover, int winner, int it = 0) {
-        const int R = steady ? 1 : D.n_rewards;
+        const int R = D.n_rewards;
         int newSq0 = INF, newSq1 = INF;
-        if (MRTS_UNLIKELY(D_ZERO(reward_need) & RN_CLOSER)) closerMin(newSq0, newSq1);
+        if (MRTS_UNLIKELY(D.reward_need & RN_CLOSER)) closerMin(newSq0, newSq1);
         bool resLeft = false;
-        if (D_ZERO(reward_need) & RN_RESOURCES)
+        if (D.reward_need & RN_RESOURCES)
             for (int o0 = 0; o0 < nu; o0 += 64) {
                 const int o = o0 + lid();
                 resLeft |= ballot(o < nu && !(uc[o] & UC_DEAD) && (U.flags[utyp(uc[o])] & N_RESOURCE) && res[o] > 0) != 0;
             }
-        const int k0 = (int)(D_ZERO(reward_kinds4) & 15u);
+        const int k0 = (int)(D.reward_kinds4 & 15u);
         // the Responses ring (mrts_set_step_responses): reward / done point at the call's ring and each
         // iteration writes its own step there (resp_stride = n_slots * n_rewards; 0 = the plain buffers)
-        const size_t ro = (size_t)((uint32_t)it * (uint32_t)D_ZERO(resp_stride));
+        const size_t ro = (size_t)((uint32_t)it * (uint32_t)D.resp_stride);
         const bool done0 = k0 == RF_WINLOSS ? gameover : (k0 == RF_RESOURCE_GATHER ? !resLeft : false);
         const int L = lid();
         if (R == 1 && k0 == RF_WINLOSS) {  // WinLoss alone (the common case): a wave-uniform branch, no switch
             if (L < nslots) {
                 const int p = L ? pl1 : pl0;
-                if (D_HAS(reward)) D.reward[ro + slot0 + L] = gameover ? (winner == p ? 1.0 : -1.0) : 0.0;
-                if (D_HAS(done)) D.done[ro + slot0 + L] = gameover ? 1 : 0;
+                if (D.reward) D.reward[ro + slot0 + L] = gameover ? (winner == p ? 1.0 : -1.0) : 0.0;
+                if (D.done) D.done[ro + slot0 + L] = gameover ? 1 : 0;
             }
             return done0;
         }
-        if (L < nslots * R && (D_HAS(reward) || D_HAS(done))) {
+        if (L < nslots * R && (D.reward || D.done)) {
             const int i = L / R, j = L - i * R;
             const int p = i ? pl1 : pl0;
-            const int kind = (int)((D_ZERO(reward_kinds4) >> (4 * j)) & 15u);
+            const int kind = (int)((D.reward_kinds4 >> (4 * j)) & 15u);
             double r = 0.0;
             bool d = false;
             switch (kind) {
@@ -2733,8 +2662,8 @@ struct Game {
                         r = closerDist(hdr[HX_OLDSQ + p]) - closerDist(p == 0 ? newSq0 : newSq1);
                     break;
             }
-            if (D_HAS(reward)) D.reward[ro + (size_t)(slot0 + i) * R + j] = r;
-            if (D_HAS(done)) D.done[ro + (size_t)(slot0 + i) * R + j] = d ? 1 : 0;
+            if (D.reward) D.reward[ro + (size_t)(slot0 + i) * R + j] = r;
+            if (D.done) D.done[ro + (size_t)(slot0 + i) * R + j] = d ? 1 : 0;
         }
         return done0;
     }
@@ -3224,9 +3153,7 @@ struct Game {
         // visibility planes over the view's units at their current positions (dead ones included:
         // the view's list still holds them): own / other player's sight disks
         const bool painter = in && uplay(cu) >= 0;
-#ifdef MRTS_ABLATE
-        if (!ab(AB_PO_NOPAINT))
-#endif
+        AB_SKIP(AB_PO_NOPAINT)
         if (ballot(painter)) paintDisks(painter, cu, uplay(cu) == p ? vis : vis + H);
         const uint64_t deadM = ballot(dead);
         if (pr && dead) poMarkCell(nextPend, cc);
@@ -3301,9 +3228,7 @@ struct Game {
         wsync();
         {
             const bool pt0 = in0 && own >= 0, pt1 = in1 && own >= 0;
-#ifdef MRTS_ABLATE
-            if (!ab(AB_PO_NOPAINT))
-#endif
+            AB_SKIP(AB_PO_NOPAINT)
             if (ballot(pt0 || pt1))
                 paintDisks2(pt0, own == 0 ? rowsV0 : rowsV0 + H, pt1, own == 1 ? rowsV1 : rowsV1 + H, cu);
         }
@@ -3343,14 +3268,8 @@ struct Game {
         }
         poLds = pr != nullptr;
         wsync();
-#ifdef MRTS_ABLATE
-        if (ab(AB_COUNT) && l == 0) {  // contended global atomics: only when counting
-            atomicAdd(&g_dbg[0], (unsigned long long)n);
-            atomicAdd(&g_dbg[1], 1ull);
-            if (delta) atomicAdd(&g_dbg[2], 1ull);
-        }
-        if (ab(AB_PO_NOSTORE)) n = 0;  // no render pass (gather + stores)
-#endif
+        AB_ON(AB_COUNT, ablCountRender(l, n, delta));
+        AB_ON(AB_PO_NOSTORE, n = 0);  // no render pass (gather + stores)
         int32_t* out = D.obs + (size_t)slot0 * D.C * HW;
         const __amdgpu_buffer_rsrc_t rs = bufRsrc(out, (uint32_t)(2 * D.C * HW * 4));
         const uint64_t deadAny = deadM0 | deadM1;
@@ -3360,15 +3279,8 @@ struct Game {
             int vv[4][8];
             poChunk(v, c4, deadAny, v ? deadM1 : deadM0, v ? rowsV1 : rowsV0, vv);
             const uint32_t base = (uint32_t)(v * D.C * HW + 4 * c4) * 4u;
-#ifdef MRTS_ABLATE
-            if (ab(AB_PO_ZEROSTORE)) {  // pricing: the render's values computed, not stored
-                int acc = 0;
-#pragma unroll
-                for (int k = 0; k < 8; k++) acc += vv[0][k] ^ vv[1][k] ^ vv[2][k] ^ vv[3][k];
-                keepv(acc);
-                continue;
-            }
-#endif
+            AB_ON(AB_PO_ZEROSTORE, ablKeepChunk(vv));  // pricing: the render's values computed (kept alive), not stored
+            AB_SKIP(AB_PO_ZEROSTORE)
 #pragma unroll
             for (int k = 0; k < 8; k++) st4sc1(rs, base + (uint32_t)(k * HW) * 4u, vv[0][k], vv[1][k], vv[2][k], vv[3][k]);
         }
@@ -3644,9 +3556,7 @@ struct Game {
             writeObsPOFast(slot, p, delta);
             return;
         }
-#ifdef MRTS_ABLATE
-        if (!ab(AB_PO_NOSCELL))
-#endif
+        AB_SKIP(AB_PO_NOSCELL)
         for (int c = lid(); c < HW; c += 64) scell[c] = 0;
         const int NW = H * ((W + 31) >> 5);
         uint32_t* mineRows = vis;
@@ -3659,16 +3569,12 @@ struct Game {
             const bool in = o < nu && snap_in(snap[o], p);
             const uint32_t cu = in ? uc[o] : 0u;
             if (in) {
-#ifdef MRTS_ABLATE
-                if (!ab(AB_PO_NOSCELL))
-#endif
+                AB_SKIP(AB_PO_NOSCELL)
                 atomicMax(&scell[uy(cu) * W + ux(cu)], (uint32_t)(o + 1));
             }
             // visibility planes over the view's units at their current positions (dead ones
             // included: the view's list still holds them): own / other player's sight disks
-#ifdef MRTS_ABLATE
-            if (!ab(AB_PO_NOPAINT))
-#endif
+            AB_SKIP(AB_PO_NOPAINT)
             {
                 const bool painter = in && uplay(cu) >= 0;
                 if (fastPaint) {
@@ -3744,9 +3650,7 @@ struct Game {
                         for (int k = 0; k < 8; k++) out[k * HW + 4 * c4 + j] = v[j][k];
             }
         }
-#ifdef MRTS_ABLATE
-        if (!ab(AB_PO_NORECORD))
-#endif
+        AB_SKIP(AB_PO_NORECORD)
         if (D.po_prev && poDeltaShape(H, W)) poRecord(p);
     }
     // the PO record of view p for the next write: this render's sight rows and the chunks of its units
@@ -4405,38 +4309,12 @@ struct Game {
         wsync();
         if (si >= 0) atomicOr(&nb[si * MW + (c >> 5)], 1u << (c & 31));
         if (rowB && l < nu && !(cu & UC_DEAD) && uplay(cu) >= 0) atomicOr(&rows[uplay(cu) * H + uy(cu)], 1u << ux(cu));
-#ifdef MRTS_ABLATE
-        if (ab(AB_MASKSETUP)) {  // the set-up once more: the same bitmaps cleared and filled again
-            wsync();
-            if (l < NW) nb[l] = 0;
-            if (rowB && l < 2 * H) rows[l] = 0;
-            int si2 = -1;
-            uint32_t cu2 = 0;
-            if (l < nu) {
-                cu2 = launder(uc[l]);
-                if (!(cu2 & UC_DEAD) && !(launder(ua[l]) & UA_PRESENT)) {
-                    const int op = uplay(cu2);
-                    if (op >= 0 && op == pl0) si2 = 0;
-                    else if (nslots > 1 && op >= 0 && op == pl1) si2 = 1;
-                }
-            }
-            const int c2 = uy(cu2) * W + ux(cu2);
-            wsync();
-            if (si2 >= 0) atomicOr(&nb[si2 * MW + (c2 >> 5)], 1u << (c2 & 31));
-            if (rowB && l < nu && !(cu2 & UC_DEAD) && uplay(cu2) >= 0) atomicOr(&rows[uplay(cu2) * H + uy(cu2)], 1u << ux(cu2));
-        }
-#endif
+        AB_ON(AB_MASKSETUP, ablMaskSetup(nb, NW, MW, rows, rowB, nslots > 1, pl0, pl1));
         uint32_t w0 = 0, w1 = 0, w2 = 0;
         {
             MPHASE(16);
             const MaskTables T = maskTables();
-#ifdef MRTS_ABLATE
-            if (ab(AB_TABLES)) {
-                const MaskTables T2 = maskTables();
-                keepv(T2.attack1 ^ T2.attackFar ^ T2.harvest ^ T2.move ^ T2.resource ^ T2.stockpile ^ T2.aff0 ^ T2.aff1 ^
-                      (uint32_t)T2.prod);
-            }
-#endif
+            AB_ON(AB_TABLES, ablTables());
             MPHASE(17);
             const int carried = l < nu ? res[l] : 0;
             // four lanes per idle unit wherever the row bitmaps exist: its 48 scratch words are rseq words 16..63
@@ -4457,20 +4335,7 @@ struct Game {
                     farAttackBits(far, cu, cu, ballot(l < nu && !(cu & UC_DEAD) && uplay(cu) >= 0), w0, w1, w2);
                 }
             }
-#ifdef MRTS_ABLATE
-            if (ab(AB_MASKBITS) && rowB) {  // a second copy of whichever form ran above
-                uint32_t v0 = 0, v1 = 0, v2 = 0;
-                const uint32_t cu2 = launder(cu);
-                if (qb) {
-                    wsync();
-                    maskBitsQuads(T, launder(si), cu2, launder(carried), rows, v0, v1, v2, qb);
-                } else {
-                    if (si >= 0) maskBitsFast(T, cu2, launder(carried), v0, v1, v2);
-                    farAttackRows(si >= 0 && ((T.attackFar >> utyp(cu2)) & 1u), cu2, rows, v0, v1, v2);
-                }
-                keepv(v0 ^ v1 ^ v2);
-            }
-#endif
+            if (rowB) AB_ON(AB_MASKBITS, ablMaskBits(T, si, cu, carried, rows, qb));
             MPHASE(19);
         }
         wsync();
@@ -4502,13 +4367,9 @@ struct Game {
         // the records stored lane-parallel (storeRecordsLanes) rather than each by its own lane
         const bool lanePar = !recOut && K == 79 && NW <= 16;
         if (lanePar) {
-#ifdef MRTS_ABLATE
-            if (!ab(AB_SKIP_RECORD))
-#endif
+            AB_SKIP(AB_SKIP_RECORD)
             storeRecordsLanes(si, c, w0, w1, w2, mrs, mbase, total);
-#ifdef MRTS_ABLATE
-            if (ab(AB_RECORD)) storeRecordsLanes(launder(si), launder(c), launder(w0), launder(w1), launder(w2), mrs, mbase, total);
-#endif
+            AB_ON(AB_RECORD, storeRecordsLanes(launder(si), launder(c), launder(w0), launder(w1), launder(w2), mrs, mbase, total));
         }
         if (si >= 0) {
             const int slot = slot0 + si;
@@ -4520,24 +4381,13 @@ struct Game {
                 recOut[192 + l] = w2;
             } else if (lanePar) {
             } else
-#ifdef MRTS_ABLATE
-            if (!ab(AB_SKIP_RECORD))
-#endif
+            AB_SKIP(AB_SKIP_RECORD)
             storeRecord(D.masks + (size_t)slot * total + (size_t)c * K, lo, w2);
-#ifdef MRTS_ABLATE
-            if (ab(AB_RECORD)) storeRecord(D.masks + (size_t)slot * total + (size_t)c * K, launder(lo), launder(w2));
-#endif
+            AB_ON(AB_RECORD, storeRecord(D.masks + (size_t)slot * total + (size_t)c * K, launder(lo), launder(w2)));
             MPHASE(13);
             if (pol) {
                 int32_t a[7];
-#ifdef MRTS_ABLATE
-                if (ab(AB_POLICY)) {
-                    int32_t a2[7];
-                    sampleBitsRaw(D.pol_seed, polStep, D.pol_slot_base + (uint32_t)launder(slot), NT, K,
-                                  launder((lo >> 1) | ((uint64_t)w2 << 63)), launder((uint64_t)(w2 >> 1)), launder(c), a2);
-                    keepv(a2[0] + a2[1] + a2[2] + a2[3] + a2[4] + a2[5] + a2[6]);
-                }
-#endif
+                AB_ON(AB_POLICY, ablSample(slot, lo, w2, c));
                 uint32_t pk;
                 sampleBitsRaw(D.pol_seed, polStep, D.pol_slot_base + (uint32_t)slot, NT, K, (lo >> 1) | ((uint64_t)w2 << 63),
                               (uint64_t)(w2 >> 1), c, a, &pk);
@@ -4579,9 +4429,7 @@ struct Game {
             wsync();
             return;
         }
-#ifdef MRTS_ABLATE
-        for (int rep_ = 0; rep_ < (ab(AB_GONE) ? 2 : 1); rep_++)
-#endif
+        AB_TWICE(AB_GONE)
         for (int b0 = 0; b0 < ngone; b0 += 64) {  // rslot holds 64 list entries at a time
             wsync();
             int k = incl - n;
@@ -4643,32 +4491,10 @@ struct Game {
         wsync();
         if (si >= 0) atomicOr(&nb[si * MW + (c >> 5)], 1u << (c & 31));
         if (rowF && l < nu && !(cu & UC_DEAD) && uplay(cu) >= 0) atomicOr(&rows[uplay(cu) * H + uy(cu)], 1u << ux(cu));
-#ifdef MRTS_ABLATE
-        if (ab(AB_MASKSETUP)) {  // the set-up once more: the same bitmaps cleared and filled again
-            wsync();
-            if (l < NW) nb[l] = 0;
-            if (rowF && l < 2 * H) rows[l] = 0;
-            int si2 = -1;
-            uint32_t cu2 = 0;
-            if (l < nu) {
-                cu2 = launder(uc[l]);
-                if (!(cu2 & UC_DEAD) && !(launder(ua[l]) & UA_PRESENT)) si2 = uplay(cu2);
-            }
-            const int c2 = uy(cu2) * W + ux(cu2);
-            wsync();
-            if (si2 >= 0) atomicOr(&nb[si2 * MW + (c2 >> 5)], 1u << (c2 & 31));
-            if (rowF && l < nu && !(cu2 & UC_DEAD) && uplay(cu2) >= 0) atomicOr(&rows[uplay(cu2) * H + uy(cu2)], 1u << ux(cu2));
-        }
-#endif
+        AB_ON(AB_MASKSETUP, ablMaskSetup(nb, NW, MW, rows, rowF, true, 0, 1));  // (slot i is player i's)
         MPHASE(16);
         const MaskTables T = maskTables();
-#ifdef MRTS_ABLATE
-        if (ab(AB_TABLES)) {
-            const MaskTables T2 = maskTables();
-            keepv(T2.attack1 ^ T2.attackFar ^ T2.harvest ^ T2.move ^ T2.resource ^ T2.stockpile ^ T2.aff0 ^ T2.aff1 ^
-                  (uint32_t)T2.prod);
-        }
-#endif
+        AB_ON(AB_TABLES, ablTables());
         MPHASE(17);
         const uint32_t own = ((uint32_t)(l < nu ? res[l] : 0) & 0xFFFFu) | (uint32_t)l << 16;
         wsync();
@@ -4684,9 +4510,7 @@ struct Game {
         const int n = __popc(gone);
         const int incl = rowInclSum(n);  // (lanes 0..15 hold the words)
         const int NR = RI + rl(incl, 15);
-#ifdef MRTS_ABLATE
-        if (ab(AB_GONE)) keepv(rl(rowInclSum(launder(n)), 15));  // the scan alone: the zero records ride the unit pass
-#endif
+        AB_ON(AB_GONE, keepv(rl(rowInclSum(launder(n)), 15)));  // the scan alone: the zero records ride the unit pass
         MPHASE(12);
         const uint32_t mbLo = (uint32_t)(uintptr_t)(D.masks + (size_t)slot0 * total);
         const __amdgpu_buffer_rsrc_t mrs = bufRsrc((void*)(D.masks + (size_t)slot0 * total), (uint32_t)(2 * total));
@@ -4739,29 +4563,14 @@ struct Game {
             const uint32_t canProd =
                 (uint32_t)(T.prod >> (8 * utyp(qcu))) & 0xFFu & (uplay(qcu) == 0 ? T.aff0 : T.aff1);
             if (((v0 >> (1 + 6 + 12)) & 0xFu) != 0u) v0 |= canProd << (1 + 6 + 16);
-#ifdef MRTS_ABLATE
-            if (ab(AB_MASKBITS)) {  // the quad's bits once more
-                uint32_t u0 = 0, u1 = 0, u2 = 0;
-                const uint32_t qcu2 = launder(qcu);
-                if (qa) maskBitsDir(T, qcu2, (int)(int16_t)launder(qown), d, u0, u1, u2);
-                farAttackRowsDir(far, qcu2, d, rows, u0, u1, u2);
-                keepv(quadOr(u0) ^ quadOr(u1) ^ quadOr(u2));
-            }
-#endif
+            AB_ON(AB_MASKBITS, ablMaskBitsDir(T, qa, far, qcu, qown, d, rows));
             MPHASE(19);
             if (qr && d == 0) {
                 const int qc = uy(qcu) * W + ux(qcu), slot = slot0 + uplay(qcu);
                 int32_t a[7] = {0, 0, 0, 0, 0, 0, 0};
                 if (qa) {
                     const uint64_t lo = (uint64_t)v0 | ((uint64_t)v1 << 32);
-#ifdef MRTS_ABLATE
-                    if (ab(AB_POLICY)) {
-                        int32_t a2[7];
-                        sampleBitsRaw(D.pol_seed, polStep, D.pol_slot_base + (uint32_t)launder(slot), NT, K,
-                                      launder((lo >> 1) | ((uint64_t)v2 << 63)), launder((uint64_t)(v2 >> 1)), launder(qc), a2);
-                        keepv(a2[0] + a2[1] + a2[2] + a2[3] + a2[4] + a2[5] + a2[6]);
-                    }
-#endif
+                    AB_ON(AB_POLICY, ablSample(slot, lo, v2, qc));
                     uint32_t pk;
                     int picks[3];  // the sampler's type, parameter and produce-type picks
                     sampleBitsRaw(D.pol_seed, polStep, D.pol_slot_base + (uint32_t)slot, NT, K, (lo >> 1) | ((uint64_t)v2 << 63),
@@ -4770,9 +4579,7 @@ struct Game {
                     // here (no cycle lies between the sample and the decode: the unit stands where it stood)
                     if (lastIt) st1<WT_STATE>(st() + stateFwdOff(CAP, HW) + (int)(qown >> 16), (int32_t)pk);
                     qb[3 * q + 2] = sampledDec(qcu, picks[0], picks[1], picks[2]);
-#ifdef MRTS_ABLATE
-                    if (ab(AB_DECFWD)) keepv(sampledDec(launder(qcu), launder(picks[0]), launder(picks[1]), launder(picks[2])));
-#endif
+                    AB_ON(AB_DECFWD, keepv(sampledDec(launder(qcu), launder(picks[0]), launder(picks[1]), launder(picks[2]))));
                 }
                 int32_t* dst = D.pol_actions + ((size_t)slot * HW + qc) * 7;
                 st4u<WT_MASK>(dst, a[0], a[1], a[2], a[3]);
@@ -4780,13 +4587,9 @@ struct Game {
             }
             MPHASE(13);
             if (qr) {
-#ifdef MRTS_ABLATE
-                if (!ab(AB_SKIP_RECORD))
-#endif
+                AB_SKIP(AB_SKIP_RECORD)
                 storeQuad(qcu, v0, v1, v2);
-#ifdef MRTS_ABLATE
-                if (ab(AB_RECORD)) storeQuad(launder(qcu), launder(v0), launder(v1), launder(v2));
-#endif
+                AB_ON(AB_RECORD, storeQuad(launder(qcu), launder(v0), launder(v1), launder(v2)));
             }
             wsync();
             if (mine) lfwd = qb[3 * (r - p0) + 2];
@@ -5406,6 +5209,178 @@ struct Game {
         issueFills(p, 10);
         MPHASE(28);
     }
+
+#ifdef MRTS_ABLATE
+    // ------------------------------------------------------------------ the ablation build's second copies
+    // What a site's AB_ON line runs where the copy is longer than the line: each takes what its site passes, launders
+    // it so that the copy cannot be merged with the original, and says why running it leaves the game as it was.
+    // selfPlayFast -----
+    // AB_DECFWD: the forwarded row's decode once more — the unpack of the decoded word (dec: the steady instance from
+    // a launch's second step on) or decodeFwd; nothing written
+    DEV void ablDecFwd(bool idle, bool dec, uint32_t cu) {
+        if (!(idle && fwdOn)) return;
+        if (dec) {
+            const uint32_t w = launder(lfwd);
+            keepv(ua_type(w) + ua_ut(w) + ua_tx(w) + ua_ty(w) + ((int)(w >> 24) - 1) + (int)(w & 0xFFFFFFu));
+        } else {
+            int t2 = 0, pr2 = -1, ut2 = 0, tx2 = 0, ty2 = 0;
+            const bool bad2 = decodeFwd(launder(cu), launder(lfwd), t2, pr2, ut2, tx2, ty2);
+            keepv((int)pack_ua(t2, ut2, tx2, ty2) + pr2 + (int)bad2);
+        }
+    }
+    // AB_ISSUE: the merged pass once more: the test (scratch only), then the writes (idempotent: the same words to the
+    // same places; the sequence number and the issue index's sums put back)
+    DEV void ablIssueBoth(bool act, bool bad, uint32_t cu, uint32_t adec, int pr) {
+        int q0, q1, d0, d1;
+        keepv((int)issueBothTest(act, launder(cu), launder(adec), launder(pr), q0, q1, d0, d1));
+        const int seqS = seq, sp0 = sumProd0, sp1 = sumProd1, mp0 = maxProd0, mp1 = maxProd1;
+        const bool amp = anyMP;
+        issueBothWrite(act, bad, launder(cu), launder(adec), launder(pr), q0, q1, d0, d1);
+        seq = seqS, sumProd0 = sp0, sumProd1 = sp1, maxProd0 = mp0, maxProd1 = mp1, anyMP = amp;
+    }
+    // AB_ACCEPT: the acceptance chain once more on copies of the running sums (nothing written)
+    DEV void ablAccept(int p, int run0, int run1, bool cand, int rank, int ncand, int t, int pr, int c, uint32_t adec) {
+        int r0 = run0, r1 = run1, ir = 0;
+        const uint64_t a2 = acceptChain(p, r0, r1, cand, launder(rank), ncand, launder(t), launder(pr), launder(c),
+                                        launder(adec), true, ir);
+        keepv(ir + (int)a2 + r0 + r1);
+    }
+    // AB_LEGAL: issueSafe's legality test once more on copies of the row (it rewrites only its arguments)
+    DEV void ablLegal(int l, uint32_t cu, int t, int pr, int tx, int ty, int ut) {
+        int a1 = launder(t), a2 = launder(pr), a3 = launder(tx), a4 = launder(ty), a5 = launder(ut);
+        legality(l, launder(cu), a1, a2, a3, a4, a5);
+        keepv(a1 + a2 + a3 + a4 + a5);
+    }
+    // cycleLanes -----
+    // AB_CYCLERANK: the ready test and the rank by sequence number once more (nothing written)
+    DEV void ablCycleRank(int l, uint32_t a, uint32_t cu, int prm, int sq) {
+        bool rd = false;
+        const uint32_t a2 = launder(a), c2 = launder(cu);
+        const int p2 = launder(prm), q2 = launder(sq);
+        if (l < nu && (a2 & UA_PRESENT))
+            rd = etaFlat(ua_type(a2), p2, ua_ut(a2), utyp(c2)) + launder(at[l]) <= time;
+        int rk = 0;
+        for (uint64_t m = ballot(rd && ua_type(a2) != T_NONE); m; m &= m - 1) rk += rl(q2, __builtin_ctzll(m)) < q2;
+        keepv(rk);
+    }
+    // AB_MOVEBATCH: the lane-parallel MOVE pass once more (the same cells and words written again; no second collision
+    // test)
+    DEV void ablMoveBatch(bool mv, uint32_t cu, int prm, int target) {
+        wsync();
+        if (mv) cell[launder(uy(cu) * W + ux(cu))] = EMPTY;
+        moveBatch(mv, launder(cu), launder(prm), launder(target), false);
+    }
+    // AB_EXECLOOP: the execute loop without its executes (they are not idempotent): each ready item's pick and lane
+    // reads (nothing written)
+    DEV void ablExecLoop(bool wk, int rank, int nw, uint32_t cu, uint32_t a, int prm) {
+        const int rk2 = launder(rank);
+        for (int r = 0; r < nw; r++) {
+            const int k = __builtin_ctzll(ballot(wk && rk2 == r));
+            uint32_t c = uniu((uint32_t)rl((int)cu, k));
+            if ((launder(killedLanes) >> k) & 1ull) c |= UC_DEAD;
+            keepv(c + (uniu((uint32_t)rl((int)a, k)) & ~(UA_READY | UA_PRESENT)) + (uint32_t)rl(prm, k) + (uint32_t)k);
+        }
+    }
+    // the PO renderers -----
+    // AB_COUNT: the render-item counters (contended global atomics: only when counting)
+    DEV void ablCountRender(int l, int n, uint32_t delta) {
+        if (l != 0) return;
+        atomicAdd(&g_dbg[0], (unsigned long long)n);
+        atomicAdd(&g_dbg[1], 1ull);
+        if (delta) atomicAdd(&g_dbg[2], 1ull);
+    }
+    // AB_PO_ZEROSTORE: a rendered chunk's values kept alive in place of their stores
+    DEV void ablKeepChunk(const int (&vv)[4][8]) {
+        int acc = 0;
+#pragma unroll
+        for (int k = 0; k < 8; k++) acc += vv[0][k] ^ vv[1][k] ^ vv[2][k] ^ vv[3][k];
+        keepv(acc);
+    }
+    // writeMasksLanes / writeMasksSteady -----
+    // AB_MASKSETUP: the set-up once more: the same bitmaps cleared and filled again (two: a second slot, pl1's)
+    DEV void ablMaskSetup(uint32_t* nb, int NW, int MW, uint32_t* rows, bool rowB, bool two, int pl0, int pl1) {
+        const int l = lid();
+        wsync();
+        if (l < NW) nb[l] = 0;
+        if (rowB && l < 2 * H) rows[l] = 0;
+        int si2 = -1;
+        uint32_t cu2 = 0;
+        if (l < nu) {
+            cu2 = launder(uc[l]);
+            if (!(cu2 & UC_DEAD) && !(launder(ua[l]) & UA_PRESENT)) {
+                const int op = uplay(cu2);
+                if (op >= 0 && op == pl0) si2 = 0;
+                else if (two && op >= 0 && op == pl1) si2 = 1;
+            }
+        }
+        const int c2 = uy(cu2) * W + ux(cu2);
+        wsync();
+        if (si2 >= 0) atomicOr(&nb[si2 * MW + (c2 >> 5)], 1u << (c2 & 31));
+        if (rowB && l < nu && !(cu2 & UC_DEAD) && uplay(cu2) >= 0) atomicOr(&rows[uplay(cu2) * H + uy(cu2)], 1u << ux(cu2));
+    }
+    // AB_TABLES: maskTables once more (a read of the unit-type table and the players' resources)
+    DEV void ablTables() {
+        const MaskTables T2 = maskTables();
+        keepv(T2.attack1 ^ T2.attackFar ^ T2.harvest ^ T2.move ^ T2.resource ^ T2.stockpile ^ T2.aff0 ^ T2.aff1 ^
+              (uint32_t)T2.prod);
+    }
+    // AB_MASKBITS, writeMasksLanes: a second copy of whichever form ran (qb: the quads' scratch, which the copy fills
+    // with the same words; else registers only)
+    DEV void ablMaskBits(const MaskTables& T, int si, uint32_t cu, int carried, uint32_t* rows, uint32_t* qb) {
+        uint32_t v0 = 0, v1 = 0, v2 = 0;
+        const uint32_t cu2 = launder(cu);
+        if (qb) {
+            wsync();
+            maskBitsQuads(T, launder(si), cu2, launder(carried), rows, v0, v1, v2, qb);
+        } else {
+            if (si >= 0) maskBitsFast(T, cu2, launder(carried), v0, v1, v2);
+            farAttackRows(si >= 0 && ((T.attackFar >> utyp(cu2)) & 1u), cu2, rows, v0, v1, v2);
+        }
+        keepv(v0 ^ v1 ^ v2);
+    }
+    // AB_MASKBITS, writeMasksSteady: the quad's bits once more (registers only)
+    DEV void ablMaskBitsDir(const MaskTables& T, bool qa, bool far, uint32_t qcu, uint32_t qown, int d, uint32_t* rows) {
+        uint32_t u0 = 0, u1 = 0, u2 = 0;
+        const uint32_t qcu2 = launder(qcu);
+        if (qa) maskBitsDir(T, qcu2, (int)(int16_t)launder(qown), d, u0, u1, u2);
+        farAttackRowsDir(far, qcu2, d, rows, u0, u1, u2);
+        keepv(quadOr(u0) ^ quadOr(u1) ^ quadOr(u2));
+    }
+    // AB_POLICY: the row sampled once more into a scratch row (a pure function of seed, step, slot, cell and bits)
+    DEV void ablSample(int slot, uint64_t lo, uint32_t w2, int c) {
+        int32_t a2[7];
+        sampleBitsRaw(D.pol_seed, polStep, D.pol_slot_base + (uint32_t)launder(slot), NT, K,
+                      launder((lo >> 1) | ((uint64_t)w2 << 63)), launder((uint64_t)(w2 >> 1)), launder(c), a2);
+        keepv(a2[0] + a2[1] + a2[2] + a2[3] + a2[4] + a2[5] + a2[6]);
+    }
+    // k_env's step loop -----
+    // AB_NEXTSTEP: nextStep once more, from the same flags; the step counters put back
+    DEV void ablNextStep() {
+        const bool fw = fwdWritten, pl = poLds;
+        nextStep();
+        fwdWritten = fw;
+        poLds = pl;
+        polStep--;
+        uniStep--;
+    }
+    // AB_PRIO: the idle count and the SIMD rank once more on a copy of the rank's state (the same entry posted twice);
+    // rankC, left: the estimate's constant and the steps left (simdRankStep)
+    template <class Rank>
+    DEV void ablPrio(const Rank& srank, int rankC, int left) {
+        const int wq2 = nu + (int)__popcll(ballot(lid() < nu && !(launder(lua) & UA_PRESENT) && uplay(launder(lcu)) >= 0));
+        Rank s2 = srank;
+        s2.seen = launder(s2.seen);
+        keepv(simdRankStep(s2, (uint32_t)(wq2 + rankC) * (uint32_t)left) + (int)s2.seen);
+    }
+    // AB_REWARD (the steady instance): the full write of the reward / done pair once more, whether or not the step's
+    // own store ran (the same values)
+    DEV void ablRewardStores(int slot0, bool gameover, int winner, bool reset) {
+        if (lane_id() < 2) {
+            D.reward[slot0 + lane_id()] = gameover ? (winner == lane_id() ? 1.0 : -1.0) : 0.0;
+            D.done[slot0 + lane_id()] = reset ? 1 : 0;
+        }
+    }
+#endif
 #undef D
 };
 
@@ -5731,7 +5706,8 @@ __global__ __launch_bounds__(HELP ? 128 : 64, (HELP || FIX == 16) ? 4 : 1) void 
         return;
     }
 #ifdef MRTS_ABLATE
-    G.G_AB = g_ablate;
+    G.G_AB = (uint32_t)g_ablate;
+    const auto ab = [&G](int b) { return G.ab(b); };  // (the macros' bit test, as inside Game)
 #endif
     // games [0, n_sp_games) are self-play (mrts_create's layout): no load needed to place the slots
     const bool selfplay = FIX ? true : G.g < D.n_sp_games;
@@ -5768,9 +5744,7 @@ __global__ __launch_bounds__(HELP ? 128 : 64, (HELP || FIX == 16) ? 4 : 1) void 
         }
     } else {
         G.load(D_ON(mask_delta) && D_HAS(masks));
-#ifdef MRTS_ABLATE
-        if (G.ab(AB_LOAD)) G.load(D.mask_delta && D.masks);
-#endif
+        AB_ON(AB_LOAD, G.load(D_ON(mask_delta) && D_HAS(masks)));
     }
     // Multi-step launch (MULTI instances: mrts_rollout_fused_dev on the specialised full-observability
     // self-play shapes): the game runs D.n_iter consecutive fused steps with its state in LDS — each
@@ -5810,16 +5784,7 @@ __global__ __launch_bounds__(HELP ? 128 : 64, (HELP || FIX == 16) ? 4 : 1) void 
     if (HELP && !FPO) __syncthreads();  // A_0: the helper drew step 0's rows
     for (int it = 0; it < niter; it++) {
     if (it > 0) {
-#ifdef MRTS_ABLATE
-        if (G.ab(AB_NEXTSTEP)) {  // once more, from the same flags; the step counters put back
-            const bool fw = G.fwdWritten, pl = G.poLds;
-            G.nextStep();
-            G.fwdWritten = fw;
-            G.poLds = pl;
-            G.polStep--;
-            G.uniStep--;
-        }
-#endif
+        AB_ON(AB_NEXTSTEP, G.ablNextStep());
         G.nextStep();
         freshObs = true;
     }
@@ -5847,14 +5812,7 @@ __global__ __launch_bounds__(HELP ? 128 : 64, (HELP || FIX == 16) ? 4 : 1) void 
             const int wq = G.nu + idle;
             q = wq >= PRIO_T3 ? 3 : wq >= PRIO_T2 ? 2 : wq >= PRIO_T1 ? 1 : 0;
             if (ranked) {  // from the second step on: the rank among the SIMD's waves by remaining work
-#ifdef MRTS_ABLATE
-                if (G.ab(AB_PRIO)) {  // the idle count and the rank once more (the same entry posted twice)
-                    const int wq2 = G.nu + (int)__popcll(ballot(G.lid() < G.nu && !(launder(G.lua) & UA_PRESENT) && uplay(launder(G.lcu)) >= 0));
-                    SimdRank s2 = srank;
-                    s2.seen = launder(s2.seen);
-                    keepv(simdRankStep(s2, (uint32_t)(wq2 + RANK_C) * (uint32_t)(niter - it)) + (int)s2.seen);
-                }
-#endif
+                AB_ON(AB_PRIO, G.ablPrio(srank, RANK_C, niter - it));
                 const int rk = simdRankStep(srank, (uint32_t)(wq + RANK_C) * (uint32_t)(niter - it));
                 if (it > 0) q = 3 - (rk < 3 ? rk : 3);
             }
@@ -6025,12 +5983,10 @@ __global__ __launch_bounds__(HELP ? 128 : 64, (HELP || FIX == 16) ? 4 : 1) void 
         PHASE(4);
         bool gameover;
         int winner;
-#ifdef MRTS_ABLATE
-        if (G.ab(AB_OUTCOME)) {
-            G.outcome(gameover, winner);
-            G.writeRewards(slot0, nslots, selfplay ? 0 : side, selfplay ? 1 : side, gameover, winner);
-        }
-#endif
+        // (in the form it had, writeRewards on the steady instance too — there it writes the WinLoss pair, R = 1 and kind 0
+        // being what a steady launch has: with the pair stored by a member of the copies' section the steady instance
+        // spilled two VGPRs)
+        AB_ON(AB_OUTCOME, G.outcome(gameover, winner); G.writeRewards(slot0, nslots, selfplay ? 0 : side, selfplay ? 1 : side, gameover, winner));
         if (steady) {
             // gameover / winner change only when a unit dies or the game is reset (a PRODUCE adds a unit to a player
             // that has one): carried between the steps of the launch (oc: winner + 1 | gameover << 2, -1 = not known)
@@ -6061,14 +6017,8 @@ __global__ __launch_bounds__(HELP ? 128 : 64, (HELP || FIX == 16) ? 4 : 1) void 
                 D.done[slot0 + lane_id()] = reset ? 1 : 0;
             }
             rwKey = key;
-#ifdef MRTS_ABLATE
-            if (G.ab(AB_REWARD) && lane_id() < 2) {  // the full write once more
-                D.reward[slot0 + lane_id()] = gameover ? (winner == lane_id() ? 1.0 : -1.0) : 0.0;
-                D.done[slot0 + lane_id()] = reset ? 1 : 0;
-            }
-#endif
+            AB_ON(AB_REWARD, G.ablRewardStores(slot0, gameover, winner, reset));
         } else {
-            // (every other instance; writeRewards' own `steady` arms now serve the AB_OUTCOME ablation copy alone)
             const bool done0 = G.writeRewards(slot0, nslots, selfplay ? 0 : side, selfplay ? 1 : side, gameover, winner, it);
             reset = done0 || steps >= D.max_steps;
             if (reset && D.done != nullptr && lane_id() < nslots)
@@ -6108,9 +6058,7 @@ __global__ __launch_bounds__(HELP ? 128 : 64, (HELP || FIX == 16) ? 4 : 1) void 
                     G.packPO(G.scell + (it & 1) * 5 * 64, poHelpHdr + (it & 1) * 4, valid & 3u, 4u);
                     poHelpFlags = 4u;
                 } else
-#ifdef MRTS_ABLATE
-                if (!G.ab(AB_SKIP_OBS))
-#endif
+                AB_SKIP(AB_SKIP_OBS)
                 G.writeObsPOFast2(slot0, valid & 3u);
             } else if (HELP && FPO) {
                 // the helper renders from the live state while this wave waits at B'_it (below)
@@ -6124,21 +6072,15 @@ __global__ __launch_bounds__(HELP ? 128 : 64, (HELP || FIX == 16) ? 4 : 1) void 
             for (int i = 0; i < nslots; i++) {
                 const int p = selfplay ? i : side;
                 if (freshObs) G.snapshot(p);  // PO view of the reset state
-#ifdef MRTS_ABLATE
-                if (!G.ab(AB_SKIP_OBS))
-#endif
+                AB_SKIP(AB_SKIP_OBS)
                 G.writeObsPO(slot0 + i, p, ((valid >> p) & 1u) != 0);
             }
         } else if (HELP) {
             G.packObs(helpBuf + 2 * 2 * 64 + (it & 1) * 2 * 64);  // the helper wave renders it
         } else {
-#ifdef MRTS_ABLATE
-            if (!G.ab(AB_SKIP_OBS))
-#endif
+            AB_SKIP(AB_SKIP_OBS)
             G.writeObsFull(slot0, nslots, side);
-#ifdef MRTS_ABLATE
-            if (G.ab(AB_OBS)) G.writeObsFull(slot0, nslots, side);
-#endif
+            AB_ON(AB_OBS, G.writeObsFull(slot0, nslots, side));
         }
     }
     if (MODE == MODE_STEP && MRTS_UNLIKELY(D_OFF(rec_out) != nullptr) && external) G.writeRecord(it);
@@ -6153,9 +6095,7 @@ __global__ __launch_bounds__(HELP ? 128 : 64, (HELP || FIX == 16) ? 4 : 1) void 
     if (MODE == MODE_STEP && !freshObs && G.deaths) {
         if (MRTS_UNLIKELY(lr)) G.lrCompact();
         G.compact();
-#ifdef MRTS_ABLATE
-        if (steady && G.ab(AB_COMPACT_STEADY)) G.compact();  // once more: no dead slot is left, every unit keeps its place
-#endif
+        if (steady) AB_ON(AB_COMPACT_STEADY, G.compact());  // once more: no dead slot is left, every unit keeps its place
     }
     PHASE(7);
     if (HELP && FPO) {  // a packed step's mask records go to the helper (storeRecordsHelp)
@@ -6194,9 +6134,7 @@ __global__ __launch_bounds__(HELP ? 128 : 64, (HELP || FIX == 16) ? 4 : 1) void 
     if (MODE != MODE_MASKS) {
         wsync();
         G.store();
-#ifdef MRTS_ABLATE
-        if (G.ab(AB_STORE)) G.store();
-#endif
+        AB_ON(AB_STORE, G.store());
         if (MRTS_UNLIKELY(lr)) G.lrStore();
     }
     if (rebalance) {  // post this game's final unit count; the launch's LAST wave writes the next placement
@@ -6271,7 +6209,7 @@ hipError_t laneAudit(int32_t* out, int reset) {
 }
 #endif
 #ifdef MRTS_ABLATE
-hipError_t setAblate(uint32_t v) { return hipMemcpyToSymbol(HIP_SYMBOL(g_ablate), &v, sizeof(v)); }
+hipError_t setAblate(uint64_t v) { return hipMemcpyToSymbol(HIP_SYMBOL(g_ablate), &v, sizeof(v)); }
 hipError_t getDbg(unsigned long long* out, int reset) {
     hipError_t e = hipMemcpyFromSymbol(out, HIP_SYMBOL(g_dbg), sizeof(unsigned long long) * 4);
     if (e == hipSuccess && reset) {

@@ -35,7 +35,7 @@ template <>
 hipError_t laneAuditUnit<2>(int32_t* out, int reset);
 #endif
 #ifdef MRTS_ABLATE
-hipError_t setAblate(uint32_t v);
+hipError_t setAblate(uint64_t v);
 hipError_t getDbg(unsigned long long* out, int reset);
 #endif
 #ifdef MRTS_PHASE_TIMING

@@ -1,7 +1,8 @@
 """Check bodies that more than one test file runs on its own scenarios (a plain helper module: every assert carries
 its own message).  tests/test_gpu_parity.py, test_headline_parity.py, test_forward_model.py and
 test_full_size_every_game.py call them on the standard maps, tests/test_gpu_combat.py on combat maps,
-tests/test_gpu_issue_both.py runs flag_rollout in a child process and tools/soak_long.py runs every_game over longer horizons."""
+tests/test_gpu_issue_both.py and tests/test_gpu_ablate.py run flag_rollout / doubled_rollout in a child process and
+tools/soak_long.py runs every_game over longer horizons."""
 import concurrent.futures as cf
 
 import numpy as np
@@ -132,27 +133,63 @@ def fm_compare(gpu, ref, n, tag, evals=True):
     assert not gpu.error_flags().any(), f"{tag}: error flags {gpu.error_flags()}"
 
 
-def flag_rollout(out):
-    """A 16x16 fused rollout of 200 steps; everything it leaves, to `out` (.npz)"""
+# flag_rollout's shapes: map, launches (steps each), partially observable, max_units, uniform policy without masks
+FLAG_ROLLOUTS = {"16x16 fused": (FUSED_MAP, (1, 19, 80, 100), False, 0, False),
+                 "8x8 uniform": ("maps/8x8/basesWorkers8x8.xml", (1, 19, 40), False, 0, True),
+                 "32x32 PO fused": ("maps/BWDistantResources32x32.xml", (1, 19, 40), True, 256, False)}
+
+
+def flag_rollout(out, shape="16x16 fused", before=None):
+    """A rollout of 32 slots (by default the 16x16 fused one of 200 steps); everything it leaves, to `out` (.npz).
+    before: called once the library is loaded, ahead of the first launch (a diagnostic build's switches)"""
     torch_gpu()
     from microrts_amd import DeviceVecEnv
 
     S = 32
-    env = DeviceVecEnv(S, 0, 2000, [FUSED_MAP] * S, seed=9)
+    mp, launches, po, mu, uniform = FLAG_ROLLOUTS[shape]
+    env = DeviceVecEnv(S, 0, 2000, [mp] * S, seed=9, partial_obs=po, max_units=mu, with_masks=not uniform)
+    if before:
+        before()
     env.reset()
-    env.random_policy(SEED, 0)
+    if not uniform:
+        env.random_policy(SEED, 0)
     res, k = {}, 0
-    for n in (1, 19, 80, 100):
-        env.rollout_fused(SEED, k + 1, n)
+    for n in launches:
+        if uniform:
+            env.rollout_uniform(SEED, k, n)
+        else:
+            env.rollout_fused(SEED, k + 1, n)
         k += n
         env.synchronize()
-        for name in ("obs", "masks", "actions", "reward", "done"):
+        for name in ("obs", "actions", "reward", "done") if uniform else ("obs", "masks", "actions", "reward", "done"):
             res[f"{name}_{k}"] = getattr(env, name).cpu().numpy()
         for s in range(0, S, 2):
             res[f"state_{k}_{s}"] = env.dump_state(s)
     res["flags"] = env.error_flags()
     env.close()
     np.savez(out, **res)
+
+
+def doubled_rollout(out, shape):
+    """tests/test_gpu_ablate.py's child, whose library is the ablation build: flag_rollout with every row of kind AGAIN
+    of the library's own table (mrts_ablate_phase) set — each runs its phase of the step a second time — and the
+    COUNT row, whose render counters show on the partially observable shape that the word reached the kernels"""
+    import ctypes
+
+    from microrts_amd import _lib
+    from tools import ablate_table
+
+    L, phases = ablate_table.load(_lib.LIB_PATH)
+
+    def every_doubling():
+        again = [p for p in phases if p.kind == "AGAIN"]
+        assert len(again) >= 20, again  # (a table that lost its rows cannot pass)
+        assert L.mrts_set_ablate(ablate_table.mask(again + [p for p in phases if p.kind == "COUNT"])) == 0
+
+    flag_rollout(out, shape, before=every_doubling)
+    if FLAG_ROLLOUTS[shape][2]:
+        dbg = (ctypes.c_ulonglong * 4)()
+        assert L.mrts_get_dbg(dbg, 0) == 0 and dbg[1] > 0, f"no render counted: {list(dbg)}"
 
 
 def record_exchange_loopback_ranks(mp, po, spl, world, rank):

@@ -1,7 +1,8 @@
 #!/usr/bin/env python3
 """Diagnostic: VALU / SALU instruction counts and VALU lane utilisation of each k_env phase, from the
-SQ counters of the ablation build (libmrts_ablate.so: g_ablate bit b runs phase b a second time,
-idempotently).  Run under one rocprofv3 --pmc pass:
+SQ counters of the ablation build (libmrts_ablate.so: a bit of g_ablate runs its phase a second time,
+idempotently; the rows of microrts_amd/csrc/mrts_ablate.h, read from the library).  Run under one
+rocprofv3 --pmc pass:
 
   rocprofv3 --pmc SQ_INSTS_VALU SQ_THREAD_CYCLES_VALU SQ_ACTIVE_INST_VALU SQ_INSTS_SALU SQ_INSTS_LDS \
       SQ_WAVE_CYCLES --kernel-trace -T --output-format csv -d OUT -o run -- python3 tools/ablate_sq.py OUT/order.json
@@ -11,7 +12,6 @@ checkpointed after the burn-in; every variant restores it and runs the same K fu
 single-step launch, then one multi-step launch).  tools/ablate_sq_summary.py subtracts the baseline
 launch's counters from each variant's: the counters of one extra copy of that phase.  Instruction
 counts do not depend on timing, so the ablation build's larger register footprint does not matter here."""
-import ctypes
 import json
 import os
 import sys
@@ -20,12 +20,9 @@ ROOT = os.path.dirname(os.path.dirname(os.path.abspath(__file__)))
 sys.path.insert(0, ROOT)
 import torch  # noqa: E402
 
-from microrts_amd import _lib  # noqa: E402
-
-L = _lib.load(os.path.join(ROOT, "microrts_amd", "libmrts_ablate.so"))
-L.mrts_set_ablate.argtypes = [ctypes.c_uint]
+from tools import ablate_table  # noqa: E402
+from tools.ablate_price import L, PHASES, SEED  # noqa: E402  (the library, loaded once, and its table)
 from microrts_amd import DeviceVecEnv  # noqa: E402
-from tools.ablate_price import NAMES, SEED, STEADY_NAMES  # noqa: E402
 
 
 def main():
@@ -46,17 +43,17 @@ def main():
     torch.cuda.synchronize()
     ck = env.checkpoint()
     acts = env.actions.clone()
-    bits = [int(b) for b in os.environ.get("BITS", ",".join(str(b) for b in range(len(NAMES)) if not NAMES[b].startswith("("))).split(",")]
+    variants = ablate_table.selection(PHASES, os.environ.get("BITS"))  # BITS: enum names (AB_...) or bit numbers
     order = []
-    for b in [None] + bits + [None]:
-        assert L.mrts_set_ablate(0 if b is None else 1 << b) == 0
+    for p in [None] + variants + [None]:
+        assert L.mrts_set_ablate(ablate_table.mask([p] if p else [])) == 0
         env.restore(ck)
         env.actions.copy_(acts)
         roll(burn + 1, K)
         torch.cuda.synchronize()
         # (the fused full-observability 16x16 workload's multi-step launch is the steady instance)
         steady = not PO and not UNI and "16x16" in MAP
-        order.append("baseline" if b is None else STEADY_NAMES[b] if steady and b in STEADY_NAMES else NAMES[b])
+        order.append("baseline" if p is None else p.steady_name if steady else p.name)
     L.mrts_set_ablate(0)
     json.dump({"order": order, "K": K, "games": E, "steps_per_multi_launch": K - 1 if not UNI else K}, open(sys.argv[1], "w"))
     env.close()

@@ -60,6 +60,13 @@ WHY = {
              "for lanes k < R and read only from lanes of work ⊂ {k < R}",
     "cycleLanes": "sq / cu / a / prm written for lanes l < nu under `if (l < nu)`; read only from lanes of "
                   "work = ballot(wk) ⊂ {l < nu}, in a uniform loop",
+    "ablCycleRank": "ablation build only, cycleLanes' ready test and rank once more: called from its top level under a "
+                    "wave-uniform test of the ablation word; q2 is a laundered copy of sq on every lane, read from lanes "
+                    "of a ballot ⊂ {l < nu}",
+    "ablExecLoop": "ablation build only, cycleLanes' execute loop without the executes: the same uniform loop over "
+                   "work = ballot(wk), reading cu / a / prm from its lanes",
+    "ablMaskBitsDir": "ablation build only, writeMasksSteady's quad bits once more: quadOr of u0..u2, each set on every "
+                      "lane, in the uniform pass loop under a wave-uniform test of the ablation word",
     "quadOr": "helper: DPP quad_perm OR within each quad — called by maskBitsQuads / writeMasksSteady in uniform flow (outside their lane "
               "tests) with v defined on every lane (0 for lanes without a unit)",
     "maskBitsQuads": "quadOr of v0..v2, each set on every lane (0 unless the lane's quad has a unit) before the calls, in "

@@ -10,12 +10,11 @@ ROOT = os.path.dirname(os.path.dirname(os.path.abspath(__file__)))
 sys.path.insert(0, ROOT)
 import torch  # noqa: E402
 
-from microrts_amd import _lib  # noqa: E402
+from tools import ablate_table  # noqa: E402
 
-L = _lib.load(os.path.join(ROOT, "microrts_amd", "libmrts_ablate.so"))
-L.mrts_get_dbg.argtypes = [ctypes.c_void_p, ctypes.c_int]
-L.mrts_set_ablate.argtypes = [ctypes.c_uint]
-L.mrts_set_ablate(1 << 24)  # AB_COUNT: the render-item counters (contended atomics: diagnostics only)
+L, PHASES = ablate_table.load()
+# the render-item counters (contended atomics: diagnostics only)
+assert L.mrts_set_ablate(ablate_table.mask([ablate_table.by_enum(PHASES, "AB_COUNT")])) == 0
 from microrts_amd import DeviceVecEnv  # noqa: E402
 
 SEED = 0x5EEDC0DE
