@@ -581,8 +581,9 @@ int mrts_env_steps(mrts_env* env, int32_t* out);
 int mrts_get_state_json(mrts_env* env, int32_t slot, char* buf, int32_t cap);
 /* GameState.fromJSON (rts/GameState.java:897-915) into the game behind `slot` (both slots of a
  * self-play game): time, players, units, terrain and assignments from the JSON; envSteps and the
- * cancel counter restart at 0; the game's random streams are kept.  The next mask / policy write of
- * the handle is a full one.  Synchronous. */
+ * cancel counter restart at 0; the game's random streams are kept.  The JSON's terrain holds until the
+ * game's next reset, which loads the env's own map again (its walls too), as Java's does.  The next mask /
+ * policy write of the handle is a full one.  Synchronous. */
 int mrts_set_state_json(mrts_env* env, int32_t slot, const char* json);
 /* Whole-handle checkpoint / resume: every game's state block (including the random streams, envSteps
  * and error flags) behind a small header.  mrts_restore accepts only a checkpoint of an identically

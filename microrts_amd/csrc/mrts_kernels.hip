@@ -2978,7 +2978,7 @@ struct Game {
     }
     // helper-wave launch: the observation's cells for the helper wave to render (lane = cell, HW <= 64),
     // player 0's view: word 0 = hp | resources << 16, word 1 = owner | type << 4 | action << 8 | wall << 12
-    DEV void packObs(uint32_t* buf) const {
+    DEV void packObs(uint32_t* buf, bool terrainToo) const {  // terrainToo: bit 13 of every cell's second word
         const int c = lid();
         if (c < HW) {
             const int sc = cell[c];
@@ -2990,7 +2990,7 @@ struct Game {
             const uint32_t v2 = (occ && pl >= 0) ? (uint32_t)(pl + 1) : 0u, v3 = occ ? (uint32_t)utyp(cu) + 1 : 0u;
             const uint32_t v4 = (occ && (ca & UA_PRESENT)) ? (uint32_t)ua_type(ca) : 0u, v5 = sc == WALL ? 1u : 0u;
             buf[2 * c] = v0 | (v1 << 16);
-            buf[2 * c + 1] = v2 | (v3 << 4) | (v4 << 8) | (v5 << 12);
+            buf[2 * c + 1] = v2 | (v3 << 4) | (v4 << 8) | (v5 << 12) | (terrainToo ? 1u << 13 : 0u);
         }
     }
     // PartiallyObservableGameState.getVectorObservation (rts/PartiallyObservableGameState.java:82-154):
@@ -5392,6 +5392,29 @@ DEV void aiGetAction(GameT& G, int kind, int p) {
     if (kind == GK_RANDOM_BIASED) G.randomBiased(p);
     if (LR && MRTS_UNLIKELY(kind == GK_LIGHT_RUSH)) G.lightRush(p);
 }
+// The in-step auto-reset's terrain: PhysicalGameState.load(mapPath) runs on every reset
+// (JNIGridnetClientSelfPlay.java:221-247, JNIGridnetClient.java:235-258), so the map's own walls come back even where
+// mrts_set_state_json had brought others.  From the template's terrain words `tt`: the walls of the LDS cell map (the
+// template's units, already placed, stand on none), the state block's terrain words `bt`, which the next launch loads,
+// and the terrain plane of the game's `nslots` observations (`obs5`, or null), which a multi-step launch stores with its
+// first observation write only.  Out of line: the path is rare, and inlined it took registers from the step loop.
+__attribute__((noinline)) static __device__ void restoreMapTerrain(uint16_t* cell, const int32_t* tt, int32_t* bt, int32_t* obs5,
+                                                                   int nslots, int slotWords, int HW, int lane) {
+    for (int w = lane; w < (HW + 3) / 4; w += 64) {
+        const uint32_t v = (uint32_t)tt[w];
+        bt[w] = (int32_t)v;
+        for (int b = 0; b < 4; b++) {
+            const int c = 4 * w + b;
+            if (c >= HW) break;
+            const bool wall = ((v >> (8 * b)) & 0xFFu) != 0;
+            if (wall) cell[c] = WALL;
+            else if (cell[c] == WALL) cell[c] = EMPTY;
+            if (obs5)
+                for (int i = 0; i < nslots; i++) obs5[(size_t)i * slotWords + c] = wall ? 1 : 0;
+        }
+    }
+}
+
 template <bool LR = false, class GameT>
 DEV void aiIssue(GameT& G, int kind, int p) {
     if (LR && MRTS_UNLIKELY(kind == GK_LIGHT_RUSH)) G.lrIssue(p);
@@ -5439,7 +5462,9 @@ DEV void helperLoop(const KDyn& D, uint8_t* smem, int g, int niter) {
         const int own = (int)(w1 & 15u);  // player + 1, 0 = none
         int32_t* o0 = D.obs + (size_t)slot0 * D.C * HW;
         const __amdgpu_buffer_rsrc_t rs = bufRsrc(o0, (uint32_t)(2 * D.C * HW * 4));
-        const int npl = k == 0 ? 6 : 5;  // the static terrain plane: first write of the launch only
+        // the static terrain plane: first write of the launch, and the step of an auto-reset (packObs' bit 13: the map's
+        // own walls are back, restoreMapTerrain)
+        const int npl = (k == 0 || ((w1 >> 13) & 1u)) ? 6 : 5;
 #pragma unroll
         for (int i = 0; i < 2; i++) {
             v[2] = own ? ((own - 1 + i) % 2) + 1 : 0;  // ((owner + player) % 2) + 1 (GameState.java:947-949)
@@ -6027,6 +6052,14 @@ __global__ __launch_bounds__(HELP ? 128 : 64, (HELP || FIX == 16) ? 4 : 1) void 
         if (MRTS_UNLIKELY(reset)) {
             G.hset(H_STEPS, 0);  // envSteps[i] = 0 (JNIGridnetVecClient.java:229,264-265,285)
             G.resetFromTemplate();
+            // the walls of the env's own map too, whatever the block held (a state injected as JSON may have brought
+            // other terrain; resetFromTemplate keeps the cell map's walls)
+            // (the 8x8 helper wave is the second writer of its games' observations: there the terrain plane is the
+            // helper's to store, told by this step's pack — packObs(buf, true) below — and no store from here races it)
+            const bool ownObs = D_HAS(obs) && external && !(HELP && !FPO);
+            restoreMapTerrain(G.cell, G.tmpl() + T_TERR, G.st() + stateTerrOff(G.CAP, G.HW),
+                              ownObs ? D.obs + ((size_t)slot0 * D.C + 5) * G.HW : nullptr, nslots, D.C * G.HW, G.HW, G.lid());
+            wsync();
             if (steady) oc = -1;
             if (G.po) G.clearSnap();
             if (MRTS_UNLIKELY(lr)) G.lrClear();  // the auto-reset resets the AIs too (JNIBotClient.java:149-167)
@@ -6076,7 +6109,8 @@ __global__ __launch_bounds__(HELP ? 128 : 64, (HELP || FIX == 16) ? 4 : 1) void 
                 G.writeObsPO(slot0 + i, p, ((valid >> p) & 1u) != 0);
             }
         } else if (HELP) {
-            G.packObs(helpBuf + 2 * 2 * 64 + (it & 1) * 2 * 64);  // the helper wave renders it
+            // the helper wave renders it; after an auto-reset (freshObs) with the terrain plane, as on the first step
+            G.packObs(helpBuf + 2 * 2 * 64 + (it & 1) * 2 * 64, MODE == MODE_STEP && freshObs);
         } else {
             AB_SKIP(AB_SKIP_OBS)
             G.writeObsFull(slot0, nslots, side);

@@ -571,6 +571,13 @@ int oref_dump_state(void* h, int slot, int32_t* buf, int cap) {
 }
 
 int oref_env_steps(void* h, int slot) { return ((VecClient*)h)->envSteps[(size_t)slot]; }
+// next() calls so far on a stream of the env behind `slot`: which = 0 sampler, 1 cancel, 2 damage; -1: no such stream
+int64_t oref_rng_draws(void* h, int slot, int which) {
+    int p;
+    const Env* e = ((VecClient*)h)->slotEnv(slot, &p);
+    const JavaRandom* g[3] = {&e->samplerGen, &e->cancelGen, &e->damageGen};
+    return which >= 0 && which < 3 ? (int64_t)g[which]->draws : -1;
+}
 // GameState.toJSON of the game behind `slot`; returns the length or -(length + 1)
 int oref_state_json(void* h, int slot, char* buf, int cap) {
     int p;

@@ -32,9 +32,11 @@ namespace oref {
 // oracle (and the GPU build) seed them per env — documented divergence.
 struct JavaRandom {
     uint64_t seed = 0;
+    uint64_t draws = 0;  // next() calls since construction (test infrastructure: oref_rng_draws); setSeed keeps it
     explicit JavaRandom(int64_t s = 0) { setSeed(s); }
     void setSeed(int64_t s) { seed = ((uint64_t)s ^ 0x5DEECE66DULL) & ((1ULL << 48) - 1); }
     int32_t next(int bits) {
+        draws++;
         seed = (seed * 0x5DEECE66DULL + 0xBULL) & ((1ULL << 48) - 1);
         return (int32_t)(uint32_t)(seed >> (48 - bits));
     }

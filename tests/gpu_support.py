@@ -4,7 +4,8 @@ carry their own messages, pytest rewrites none of them).
 
 * same(got, want, name, tag)            one tensor against an array or a tensor
 * assert_matches_oracle(env, ref, tag)  a device env against the CPU oracle
-* assert_same_outputs(A, B, tag)        two device envs against each other
+* assert_same_outputs(A, B, tag)        two device envs against each other (or against a Record: one env's
+                                        outputs as they stood at an earlier moment)
 
 tests/test_gpu_support_cpu.py shows on stand-ins that each of them fails on a difference in each output."""
 import ctypes
@@ -94,6 +95,34 @@ def assert_matches_oracle(env, ref, tag, slots=None, masks=0, next_rows=None, re
         got = env._h.env_steps()
         for i, s in enumerate(sl):
             assert int(got[s]) == ref.env_steps(i), f"{tag}: env steps of slot {s}: gpu {int(got[s])} ref {ref.env_steps(i)}"
+
+
+class Record:
+    """Everything assert_same_outputs compares, copied out of a device env as it stands: a later
+    assert_same_outputs(env, record, tag) holds that env (or another) to this moment."""
+
+    def __init__(self, env):
+        env.synchronize()
+        for name in ("obs", "masks", "actions", "source", "reward", "done"):
+            t = getattr(env, name)
+            setattr(self, name, None if t is None else t.clone())
+        self._flags = env.error_flags().copy()
+        self._steps = env._h.env_steps().copy()
+        self.S = env._h.S
+        self._states = {s: env.dump_state(s).copy() for s in range(0, self.S, 2)}
+        self._h = self
+
+    def synchronize(self):
+        pass
+
+    def error_flags(self):
+        return self._flags
+
+    def env_steps(self):
+        return self._steps
+
+    def dump_state(self, s):
+        return self._states[s]
 
 
 def assert_same_outputs(A, B, tag):

@@ -42,6 +42,8 @@ def load():
         L.oref_get_masks.argtypes = [P, I, P]
         L.oref_dump_state.argtypes = [P, I, P, I]
         L.oref_env_steps.argtypes = [P, I]
+        L.oref_rng_draws.restype = ctypes.c_int64
+        L.oref_rng_draws.argtypes = [P, I, I]
         L.oref_errors.argtypes = [P, I]
         L.oref_last_error.restype = ctypes.c_char_p
         L.oref_trace_replay.argtypes = [ctypes.c_char_p, ctypes.c_char_p, ctypes.c_char_p, I]
@@ -181,6 +183,10 @@ class OracleVecClient:
 
     def env_steps(self, slot):
         return self.L.oref_env_steps(self.h, slot)
+
+    def rng_draws(self, slot):
+        """java.util.Random draws so far of the env behind `slot`: (sampler, cancel, damage)."""
+        return tuple(int(self.L.oref_rng_draws(self.h, slot, w)) for w in range(3))
 
     def state_json(self, slot):
         """GameState.toJSON of the game behind `slot` (Java's unit IDs)."""

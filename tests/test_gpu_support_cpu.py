@@ -11,7 +11,7 @@ import torch
 
 from tests import dumps, oracle_py
 from tests.defs import BASE, SEED, WORKER, write_map
-from tests.gpu_support import assert_matches_oracle, assert_same_outputs, same
+from tests.gpu_support import Record, assert_matches_oracle, assert_same_outputs, same
 
 MAP = "maps/8x8/basesWorkers8x8.xml"
 S, STEPS = 4, 25
@@ -197,6 +197,18 @@ def test_twin_comparator_fails_on_each_output(pair, name):
     DAMAGE[name](twin, 2)
     with pytest.raises(AssertionError, match=f"t: {TWIN_OUTPUTS[name]}"):
         assert_same_outputs(env, twin, "t")
+
+
+@pytest.mark.parametrize("name", list(TWIN_OUTPUTS))
+def test_a_record_holds_an_env_to_an_earlier_moment(pair, name):
+    """Record copies: the env it was taken from equals it until one of its outputs changes, whichever it is."""
+    env, ref, rows = pair
+    rec = Record(env)
+    assert_same_outputs(env, rec, "t")
+    assert_same_outputs(Env(ref, rows), rec, "t")
+    DAMAGE[name](env, 2)
+    with pytest.raises(AssertionError, match=f"t: {TWIN_OUTPUTS[name]}"):
+        assert_same_outputs(env, rec, "t")
 
 
 def test_twin_comparator_wants_the_error_flags_unset(pair):
